@@ -221,6 +221,52 @@ def _respawn(a):
     sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this many bytes in all
+DUMP_ROWS = 8192            # rows of the fixed sample taken from an output with more rows than that
+DUMP_SEED = 0
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the result dict of the last timed step as <path>/<key>.npy in float32 (float64 and 32/64-bit integer
+    outputs in float64, which holds them exactly).  An output with more than DUMP_ROWS rows is reduced to a fixed sample of its
+    rows: the first k of np.random.default_rng(DUMP_SEED).permutation(rows), sorted, with k = DUMP_ROWS halved until everything
+    fits in DUMP_BYTES (every smaller sample is a subset of a larger one).  The same arguments give the same inputs, so two
+    builds can be compared key by key."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+
+    def wide(t):
+        return t.dtype in (torch.float64, torch.int32, torch.int64)
+
+    def rows(n, k):
+        if n <= k:
+            return None
+        if n not in picks:
+            picks[n] = np.random.default_rng(DUMP_SEED).permutation(n)
+        return np.sort(picks[n][:k])
+
+    def size(t, k):
+        n = t.shape[0] if t.dim() else 1
+        return min(n, k) * (t.numel() // max(1, n)) * (8 if wide(t) else 4)
+
+    k = DUMP_ROWS
+    while k > 1 and sum(size(t, k) for t in out.values()) > DUMP_BYTES:
+        k //= 2
+    total = 0
+    for name in sorted(out):
+        t = out[name].detach()
+        idx = rows(t.shape[0], k) if t.dim() else None
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if wide(t) else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte budget")
+    return total
+
+
 def _build_commit():
     try:
         with open(os.path.join(ROOT, "mirror_nerf_amd", "BUILD_COMMIT")) as f:
@@ -240,7 +286,12 @@ def main():
     ap.add_argument("--precision", choices=("split", "fp32"), default="split",
                     help="arithmetic of the field kernel's Linears: fp32 operands as hi/lo f16 pairs on the f16 matrix "
                          "pipe (default, ~1e-6 of fp32) or the bit-exact fp32 MFMA chain")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result dict of the last timed frame (rank 0) as DIR/<key>.npy "
+                         "(fixed seeded row sample of the large ones, at most 64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # MNRF_BENCH_LEGS=headline,strong,other,host_maps,fused,train,train_total,config3,hash_grid,rough,trained,config1,cpu : run only
     # these secondary legs (default: all that apply) -- an 8-rank run can be bounded to "headline,strong,train"
     want = os.environ.get("MNRF_BENCH_LEGS")
@@ -306,6 +357,8 @@ def main():
     log, MN.LAUNCH_LOG = MN.LAUNCH_LOG, None
 
     n_mirror = int((out["mirror_mask_fine"] != 0).sum().item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
     out = None
     rays_per_frame = H * W + (H * W if n_mirror > 0 else 0)      # eval.py:159: level 0 traces every ray
     evals_per_ray = N_SAMPLES + (N_SAMPLES + N_IMPORTANCE)

@@ -11,11 +11,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_line_schema():
+def test_bench_line_schema(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["MNRF_BENCH_LEGS"] = "headline,other,train"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                        "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "one JSON line at N = 1"
@@ -36,3 +37,10 @@ def test_bench_line_schema():
     assert len(d["train_ms"]) == 5 and d["train_ms"][0] > 0 and d["train_ms"][0] == d["train_step"]["ms_per_step"]
     assert d["train_route"] == d["train_step"]["route"] == "graph" and 0.05 < d["train_frac"] < 0.3
     assert d["legs_requested"] == ["headline", "other", "train"]
+    # --dump-outputs: the result dict of the timed frame, float32 / float64, at most 64 MB, the frame's colour among them
+    import numpy as np
+    files = sorted(dump.glob("*.npy"))
+    assert files and sum(f.stat().st_size for f in files) <= (64 << 20) + 128 * len(files)     # (+ the .npy headers)
+    arrs = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert arrs["rgb_fine"].ndim == 2 and arrs["rgb_fine"].shape[1] == 3 and np.isfinite(arrs["rgb_fine"]).all()
