@@ -180,6 +180,31 @@ int mnrf_blend_scatter(const float* base, const float* sec, const int32_t* index
                        const float* mask, int64_t n, int c, float* out, float* reflect_out,
                        void* stream);
 
+/* Scene editing (eval.batched_inference applications, round 7).
+ *
+ * Place a new axis-aligned planar mirror into one recursion level (eval.py:364-504, app_place_new_mirror).  Per ray of
+ * rays (n_rays,8): the intersection x of the ray's line with the plane x = position (axis MNRF_PLANE_X; the rectangle bounds
+ * (y, z)) or y = position (MNRF_PLANE_Y; bounds (x, z)), written `t = (position - o_a) / d_a`, `t * d_b + o_b` as the
+ * reference does.  A ray is inside the rectangle when `!(u < rect_u0 || w < rect_w0 || u > rect_u1 || w > rect_w1)` (a NaN
+ * coordinate counts as inside); those rays get normal (n_rays,3) = (normal_x, normal_y, normal_z) in place.  The ones whose
+ * intersection also lies ahead of the origin (`sum((x - o) * d) > 0`) and is not behind the foreground
+ * (`!(|o - x| > depth && depth > near)`, depth of the level before this call, near = the global hyper-parameter) hit the new
+ * mirror: x_surface (n_rays,3) = x and depth (n_rays) = |o - x| in place.  mask (n_rays; thresholded) becomes the merged 0/1
+ * mask `mask != 0 || hit` in place; mask_bool (n_rays, 1 byte per ray, torch.bool) receives the same, null = skip; *any
+ * (int32, device, caller zeroes it, null = skip) is OR-ed with "any merged ray". */
+#define MNRF_PLANE_X 0
+#define MNRF_PLANE_Y 1
+int mnrf_place_mirror(const float* rays, int64_t n_rays, int axis, float position, float normal_x, float normal_y,
+                      float normal_z, float rect_u0, float rect_u1, float rect_w0, float rect_w1, float near,
+                      float* depth, float* mask, float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any,
+                      void* stream);
+
+/* Transform secondary rays (n_rays,8) in place before a reflection-substitution render (eval.py:550-594): with rotation (a
+ * HOST array of 9 floats, row-major R; null = none) o = R o and d = l2_normalize(R d) (utils/func.py:5-7); then
+ * o = o * scale + (tx, ty, tz).  Columns 6..7 (near, far) are left as they are. */
+int mnrf_transform_rays(float* rays, int64_t n_rays, const float* rotation, float scale, float tx, float ty, float tz,
+                        void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

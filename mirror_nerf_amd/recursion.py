@@ -2,15 +2,21 @@
 
   * `NeRFSystem.forward` / `render_rays_chunk_recursively`  -- TRAIN semantics, train.py:102-348
   * `batched_inference`                                      -- EVAL semantics, eval.py:114-172,
-    293-360, 506-548, 614-740 (core path + roughness; the scene-editing demo branches
-    place-mirror / substitution / new-object are out of scope)
+    293-740: the core path, roughness (app_control_mirror_roughness) and the two scene-editing
+    applications that need only MirrorNeRF fields -- a new planar mirror (app_place_new_mirror,
+    eval.py:311-320, 364-504; run.sh MODE 3) and reflection substitution (app_reflection_substitution,
+    eval.py:550-613: the reflections are rendered by a second system).  The new-object branch
+    (app_reflect_newly_placed_objects, eval.py:173-291) is refused: it needs D-NeRF / nerf_pl object
+    models, and cannot run in the reference itself (see _refuse_apps).
 
 Python here is the recursion driver only: mask thresholding, reflected-ray construction,
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
-mnrf_reflect_compact and mnrf_blend_scatter.  One 4-byte device->host read per level decides
+mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror and
+mnrf_transform_rays.  One 4-byte device->host read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
+import ctypes
 import os
 from collections import defaultdict
 from types import SimpleNamespace
@@ -25,28 +31,153 @@ from .rendering import render_rays
 RAY_FORWARD_OFFSET = 0.1   # train.py:232, eval.py:529 (absolute near of a reflected ray)
 JITTER_RAYS = 262144       # rays per batched group of jittered reflections (roughness, eval.py:622-674)
 
+# app_place_new_mirror presets (eval.py:369-433), restated as data: the first entry whose key is a substring of args.root_dir
+# wins (None: the reference's `else`).  position: the plane x = position (plane_x) or y = position (plane_y); rect: the
+# rectangle (u0, u1, w0, w1) on the plane's (y, z) resp. (x, z).  The livingroom plane_y preset assigns position and rectangle
+# twice (eval.py:421-425): the last assignment is the one the reference uses.
+PLACE_MIRROR_PRESETS = {
+    "plane_x": (
+        ("livingroom", dict(position=0.0, normal=(-1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),     # eval.py:370-374
+        ("washroom", dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),      # eval.py:375-378
+        ("office", dict(position=1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),         # eval.py:379-382
+        (None, dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:383-386
+    ),
+    "plane_y": (
+        ("washroom", dict(position=1.3, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -1.0, 1.0))),       # eval.py:416-419
+        ("livingroom", dict(position=1.65, normal=(0.0, -1.0, 0.0), rect=(-0.3, 1.5, -0.5, 1.0))),    # eval.py:420-425
+        ("office", dict(position=0.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),         # eval.py:426-429
+        (None, dict(position=1.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:430-433
+    ),
+}
+# app_reflection_substitution presets (eval.py:551-591): how the reflected rays are moved into the substituted scene.
+# rotation: the 3x3 of the market `pose_align` (its translation column is zero), directions re-normalised after it.
+SUBSTITUTION_PRESETS = (
+    ("office", dict(rotation=None, scale=1.0, translation=(0.0, 1.0, 0.0))),                                 # eval.py:552-554
+    ("market", dict(rotation=((0.0, 1.0, 0.0), (-1.0, 0.0, 0.0), (0.0, 0.0, 1.0)), scale=1.0,
+                    translation=(0.0, 0.0, 0.0))),                                                          # eval.py:555-583
+    (None, dict(rotation=None, scale=1.0, translation=(0.0, 0.0, 0.0))),                                    # eval.py:584-586
+)
+
+
+def _preset(table, root_dir):
+    for key, value in table:
+        if key is None or key in (root_dir or ""):
+            return dict(value)
+    raise AssertionError("preset tables end with a default entry")
+
+
+def resolve_new_mirror(args, new_mirror=None):
+    """The plane of app_place_new_mirror: dict(axis="x"|"y", position, normal (3,), rect (u0, u1, w0, w1)).  `new_mirror`
+    (same keys) overrides the preset that args.plane_pos / args.root_dir select (eval.py:369-433)."""
+    if new_mirror is not None:
+        nm = dict(new_mirror)
+        missing = {"axis", "position", "normal", "rect"} - set(nm)
+        if missing:
+            raise ValueError(f"new_mirror needs the keys axis, position, normal, rect (missing: {sorted(missing)})")
+        if nm["axis"] not in ("x", "y"):
+            raise ValueError(f"new_mirror axis must be 'x' or 'y', not {nm['axis']!r}")
+        if len(nm["normal"]) != 3 or len(nm["rect"]) != 4:
+            raise ValueError("new_mirror normal has 3 entries and rect 4 (u0, u1, w0, w1)")
+        return dict(axis=nm["axis"], position=float(nm["position"]), normal=tuple(float(v) for v in nm["normal"]),
+                    rect=tuple(float(v) for v in nm["rect"]))
+    plane_pos = getattr(args, "plane_pos", "plane_x")            # eval.py get_opt: default plane_x
+    if plane_pos not in PLACE_MIRROR_PRESETS:
+        raise ValueError(f"args.plane_pos must be 'plane_x' or 'plane_y', not {plane_pos!r}")
+    p = _preset(PLACE_MIRROR_PRESETS[plane_pos], getattr(args, "root_dir", ""))
+    return dict(axis=plane_pos[-1], **p)
+
+
+def resolve_substitution(args):
+    """The ray transform of app_reflection_substitution chosen by args.root_dir (eval.py:551-591)."""
+    return _preset(SUBSTITUTION_PRESETS, getattr(args, "root_dir", ""))
+
+
+def _refuse_apps(args, models, kwargs):
+    """The application flags batched_inference cannot honour, refused up front with the reason."""
+    if getattr(args, "app_reflect_newly_placed_objects", False):
+        raise NotImplementedError(
+            "app_reflect_newly_placed_objects is not supported: it needs D-NeRF / nerf_pl object models, and the reference "
+            "cannot run it either (pose_align is always None there, so pose_scale at eval.py:264 is never bound: "
+            "UnboundLocalError)")
+    place = bool(getattr(args, "app_place_new_mirror", False))
+    subst = bool(getattr(args, "app_reflection_substitution", False))
+    if not (place or subst):
+        return
+    which = "app_place_new_mirror" if place else "app_reflection_substitution"
+    if getattr(args, "app_control_mirror_roughness", False):
+        raise ValueError(f"app_control_mirror_roughness cannot be combined with {which} (one application at a time, except "
+                         "place-mirror with substitution)")
+    if not any(getattr(m, "predict_mirror_mask", False) for m in models.values()):
+        raise ValueError(f"{which} needs a mirror-mask head (predict_mirror_mask=True): the new mirror is merged into the "
+                         "predicted mirror mask, and substitution replaces what the mask marks")
+    if subst and kwargs.get("system_substitution") is None:
+        raise ValueError("app_reflection_substitution needs system_substitution= (an object with .models and .embeddings, "
+                         "the radiance field rendered in the mirrors)")
+    if place and getattr(args, "near", None) is None:
+        raise ValueError("app_place_new_mirror needs args.near: the foreground test compares the depth with it (eval.py:169-171)")
+
+
+def _place_mirror(r, rays_chunk, sel, plane, near, flag):
+    """eval.py:364-504 on one level's maps, in place (mnrf_place_mirror); `flag` (device int32) is OR-ed with "any mirror
+    after the merge".  The returned mirror mask becomes the merged bool tensor (eval.py:492-496), and depth_fine the edited
+    depth (eval.py:497-500)."""
+    N = rays_chunk.shape[0]
+    for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
+        if k in r and not r[k].is_contiguous():
+            r[k] = r[k].contiguous()
+    mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
+    mask, depth, normal = r[mkey], r[f"depth_{sel}"], _pick_normal(r, sel)
+    merged = torch.empty(N, dtype=torch.bool, device=rays_chunk.device)
+    p = _lib.ptr
+    nx, ny, nz = plane["normal"]
+    u0, u1, w0, w1 = plane["rect"]
+    _lib.check(_lib.lib().mnrf_place_mirror(
+        p(rays_chunk), N, 1 if plane["axis"] == "y" else 0, plane["position"], nx, ny, nz, u0, u1, w0, w1, float(near),
+        p(depth), p(mask), p(normal), p(r[f"x_surface_{sel}"]), ctypes.c_void_p(merged.data_ptr()), p(flag), _lib.stream()),
+        "mnrf_place_mirror")
+    r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
+    if "depth_fine" in r:
+        r["depth_fine"] = depth
+    elif "depth_coarse" in r:
+        r["depth_coarse"] = depth
+    return mask
+
+
+def _transform_rays(sec, xform):
+    """eval.py:551-594 in place on the (M,8) secondary rays (mnrf_transform_rays)."""
+    rot = xform["rotation"]
+    rot = (ctypes.c_float * 9)(*[float(v) for row in rot for v in row]) if rot is not None else None
+    tx, ty, tz = xform["translation"]
+    _lib.check(_lib.lib().mnrf_transform_rays(_lib.ptr(sec), sec.shape[0], rot, float(xform["scale"]), tx, ty, tz, _lib.stream()),
+               "mnrf_transform_rays")
+
 
 def _f(dev, *s):
     return torch.empty(*s, dtype=torch.float32, device=dev)
 
 
-def _threshold_(mask, want_any=True):
+def _threshold_(mask, want_any=True, edit=None):
     """In place m[m>0.5]=1, m[m<0.5]=0 (exactly 0.5 untouched); returns any(m != 0) as a bool.
-    want_any=False skips the device->host read of the flag (a stream sync) when the caller does not branch on it."""
+    want_any=False skips the device->host read of the flag (a stream sync) when the caller does not branch on it.
+    edit(flag): launched behind the threshold (the new mirror of app_place_new_mirror), may OR into the flag."""
     n = mask.shape[0]
     flag = torch.full((1,), 0, dtype=torch.int32, device=mask.device)      # (not torch.zeros: that is a memset, ~40 us of idle GPU)
     if n:
         _lib.check(_lib.lib().mnrf_threshold_mask(_lib.ptr(mask), n, _lib.ptr(flag), _lib.stream()),
                    "mnrf_threshold_mask")
+        if edit is not None:
+            edit(flag)
     return bool(flag.item()) if want_any else False
 
 
-def _threshold_async(mask, host_flags, slot):
+def _threshold_async(mask, host_flags, slot, edit=None):
     """_threshold_ without the stream sync: the flag travels to pinned host memory behind the kernel and an event marks its
     arrival; `_flag_ready` waits for THAT event only, so launches queued meanwhile (the next chunk's primary pass) keep
     the GPU busy."""
     flag = torch.full((1,), 0, dtype=torch.int32, device=mask.device)      # (not torch.zeros: that is a memset, ~40 us of idle GPU)
     _lib.check(_lib.lib().mnrf_threshold_mask(_lib.ptr(mask), mask.shape[0], _lib.ptr(flag), _lib.stream()), "mnrf_threshold_mask")
+    if edit is not None:
+        edit(flag)
     host = host_flags[slot:slot + 1]
     host.copy_(flag, non_blocking=True)
     ev = torch.cuda.Event()
@@ -386,13 +517,23 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     x_surface, ~100 B/ray instead of ~3 KB/ray of per-sample tensors nobody downstream of eval.py:743-894 reads -- on
     the CPU), batch_jitter (roughness: render the trace_ray_times jittered reflections of a level in groups through one
     recursion call each instead of one by one; default on unless draws are injected),
-    _normal_noise (iterator of pre-drawn (n,3) standard-normal tensors, for tests)."""
+    _normal_noise (iterator of pre-drawn (n,3) standard-normal tensors, for tests).
+
+    Applications (the reference's flags, unchanged): args.app_place_new_mirror with args.plane_pos / args.root_dir (the
+    preset, PLACE_MIRROR_PRESETS) and args.near -- every level below max_recursive_level traces, the new mirror is merged into
+    the mirror mask right behind the threshold (mnrf_place_mirror), `new_mirror=dict(axis=, position=, normal=, rect=)`
+    overrides the preset; args.app_reflection_substitution with system_substitution= (.models, .embeddings): the level-0
+    reflections are moved by the args.root_dir preset (SUBSTITUTION_PRESETS, mnrf_transform_rays) and rendered once by
+    that system.  Both may be combined, as in the reference."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
-    for flag in ("app_place_new_mirror", "app_reflection_substitution", "app_reflect_newly_placed_objects"):
-        if getattr(args, flag, False):
-            raise NotImplementedError(f"{flag}: scene-editing demo branches are out of scope")
+    _refuse_apps(args, models, kwargs)
+    place = bool(getattr(args, "app_place_new_mirror", False))
+    subst = bool(getattr(args, "app_reflection_substitution", False))
+    plane = resolve_new_mirror(args, kwargs.get("new_mirror")) if place else None
+    xform = resolve_substitution(args) if subst else None
+    system_sub = kwargs.get("system_substitution") if subst else None
     trace_flag = kwargs.get("trace_secondary_rays", False)
     test_time = kwargs.get("test_time", True)
     white_back = kwargs.get("white_back", False)
@@ -437,14 +578,18 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                 mask = r[key]
                 break
         # in place (eval.py:303-307); at the last level nothing branches on "any mirror pixel": no host read, so the next
-        # chunk's launches queue behind this pass without a stream sync
-        last = level >= args.max_recursive_level or not trace_flag
+        # chunk's launches queue behind this pass without a stream sync.  A new mirror (eval.py:311-320) makes every level
+        # below the last one trace; it is merged into the mask right behind the threshold, and its flag is the one read.
+        last = level >= args.max_recursive_level or not (trace_flag or place)
+        edit = None
+        if place and not last:
+            edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
         pending, any_mirror = None, False
         if mask is not None:
             if host_flags is not None and not last and rays_chunk.shape[0]:
-                pending = _threshold_async(mask, host_flags, slot)
+                pending = _threshold_async(mask, host_flags, slot, edit)
             else:
-                any_mirror = _threshold_(mask, want_any=not last)
+                any_mirror = _threshold_(mask, want_any=not last, edit=edit)
         return r, rays_chunk, level, mask, any_mirror, pending
 
     def recurse(rays_chunk, level):
@@ -457,7 +602,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         N = rays_chunk.shape[0]
         dev = rays_chunk.device
         only_in = not (level < 1)                                         # eval.py:159
-        trace = bool(mask is not None and any_mirror and trace_flag)
+        trace = bool(mask is not None and any_mirror and (trace_flag or place))     # eval.py:311-320, 503-504
         if level >= args.max_recursive_level:
             trace = False
         if not trace or N == 0:
@@ -469,7 +614,17 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         sec, index, rdir = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, only_in, nn0, noise_std)
         r["reflect_direction"] = rdir
         if sec.shape[0] > 0:
-            r2 = recurse(sec.contiguous(), level + 1)
+            if subst:                                                     # eval.py:550-613: no recursion below
+                _transform_rays(sec, xform)
+                # only rgb / depth of this render are read (eval.py:676-697): the maps-only path, without the density-gradient
+                # normals the reference also computes for it
+                r2 = render_rays(system_sub.models, system_sub.embeddings, sec.contiguous(), N_samples, use_disp, 0, 0,
+                                 N_importance, chunk, white_back, test_time=test_time, compute_normal=False,
+                                 only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
+                                 current_epoch=fine_epoch + 1, _guard=False,
+                                 _maps_only=os.environ.get("MNRF_FUSED_EVAL", "1") != "0")
+            else:
+                r2 = recurse(sec.contiguous(), level + 1)
             if rough:                                                     # eval.py:622-674
                 times = args.trace_ray_times
                 if batch_jitter and times > 0:
@@ -564,10 +719,11 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         torch.cuda.current_stream().synchronize()
     # range guard of the split arithmetic, once per call (= per frame): a tripped model is on the fp32 kernels now
     from .mirror_nerf import check_guard, release_transient
-    if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard([m for m in models.values()]):
+    guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else [])
+    if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard(guarded):
         try:
             return batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk,
                                      **dict(kwargs, _guard_retry=True))
         finally:
-            release_transient(list(models.values()))      # (a range-only trip: this frame on fp32, the next one on split again)
+            release_transient(guarded)      # (a range-only trip: this frame on fp32, the next one on split again)
     return {k: torch.cat(v, 0) for k, v in results.items()}
