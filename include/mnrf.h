@@ -111,6 +111,11 @@ int mnrf_pack_weights(const float* const* params, float* packed, void* stream);
 /* The same for n_models models at once (a training step re-packs its coarse and its fine model behind every optimizer step: one
  * launch pair instead of one per model): params = n_models x 32 pointers, model after model; packed = n_models images. */
 int mnrf_pack_weights_n(int n_models, const float* const* params, float* const* packed, void* stream);
+/* Folded forward stream of n_models packed images (same arguments as mnrf_pack_weights_n): normal_net's two Linears as one map,
+ * xyz_encoding_final folded into dir_encoding, formed in fp64 on the GPU.  The full forward-only split launches (mnrf_field_forward
+ * with MNRF_SPLIT_F16 and neither MNRF_SIGMA_ONLY nor MNRF_GRAD_NORMAL, mnrf_field_composite_fused) read it: call this after
+ * every mnrf_pack_weights* of an image and before its first such launch.  No-op under MNRF_SPLIT32=1. */
+int mnrf_fold_weights_n(int n_models, const float* const* params, float* const* packed, void* stream);
 
 /* Embedding.forward (models/mirror_nerf.py:20-38): x (n, c) -> out (n, c*(2*n_freqs+1)). */
 int mnrf_embed(const float* x, int64_t n, int c, int n_freqs, float* out, void* stream);

@@ -47,6 +47,7 @@ SIGNATURES = {
     "mnrf_packed_floats": (_i64, []),
     "mnrf_pack_weights": (_int, [ctypes.POINTER(ctypes.c_void_p), _c_f, _str]),
     "mnrf_pack_weights_n": (_int, [_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _str]),
+    "mnrf_fold_weights_n": (_int, [_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _str]),
     "mnrf_embed": (_int, [_c_f, _i64, _int, _int, _c_f, _str]),
     "mnrf_field_forward": (_int, [_c_f, _u32, _i64, _c_f, _i64, _c_f, _c_f, _int, _c_f, _i64,
                                   _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _str]),

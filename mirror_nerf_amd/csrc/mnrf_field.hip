@@ -167,6 +167,24 @@ extern "C" int mnrf_pack_weights_n(int n_models, const float* const* params, flo
     return mnrf_check_launch("mnrf_pack_weights");
 }
 
+// The folded forward stream (mnrf_layout.h OFF_FOLD_FWD) is built by its own entry point and not by every pack: the captured
+// training step re-packs both models behind every optimizer step and never runs a forward-only launch -- built there, it cost the
+// step 2 % (A/B, alternating).  A no-op under MNRF_SPLIT32=1 (the region holds the 32x32x16 stream then).
+extern "C" int mnrf_fold_weights_n(int n_models, const float* const* params, float* const* packed, void* stream) {
+    if (n_models < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: negative model count");
+    if (n_models == 0 || split32_enabled()) return MNRF_OK;
+    if (!params || !packed) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: null pointer");
+    for (int i = 0; i < n_models * MNRF_N_PARAMS; ++i)
+        if (!params[i]) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: null parameter pointer");
+    for (int m = 0; m < n_models; ++m)
+        if (!packed[m]) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: null image pointer");
+    for (int m0 = 0; m0 < n_models; m0 += PACK_BATCH) {
+        const int nb = n_models - m0 < PACK_BATCH ? n_models - m0 : PACK_BATCH;
+        launch_split_fold(params + m0 * MNRF_N_PARAMS, packed + m0, nb, (hipStream_t)stream);
+    }
+    return mnrf_check_launch("mnrf_fold_weights");
+}
+
 extern "C" int mnrf_pack_weights(const float* const* params, float* packed, void* stream) {
     if (!params || !packed) return mnrf_fail(MNRF_ERR_ARG, "mnrf_pack_weights: null pointer");
     return mnrf_pack_weights_n(1, params, &packed, stream);
@@ -204,6 +222,7 @@ extern "C" int mnrf_field_forward(float* packed, unsigned flags, int64_t B, cons
     const int rc = variant >= 3 ? launch_split(A, sigma_only, grad, variant - 3, (hipStream_t)stream)
                  : variant == 1 ? s1::launch(A, sigma_only, grad, (hipStream_t)stream)
                                 : s2::launch(A, sigma_only, grad, (hipStream_t)stream);
+    if (rc == -2) return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_forward: a forced h2 / hx forward variant needs the folded stream (MNRF_SPLIT32 unset)");
     if (rc != 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_forward: too many samples for one launch");
     return mnrf_check_launch("mnrf_field_forward");
 }

@@ -106,6 +106,9 @@ struct FieldBwd2Args {
 int launch_split(const FieldArgs& A, bool sigma_only, bool grad, int variant, hipStream_t s);
 // builds the split streams of a packed image from its fp32 streams (same stream, after pack_kernel)
 void launch_split_pack(float* const* packed, int n_images, hipStream_t s);      // up to 4 images per launch
+// builds the folded forward stream and its bias block (mnrf_layout.h OFF_FOLD_*) from the split stream and the fp32 bias block of
+// each image and from its state_dict-ordered parameter pointers (n_images x 32 of them); same stream, after launch_split_pack
+void launch_split_fold(const float* const* params, float* const* packed, int n_images, hipStream_t s);      // up to 4 images
 int launch_split_bwd(const FieldBwdArgs& A, hipStream_t s);
 // 32x32x16 tuning of the forward-only split kernels (mnrf_field_split32.hip) and the packer of its stream (from the
 // state_dict-ordered parameter pointers)

@@ -56,6 +56,9 @@ int launch_split(const FieldArgs& A, bool sigma_only, bool grad, int variant, hi
     // (a third less LDS-DMA per sample): it needs all 512 registers, spills 200 bytes and ends up 1 % slower.
     // MNRF_SPLIT32=1: the forward-only launches on the 32x32x16 tuning (mnrf_field_split32.inc)
     if (!grad && variant == 0 && split32_enabled()) return launch_split32(A, sigma_only, s);
+    // the full forward-only kernels read the folded stream (mnrf_layout.h OFF_FOLD_FWD), whose region holds the 32x32x16 stream
+    // instead under MNRF_SPLIT32=1: a forced h2 / h2x variant cannot run there
+    if (!grad && !sigma_only && split32_enabled()) return -2;
     // default of the forward-only launches: 48 samples per wave (mnrf_field_split3.hip); geo_feat needs both halves of L8
     // in registers, which that tuning cannot afford
     if (!grad && variant == 0 && !A.geo_feat && split48_enabled()) return launch_split48(A, sigma_only, s);
@@ -146,6 +149,104 @@ void launch_split_pack(float* const* packed, int n_images, hipStream_t s) {     
     for (int m = 0; m < n_images; ++m) I.packed[m] = packed[m];
     const long long n = (long long)(SPLIT_FWD_PAIRS + SPLIT_BWD_PAIRS + SPLIT_HBWD_PAIRS) * 64;
     hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((n + 255) / 256), n_images), dim3(256), 0, s, I, T);
+}
+
+// ------------------------------------------------------------------ folded forward stream (mnrf_layout.h OFF_FOLD_*)
+// One thread per lane of a pair of the folded stream, then one per float of its bias block.  Pairs that are not folded are
+// copied from the split stream (so sigma, the mirror head, the view columns and rgb carry the very same halves); a folded weight
+// is a fixed-order fp64 dot product over the parameters, split as hi = f16(w), lo = f16(w - hi) from the fp64 value.  Half j of
+// lane l of pair (T, nb) is W[16 nb + (l & 15)][32 T + 16 (j >> 2) + 4 (l >> 4) + (j & 3)] (mnrf_layout.h, KIND_H columns).
+struct FoldImages {
+    float* packed[4];
+    const float* wfin[4];      // xyz_encoding_final.weight  [256][256]
+    const float* wdir[4];      // dir_encoding.weight        [128][283]
+    const float* wn1[4];       // normal_net.0.weight        [128][256]
+    const float* wn2[4];       // normal_net.1.weight        [3][128]
+};
+__global__ void split_fold_kernel(FoldImages I) {
+    float* packed = I.packed[blockIdx.y];
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    constexpr long long FOLD_LANES = (long long)SPLIT_FOLD_PAIRS * 64;
+    if (q >= FOLD_LANES + BIAS_FLOATS) return;
+    const float* bias = packed + OFF_BIAS;
+    if (q >= FOLD_LANES) {
+        // ---- bias block: a copy, the folded biases in place (fp64 dot product, then the second bias, then one rounding)
+        const int b = (int)(q - FOLD_LANES);
+        float v = bias[b];
+        if (b > BIAS_SIG && b <= BIAS_SIG + 3) {
+            const int i = b - BIAS_SIG - 1;
+            const float* w2 = I.wn2[blockIdx.y] + i * 128;
+            double a = 0.0;
+            for (int k = 0; k < 128; ++k) a = fma((double)w2[k], (double)bias[BIAS_NRM1 + k], a);
+            v = (float)(a + (double)bias[BIAS_NRM2 + i]);
+        } else if (b >= BIAS_DIR && b < BIAS_DIR + 128) {
+            const float* wd = I.wdir[blockIdx.y] + (b - BIAS_DIR) * (W + ENC_DIR);
+            double a = 0.0;
+            for (int k = 0; k < W; ++k) a = fma((double)wd[k], (double)bias[BIAS_FIN + k], a);
+            v = (float)(a + (double)bias[b]);
+        }
+        packed[OFF_FOLD_BIAS + b] = v;
+        return;
+    }
+    const int pair = (int)(q >> 6);
+    const int lane = (int)(q & 63);
+    const int row = lane & 15;
+    typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+    h8v hi, lo;
+    for (int j = 0; j < 8; ++j) hi[j] = lo[j] = (_Float16)0.f;
+    // source pair in the split stream: trunk and sigma block (its rows 1..3 are replaced below), mirror head, view columns and rgb
+    const int sp = pair < 968 ? pair : (pair < 1036 ? pair + (1036 - 968) : (pair >= 1100 && pair < 1112 ? pair + (1296 - 1100) : -1));
+    if (sp >= 0) {
+        const char* src = (const char*)(packed + OFF_SPLIT_FWD) + (long long)sp * PAIR_BYTES + lane * 16;
+        hi = *(const h8v*)src;
+        lo = *(const h8v*)(src + PAIR_BYTES / 2);
+    }
+    const bool fold_nrm = pair >= 960 && pair < 968 && row >= 1 && row <= 3;
+    const bool fold_dir = pair >= 1036 && pair < 1100;
+    if (fold_nrm || fold_dir) {
+        const int T = fold_nrm ? pair - 960 : (pair - 1036) / 8;
+        const int c0 = 32 * T + 4 * (lane >> 4);      // columns c0 + 0..3 (halves 0..3) and c0 + 16 + 0..3 (halves 4..7)
+        // out[n][c] = sum_k A[n][k] B[k][c], k ascending
+        const float* a = fold_nrm ? I.wn2[blockIdx.y] + (row - 1) * 128 : I.wdir[blockIdx.y] + (16 * ((pair - 1036) % 8) + row) * (W + ENC_DIR);
+        const float* bm = fold_nrm ? I.wn1[blockIdx.y] : I.wfin[blockIdx.y];
+        const int K = fold_nrm ? 128 : W;
+        double acc[8];
+        for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double ak = (double)a[k];
+            const float* bk = bm + (long long)k * W + c0;      // (scalar reads: a parameter may be a view at any offset)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                acc[c] = fma(ak, (double)bk[c], acc[c]);
+                acc[4 + c] = fma(ak, (double)bk[16 + c], acc[4 + c]);
+            }
+        }
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            hi[j] = (_Float16)acc[j];
+            lo[j] = (_Float16)(acc[j] - (double)hi[j]);
+            bad |= !(fabs(acc[j]) < 65504.0);      // inf / nan / out of range, as for every other weight
+        }
+        if (bad) atomicOr((unsigned*)(packed + PACKED_FLOATS - 1), MNRF_GUARD_WEIGHT);
+    }
+    char* dst = (char*)(packed + OFF_FOLD_FWD) + (long long)pair * PAIR_BYTES + lane * 16;
+    *(h8v*)dst = hi;
+    *(h8v*)(dst + PAIR_BYTES / 2) = lo;
+}
+
+void launch_split_fold(const float* const* params, float* const* packed, int n_images, hipStream_t s) {      // n_images <= 4
+    FoldImages I{};
+    for (int m = 0; m < n_images; ++m) {
+        const float* const* p = params + m * 32;
+        I.packed[m] = packed[m];
+        I.wfin[m] = p[16];
+        I.wdir[m] = p[18];
+        I.wn1[m] = p[24];
+        I.wn2[m] = p[26];
+    }
+    const long long n = (long long)SPLIT_FOLD_PAIRS * 64 + BIAS_FLOATS;
+    hipLaunchKernelGGL(split_fold_kernel, dim3((unsigned)((n + 255) / 256), n_images), dim3(256), 0, s, I);
 }
 
 }  // namespace mnrf

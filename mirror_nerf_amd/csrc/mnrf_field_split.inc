@@ -553,10 +553,15 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // inside the MFMA streams (gemm_part_impl STB); the smaller sections (encoding, heads) still go out between the GEMMs
 // FUSE (eval, maps only; S = 3: one ray of 192 samples per workgroup): the head outputs stay in LDS and wave 0 composites the
 // ray at the end -- no per-sample tensor reaches HBM (36 B per sample written and read back otherwise)
+// FOLD (every full forward-only kernel): the folded stream (mnrf_layout.h OFF_FOLD_FWD) -- normal_net as one 3 x 256 map in rows
+// 1..3 of the sigma block, xyz_encoding_final folded into dir_encoding's h8 columns: 1112 instead of 1308 pairs per sample.  The
+// kernels that keep activations for a backward pass (GRAD) need the unfolded heads; the sigma-only ones stay on the split stream
+// (same trunk, same sigma row).
 template <bool SIGMA_ONLY, bool GRAD, bool PLANES = false, bool FUSE = false>
 __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_kernel(FieldArgs A) {
     static_assert(!PLANES || (GRAD && !SIGMA_ONLY && S == 2), "operand planes: the training forward (32 samples per wave)");
     static_assert(!FUSE || (S == 3 && !SIGMA_ONLY && !GRAD), "ray-fused compositing: the 192-sample fine pass");
+    constexpr bool FOLD = !SIGMA_ONLY && !GRAD;
     float* const fz = (float*)(smem + LDS_FUSE);      // FUSE: [9][WG_SAMPLES]
     // Dynamic tile queue (S = 3, FieldArgs::tile_queue): the launch has one workgroup per CU; the first tile is the workgroup's
     // own id, every further one comes from the global counter -- requested at the START of the tile before, parked in LDS
@@ -576,7 +581,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     int round = 0;
     unsigned long long sat_all = 0, enc_all = 0;
     {   // bias block -> LDS (read by init_bias behind the __syncthreads() below)
-        const f32x4* src = (const f32x4*)(A.packed + OFF_BIAS);
+        const f32x4* src = (const f32x4*)(A.packed + (FOLD ? OFF_FOLD_BIAS : OFF_BIAS));
         f32x4* dst = (f32x4*)(smem + LDS_BIAS);
         for (int i = threadIdx.x; i < BIAS_FLOATS / 4; i += WG_THREADS) dst[i] = src[i];
     }
@@ -636,7 +641,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     Stream st;
     st.sat = 0;
     st.tmax = 0.f;
-    open_stream<true>(st, A.packed + OFF_SPLIT_FWD, wave, lane);
+    open_stream<true>(st, A.packed + (FOLD ? OFF_FOLD_FWD : OFF_SPLIT_FWD), wave, lane);
     int next_tile = 0;
     if (queued && tid == 0) next_tile = (int)gridDim.x + atomicAdd(A.tile_queue, 1);
 
@@ -882,7 +887,34 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
 #endif
     }
     MNRF_MARK(5);   // L6..L8
-    // ---- sigma: 256 -> 1 (row 0 of a padded 16-row block lives in lane group 0, reg 0)
+    // predicted normal = l2_normalize of registers R0 .. R0 + 2 of lane group 0 (mirror_nerf.py:85-88)
+    const auto put_normal = [&](const f32x4 (&acc)[S][1], auto r0) {
+        constexpr int R0 = decltype(r0)::value;
+        if (FUSE) {
+            if (gq() == 0) {
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    const float a0 = acc[s][0][R0], a1 = acc[s][0][R0 + 1], a2 = acc[s][0][R0 + 2];
+                    const float inv = 1.f / sqrtf(fmaxf(a0 * a0 + a1 * a1 + a2 * a2, 1.1920928955078125e-07f));
+                    const int q = wave * (S * 16) + s * 16 + (int)m15();
+                    fz[4 * WG_SAMPLES + q] = a0 * inv; fz[5 * WG_SAMPLES + q] = a1 * inv; fz[6 * WG_SAMPLES + q] = a2 * inv;
+                }
+            }
+        } else if (A.pred_normal && g == 0) {
+#pragma unroll
+            for (int s = 0; s < S; ++s)
+                if (sval(s)) {
+                    const float a0 = acc[s][0][R0], a1 = acc[s][0][R0 + 1], a2 = acc[s][0][R0 + 2];
+                    // utils/func.py:5-7: eps clamps the squared norm
+                    const float inv = 1.f / sqrtf(fmaxf(a0 * a0 + a1 * a1 + a2 * a2, 1.1920928955078125e-07f));
+                    float* o = A.pred_normal + (long long)sidx(s) * 3;
+                    out_store(o, a0 * inv); out_store(o + 1, a1 * inv); out_store(o + 2, a2 * inv);
+                    if (GRAD && A.save_inv)   // negative marks the clamped branch (constant denominator)
+                        A.save_inv[idx[s]] = (a0 * a0 + a1 * a1 + a2 * a2) > 1.1920928955078125e-07f ? inv : -inv;
+                }
+        }
+    };
+    // ---- sigma: 256 -> 1 (row 0 of a padded 16-row block lives in lane group 0, reg 0); FOLD: the folded normal_net in rows 1..3
     {
         f32x4 acc[S][1];
         init_bias<1>(acc, BIAS_SIG, gq());
@@ -897,12 +929,13 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             for (int s = 0; s < S; ++s)
                 if (sval(s)) out_store(A.sigma + sidx(s), acc[s][0][0]);
         }
+        if constexpr (FOLD) put_normal(acc, std::integral_constant<int, 1>{});
     }
 
     MNRF_MARK(6);   // sigma head
     if (!SIGMA_ONLY) {
-        // ---- predicted normal: 256 -> 128 -> 3, no activation in between (mirror_nerf.py:85-88)
-        {
+        // ---- predicted normal: 256 -> 128 -> 3, no activation in between (mirror_nerf.py:85-88); FOLD: done above
+        if constexpr (!FOLD) {
             u32x4 nh[S][4], nl[S][4];
             {
                 f32x4 acc[S][8];
@@ -915,29 +948,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_NRM2, gq());
             gemm_part<4, 1, 1032>(acc, nh, nl, st, wave, lane16);
-            if (FUSE) {
-                if (gq() == 0) {
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const float a0 = acc[s][0][0], a1 = acc[s][0][1], a2 = acc[s][0][2];
-                        const float inv = 1.f / sqrtf(fmaxf(a0 * a0 + a1 * a1 + a2 * a2, 1.1920928955078125e-07f));
-                        const int q = wave * (S * 16) + s * 16 + (int)m15();
-                        fz[4 * WG_SAMPLES + q] = a0 * inv; fz[5 * WG_SAMPLES + q] = a1 * inv; fz[6 * WG_SAMPLES + q] = a2 * inv;
-                    }
-                }
-            } else if (A.pred_normal && g == 0) {
-#pragma unroll
-                for (int s = 0; s < S; ++s)
-                    if (sval(s)) {
-                        const float a0 = acc[s][0][0], a1 = acc[s][0][1], a2 = acc[s][0][2];
-                        // utils/func.py:5-7: eps clamps the squared norm
-                        const float inv = 1.f / sqrtf(fmaxf(a0 * a0 + a1 * a1 + a2 * a2, 1.1920928955078125e-07f));
-                        float* o = A.pred_normal + (long long)sidx(s) * 3;
-                        out_store(o, a0 * inv); out_store(o + 1, a1 * inv); out_store(o + 2, a2 * inv);
-                        if (GRAD && A.save_inv)   // negative marks the clamped branch (constant denominator)
-                            A.save_inv[idx[s]] = (a0 * a0 + a1 * a1 + a2 * a2) > 1.1920928955078125e-07f ? inv : -inv;
-                    }
-            }
+            put_normal(acc, std::integral_constant<int, 0>{});
         }
         MNRF_MARK(7);   // normal head
         // ---- mirror probability: 256 -> 128 LeakyReLU(0.01) -> 1 sigmoid (mirror_nerf.py:94-99)
@@ -946,7 +957,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             {
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_MIR1, gq());
-                gemm_part<8, 8, 1036, HP, ST4>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
+                gemm_part<8, 8, FOLD ? 968 : 1036, HP, ST4>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
                 if (keep) {
                     uint64_t bits[S];
                     save_acc<8, 2>(A.save_x + (long long)SEC_HM * A.B, 128, 0, acc, idx, valid, g, bits);
@@ -960,7 +971,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_MIR2, gq());
-            gemm_part<4, 1, 1100>(acc, mh, ml, st, wave, lane16);
+            gemm_part<4, 1, FOLD ? 1032 : 1100>(acc, mh, ml, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll
@@ -973,10 +984,38 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             }
         }
         MNRF_MARK(8);   // mirror head
-        // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid
+        // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid.  FOLD: dir_encoding reads h8
+        //      through the folded map (final's 256 outputs are never formed)
+        // view-encoding B operands (32 padded columns: one k-step)
+        const auto view_operands = [&](u32x4 (&vh)[S][1], u32x4 (&vl)[S][1]) {
+            float de[S][8];
+            const int gv = gq();
+            const int spr = opaque_spr();
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const float* dp = A.dir_emb + (long long)(sidx(s) / spr) * A.dir_stride;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const int e = 16 * (t >> 2) + 4 * gv + (t & 3);
+                    de[s][t] = e < ENC_DIR ? dp[e] : 0.f;
+                }
+            }
+            if (keep) save_bform<8>(A.save_x + (long long)SEC_DIRE * A.B, 32, de, idx, valid, g);
+            split_b<8>(de, vh, vl, st.sat);
+            if constexpr (S == 2) { if (pl) store_planes<1, 1>(sc, SEC_DIRE / 16, vh, vl); }
+        };
         {
             u32x4 dh[S][4], dl[S][4];
-            {
+            if constexpr (FOLD) {
+                u32x4 vh[S][1], vl[S][1];
+                view_operands(vh, vl);
+                MNRF_MARK(9);   // view encoding load
+                f32x4 acc[S][8];
+                init_bias<8>(acc, BIAS_DIR, gq());
+                gemm_part<8, 8, 1036, HP>(acc, hh, hl, st, wave, lane16);
+                gemm_part<1, 8, 1100>(acc, vh, vl, st, wave, lane16);
+                acc_to_b<8, 1, false>(dh, dl, acc, 0, tid, st.sat);
+            } else {
                 u32x4 fh[S][8], fl[S][8];
                 {
                     f32x4 acc[S][16];
@@ -987,23 +1026,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                     if constexpr (S == 2) { if (pl) store_planes<8, 8>(sc, SEC_FIN / 16, fh, fl); }
                 }
                 u32x4 vh[S][1], vl[S][1];
-                {
-                    float de[S][8];
-                    const int gv = gq();
-                    const int spr = opaque_spr();
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const float* dp = A.dir_emb + (long long)(sidx(s) / spr) * A.dir_stride;
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) {
-                            const int e = 16 * (t >> 2) + 4 * gv + (t & 3);
-                            de[s][t] = e < ENC_DIR ? dp[e] : 0.f;
-                        }
-                    }
-                    if (keep) save_bform<8>(A.save_x + (long long)SEC_DIRE * A.B, 32, de, idx, valid, g);
-                    split_b<8>(de, vh, vl, st.sat);
-                    if constexpr (S == 2) { if (pl) store_planes<1, 1>(sc, SEC_DIRE / 16, vh, vl); }
-                }
+                view_operands(vh, vl);
                 MNRF_MARK(9);   // xyz_encoding_final + view encoding load
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_DIR, gq());
@@ -1022,7 +1045,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_RGB, gq());
-            gemm_part<4, 1, 1304>(acc, dh, dl, st, wave, lane16);
+            gemm_part<4, 1, FOLD ? 1108 : 1304>(acc, dh, dl, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll

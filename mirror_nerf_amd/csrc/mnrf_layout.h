@@ -150,6 +150,19 @@ __host__ __device__ inline int enc_col32(int T, int h, int e) {
 // tail pad: the split kernel's static LDS-DMA schedule reads two chunks (of up to 32 KiB) past the end of a stream
 constexpr int64_t SPLIT_TAIL_FLOATS = 2 * 16 * (PAIR_BYTES / 4);
 constexpr int64_t PACKED_FLOATS = OFF_SPLIT32_FWD + (int64_t)SPLIT32_FWD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
+// ---- FOLDED forward stream of the forward-only split kernels (mnrf_field_split.inc FOLD).  Two head Linears of the model have
+//      no activation behind them: normal_net = Linear(256,128) -> Linear(128,3) is one 3 x 256 map W2.W1 (bias W2.b1 + b2), and
+//      xyz_encoding_final only feeds dir_encoding, whose first 256 columns Wd times it are one 128 x 256 map Wd.Wf on h8 (bias
+//      Wd.bf + bd).  The products are formed in fp64 by mnrf_fold_weights_n and split from the fp64 value.  The stream is the
+//      split forward stream with those heads folded: trunk 0..959 (a copy), sigma | normal 960 (one 16-row block: sigma in row 0,
+//      the folded normal in rows 1..3), is_mirror_net.0 968, is_mirror_net.2 1032, dir_encoding 1036 (folded h8 columns) 1100
+//      (view), rgb 1108, end 1112 -- 1112 pairs per full sample instead of 1308.  Behind its read-ahead tail lies a copy of the
+//      bias block with the folded biases in place (normal at BIAS_SIG + 1..3, dir_encoding at BIAS_DIR).
+//      It occupies the region of the 32x32x16 tuning's stream, so it exists only while MNRF_SPLIT32 is off (the default).
+constexpr int SPLIT_FOLD_USED = 960 + 8 + 64 + 4 + 64 + 8 + 4;                                      // 1112
+constexpr int SPLIT_FOLD_PAIRS = padded_pairs(SPLIT_FOLD_USED);                                      // 1120
+constexpr int64_t OFF_FOLD_FWD = OFF_SPLIT32_FWD;
+constexpr int64_t OFF_FOLD_BIAS = OFF_FOLD_FWD + (int64_t)SPLIT_FOLD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
 // The last words of the image (inside the tail pad, whose contents no kernel consumes) are CALLER-OWNED device state of the
 // launches that use this image: [PACKED_FLOATS - 1] the range-guard word (mnrf.h), before it TQ_PAIRS {next, done} counter
 // pairs of the dynamic tile queue (mnrf_field_split3.hip).  mnrf_pack_weights zeroes all of them.
@@ -160,6 +173,7 @@ constexpr int64_t OFF_TILE_QUEUE = PACKED_FLOATS - 1 - 2 * TQ_PAIRS;
 // workgroup out hands the value over and resets both words -- so a reduction needs no zero-fill launch in front of it
 constexpr int64_t OFF_REDUCE_PAIR = OFF_TILE_QUEUE - 2;
 constexpr int DEVICE_STATE_WORDS = 2 + 2 * TQ_PAIRS + 1;      // what mnrf_pack_weights zeroes, from OFF_REDUCE_PAIR on
+static_assert(OFF_FOLD_BIAS + BIAS_FLOATS <= OFF_REDUCE_PAIR, "the folded stream and its bias block fit the 32x32x16 region");
 
 // ---- activations saved by the training forward, [section][sample][width], B-form column order
 constexpr int SEC_ENC = 0;            // 64   xyz encoding in (sin,cos)-pair order (enc_col)

@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .weights import packed_of
+from .weights import folded_of, packed_of
 
 
 class Embedding(nn.Module):
@@ -275,7 +275,8 @@ FLOP_GRAD = 982528      # density-gradient pass: the trunk GEMMs once more, tran
 def field_forward(module, B, *, xyz=None, xyz_stride=3, rays=None, z_vals=None, spr=1, dir_emb=None,
                   dir_stride=27, sigma_only=False, grad_normal=False, want_geo=False, device=None):
     """Run the fused field kernel; returns flat per-sample tensors (sigma (B,), rgb (B,3), ...)."""
-    packed = packed_of(module)
+    # (the full forward-only split launches read the image's folded head stream: weights.folded_of)
+    packed = folded_of(module) if precision_of(module).startswith("split") and not sigma_only and not grad_normal else packed_of(module)
     dev = packed.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
     out = {"sigma": f(B)}

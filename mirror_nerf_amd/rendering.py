@@ -203,7 +203,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         as the two-kernel path; the per-sample keys (weights_*, pred_normal_*) are not produced.  Returns False when the
         launch class is not covered (the caller then takes the two-kernel path)."""
         from . import mirror_nerf as _mn
-        from .weights import packed_of
+        from .weights import folded_of
         if _mn.precision_of(model) != "split" or z.shape[1] != L.mnrf_fused_samples_per_ray():
             return False
         has_m, has_n = getattr(model, "predict_mirror_mask", True), getattr(model, "predict_normal", True)
@@ -213,7 +213,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         if _mn.LAUNCH_LOG is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        rc = L.mnrf_field_composite_fused(p(packed_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], int(bool(white_back)),
+        rc = L.mnrf_field_composite_fused(p(folded_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], int(bool(white_back)),
                                           None, p(opacity), p(rgb_map), p(depth), p(mask), p(sn), p(xs), _lib.stream())
         if rc == -3:          # MNRF_ERR_UNSUPPORTED: the 48-samples-per-wave tuning is switched off
             return False

@@ -168,6 +168,7 @@ class PackedCache:
     def __init__(self):
         self.key = None
         self.packed = None
+        self.folded = False      # the image's folded forward stream (mnrf_fold_weights_n) is current
 
     def stale(self, module):
         """-> the key the image should have, or None when the image is current."""
@@ -188,7 +189,18 @@ class PackedCache:
         if key is not None:
             self.packed = pack_state({full: sub._parameters[pname] for sub, pname, full in param_refs(module)}, self.packed)
             self.key = key
+            self.folded = False
         return self.packed
+
+    def fold(self, module):
+        """Build the folded forward stream of the current image once per re-pack (csrc/mnrf_layout.h OFF_FOLD_FWD): only the
+        full forward-only split launches read it, so a training step that re-packs behind every optimizer step never pays for it."""
+        if not self.folded:
+            L = _lib.lib()
+            arr, img, keep = (ctypes.c_void_p * _lib.N_PARAMS)(), (ctypes.c_void_p * 1)(self.packed.data_ptr()), []
+            _param_pointers({full: sub._parameters[pname] for sub, pname, full in param_refs(module)}, arr, 0, keep)
+            _lib.check(L.mnrf_fold_weights_n(1, arr, img, _lib.stream()), "mnrf_fold_weights")
+            self.folded = True
 
 
 def packed_of_many(modules):
@@ -208,7 +220,7 @@ def packed_of_many(modules):
         outs = pack_states([{full: sub._parameters[pname] for sub, pname, full in param_refs(m)} for m, _, _ in todo],
                            [c.packed for _, c, _ in todo])
         for (m, c, key), out in zip(todo, outs):
-            c.packed, c.key = out, key
+            c.packed, c.key, c.folded = out, key, False
     return [c.packed for c in caches]
 
 
@@ -256,3 +268,13 @@ def packed_of(module):
         cache = PackedCache()
         module.__dict__["_mnrf_packed"] = cache
     return cache.get(module)
+
+
+def folded_of(module):
+    """packed_of, with the image's folded forward stream built: what the full forward-only split launches read."""
+    image = packed_of(module)
+    cache = module.__dict__["_mnrf_packed"]
+    if cache.packed is not image:      # (cannot happen through packed_of / validated; a stale image must not be folded)
+        raise RuntimeError("folded_of: the validated image is not the module's cached one")
+    cache.fold(module)
+    return image

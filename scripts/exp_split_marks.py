@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 import mirror_nerf_amd as M  # noqa: E402,F401
 from mirror_nerf_amd import _lib  # noqa: E402
-from mirror_nerf_amd.weights import packed_of  # noqa: E402
+from mirror_nerf_amd.weights import folded_of  # noqa: E402
 from oracle import mirror_nerf_oracle as O  # noqa: E402
 
 dev = torch.device("cuda", 0)
@@ -20,7 +20,7 @@ rays = torch.from_numpy(O.synthetic_rays(800, 800)[300 * 800:300 * 800 + 32768])
 S = 192
 z = torch.sort(torch.rand(32768, S, device=dev) * 7 + 0.05, 1)[0].contiguous()
 dir_emb = emb["dir"](rays[:, 3:6].contiguous())
-packed = packed_of(models["fine"])
+packed = folded_of(models["fine"])      # the full forward-only launch reads the folded head stream
 B = 32768 * S
 f = lambda *s: torch.empty(*s, device=dev)  # noqa: E731
 sig, rgb, pn, mir = f(B), f(B, 3), f(B, 3), f(B)
