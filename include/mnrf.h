@@ -114,7 +114,7 @@ int mnrf_pack_weights_n(int n_models, const float* const* params, float* const* 
 /* Folded forward stream of n_models packed images (same arguments as mnrf_pack_weights_n): normal_net's two Linears as one map,
  * xyz_encoding_final folded into dir_encoding, formed in fp64 on the GPU.  The full forward-only split launches (mnrf_field_forward
  * with MNRF_SPLIT_F16 and neither MNRF_SIGMA_ONLY nor MNRF_GRAD_NORMAL, mnrf_field_composite_fused) read it: call this after
- * every mnrf_pack_weights* of an image and before its first such launch.  No-op under MNRF_SPLIT32=1. */
+ * every mnrf_pack_weights* of an image and before its first such launch. */
 int mnrf_fold_weights_n(int n_models, const float* const* params, float* const* packed, void* stream);
 
 /* Embedding.forward (models/mirror_nerf.py:20-38): x (n, c) -> out (n, c*(2*n_freqs+1)). */
@@ -334,7 +334,7 @@ int mnrf_bench_gather(const void* table, int64_t table_bytes, int bytes_per_gath
  * no per-sample tensor (36 B per sample written and read back otherwise) touches HBM.  What the reference's eval caller
  * copies to the CPU and nobody reads (eval.py:735-736, SURVEY 3 "result-dict contract") is simply never produced.
  * noise_std = 0 (test_time), no density-gradient normal.  Null map pointers are skipped; weights (n_rays, 192) optional.
- * Returns MNRF_ERR_UNSUPPORTED when the 48-samples-per-wave tuning is off (MNRF_SPLIT48=0 / MNRF_SPLIT32=1). */
+ * Returns MNRF_ERR_UNSUPPORTED when the 48-samples-per-wave tuning is off (MNRF_SPLIT48=0). */
 int mnrf_fused_samples_per_ray(void);
 int mnrf_field_composite_fused(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
                                const float* dir_emb, int64_t dir_stride, int white_back,

@@ -146,7 +146,7 @@ class FieldFn(torch.autograd.Function):
         xyz, rays, z_vals, dir_emb = _c(xyz), _c(rays), _c(z_vals), _c(dir_emb)
         sigma, rgb, pn, mir = f(B), f(B, 3), f(B, 3), f(B)
         normal = f(B, 3) if want_normal else None
-        split = _mn.precision_of(module).startswith("split")
+        split = _mn.precision_of(module) == "split"
         planes = split and DW_PLANES
         if ctx.n_live is not None and not planes:
             raise RuntimeError("a live row count (static training step) needs the split arithmetic with operand planes")

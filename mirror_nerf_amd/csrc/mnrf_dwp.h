@@ -47,16 +47,10 @@ constexpr int PL_BOOST_LOG2 = 4;
 // (profiles/r03r_store_policy_pmc.txt): same fetched bytes, same L2 hits / misses; the L2's memory-side write requests stall
 // 34-84 % longer with the default policy (lines allocated, written back later), and the weight stream's counted waits sit
 // behind the stores.
-#ifndef MNRF_EXP_STORE_AUX
-#define MNRF_EXP_STORE_AUX 2
-#endif
+constexpr int PL_STORE_AUX = 2;
 // ... and of the GEMM's LDS-DMA loads of them: nt (2) measured 1.365 against 1.40-1.43 ms for the two evaluations of a training
 // step and 0.1-0.2 ms per step in alternating runs (round 4; the streaming probe reads 6.87 TB/s with nt, 6.06 without)
-#ifndef MNRF_EXP_LOAD_AUX
-#define MNRF_EXP_LOAD_AUX 2
-#endif
-constexpr int PL_LOAD_AUX = MNRF_EXP_LOAD_AUX;      // the same operand of the GEMM's LDS-DMA loads of the planes
-constexpr int PL_STORE_AUX = MNRF_EXP_STORE_AUX;
+constexpr int PL_LOAD_AUX = 2;      // the same operand of the GEMM's LDS-DMA loads of the planes
 constexpr int PL_TILE_BYTES = 1024;                  // one plane of one feature block of one sample block
 constexpr int PL_FB_BYTES = 2 * PL_TILE_BYTES;       // [hi tile][lo tile]
 constexpr int PL_SB = 32;                            // samples per sample block = one wave of the field kernels (2 groups x 16)
@@ -135,10 +129,7 @@ __host__ __device__ inline DwpJob dwp_job_of(int kind, int j) {
 // cost of one stage (32 samples) of job j: KiB of operand tiles (the GEMM is HBM-bound, work is dealt by bytes) plus what a
 // stage costs whatever its size -- barrier, counted wait, request -- expressed in KiB: without it the workgroups that own the
 // small jobs (18-40 KiB per stage) finish last
-#ifndef MNRF_EXP_DWP_STAGE_KIB
-#define MNRF_EXP_DWP_STAGE_KIB 0
-#endif
-constexpr int DWP_STAGE_KIB = MNRF_EXP_DWP_STAGE_KIB;
+constexpr int DWP_STAGE_KIB = 0;
 constexpr int DWP_MAX_WEIGHT = 64 + DWP_STAGE_KIB;
 __host__ __device__ inline int dwp_weight(int j) {
     const DwpJob jb = dwp_job(j);

@@ -258,12 +258,8 @@ __device__ __forceinline__ void dwp_segment_run_h(const char* __restrict__ Yb, c
     // PACED (default since the end of round 4): the 2 Q requests that refill a stage's slots are spread over the KB column blocks
     // of the stage's MFMAs instead of leaving as one burst of 8 waves x 2 Q instructions right after the barrier, and the X
     // operands are read one column block ahead (below).  Together 1.23 against 1.28-1.36 ms for the two evaluations of a training
-    // step -- the time of this loop with its LDS reads and MFMAs compiled out (MNRF_EXP_DWP_NOMATH): the math is hidden now.
-#if defined(MNRF_EXP_DWP_BURST) || defined(MNRF_EXP_DWP_NOMATH)
-    constexpr bool PACED = false;
-#else
+    // step -- the time of this loop with its LDS reads and MFMAs compiled out: the math is hidden now.
     constexpr bool PACED = true;
-#endif
 
     __syncthreads();                 // the previous segment's last stage has been read by every wave
     int next_hs = 0, next_slot = 0;  // next half-stage to request and the slot it goes to (hs mod D)
@@ -294,11 +290,7 @@ __device__ __forceinline__ void dwp_segment_run_h(const char* __restrict__ Yb, c
         const char* A1 = lds + cur1 * SLOT;
         const char* X0 = A0 + NA * 1024;
         const char* X1 = A1 + NA * 1024;
-#ifdef MNRF_EXP_DWP_NOMATH      // experiment (no sums): the LDS-DMA stream, counted waits and barriers alone -- what the plane reads cost
-        if (false) {
-#else
         if (has_a) {
-#endif
             u32x4 ah[MB], al[MB];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {

@@ -161,18 +161,16 @@ extern "C" int mnrf_pack_weights_n(int n_models, const float* const* params, flo
         // itself: split_pack_kernel, which may raise MNRF_GUARD_WEIGHT, runs behind it on the stream)
         hipLaunchKernelGGL(pack_kernel, dim3(blocks, nb), dim3(threads), 0, (hipStream_t)stream, PB, T);
         launch_split_pack(images, nb, (hipStream_t)stream);   // hi/lo f16 streams of the split tunings, from the fp32 tiles
-        if (split32_enabled())      // stream of the 32x32x16 tuning (MNRF_SPLIT32=1 only)
-            for (int m = 0; m < nb; ++m) launch_split32_pack(params + (m0 + m) * MNRF_N_PARAMS, images[m], (hipStream_t)stream);
     }
     return mnrf_check_launch("mnrf_pack_weights");
 }
 
 // The folded forward stream (mnrf_layout.h OFF_FOLD_FWD) is built by its own entry point and not by every pack: the captured
 // training step re-packs both models behind every optimizer step and never runs a forward-only launch -- built there, it cost the
-// step 2 % (A/B, alternating).  A no-op under MNRF_SPLIT32=1 (the region holds the 32x32x16 stream then).
+// step 2 % (A/B, alternating).
 extern "C" int mnrf_fold_weights_n(int n_models, const float* const* params, float* const* packed, void* stream) {
     if (n_models < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: negative model count");
-    if (n_models == 0 || split32_enabled()) return MNRF_OK;
+    if (n_models == 0) return MNRF_OK;
     if (!params || !packed) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: null pointer");
     for (int i = 0; i < n_models * MNRF_N_PARAMS; ++i)
         if (!params[i]) return mnrf_fail(MNRF_ERR_ARG, "mnrf_fold_weights_n: null parameter pointer");
@@ -211,18 +209,10 @@ extern "C" int mnrf_field_forward(float* packed, unsigned flags, int64_t B, cons
     // Tunings.  fp32 MFMA (bit-exact fmaf chains): s2 (32 samples/wave, one wave per SIMD) is fastest for the
     // forward-only kernels, s1 (16 samples/wave, two workgroups per CU) for the ones with the density-gradient
     // pass.  MNRF_SPLIT_F16 selects the split-f16 tuning (fp32 operands as hi/lo f16 pairs on the f16 matrix
-    // pipe).  MNRF_FIELD_VARIANT=s1|s2|h|h2|hx forces one (experiments; h = split with its own default).
-    static const int forced = [] {
-        const char* e = getenv("MNRF_FIELD_VARIANT");
-        if (e && e[0] == 's' && (e[1] == '1' || e[1] == '2')) return e[1] - '0';
-        if (e && e[0] == 'h') return e[1] == 'x' ? 5 : (e[1] == '2' ? 4 : 3);
-        return 0;
-    }();
-    const int variant = forced ? forced : ((flags & MNRF_SPLIT_F16) ? 3 + (int)((flags >> 3) & 3u) : (grad ? 1 : 2));   // bits 3-4: experimental split tunings
-    const int rc = variant >= 3 ? launch_split(A, sigma_only, grad, variant - 3, (hipStream_t)stream)
-                 : variant == 1 ? s1::launch(A, sigma_only, grad, (hipStream_t)stream)
-                                : s2::launch(A, sigma_only, grad, (hipStream_t)stream);
-    if (rc == -2) return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_forward: a forced h2 / hx forward variant needs the folded stream (MNRF_SPLIT32 unset)");
+    // pipe).
+    const int rc = (flags & MNRF_SPLIT_F16) ? launch_split(A, sigma_only, grad, (hipStream_t)stream)
+                 : grad ? s1::launch(A, sigma_only, grad, (hipStream_t)stream)
+                        : s2::launch(A, sigma_only, grad, (hipStream_t)stream);
     if (rc != 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_forward: too many samples for one launch");
     return mnrf_check_launch("mnrf_field_forward");
 }
@@ -237,8 +227,8 @@ extern "C" int mnrf_field_composite_fused(float* packed, int64_t n_rays, const f
     if (!packed || !rays || !z_vals || !dir_emb) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: null pointer");
     if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: negative ray count");
     if (n_rays == 0) return MNRF_OK;
-    if (!split48_enabled() || split32_enabled())
-        return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_composite_fused: needs the 48-samples-per-wave tuning (MNRF_SPLIT48 != 0, MNRF_SPLIT32 unset)");
+    if (!split48_enabled())
+        return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_composite_fused: needs the 48-samples-per-wave tuning (MNRF_SPLIT48 != 0)");
     const int spr = split48_ray_samples();
     FieldArgs A{packed, MNRF_SPLIT_F16, (long long)n_rays * spr, nullptr, 3, rays, z_vals, spr, dir_emb, (long long)dir_stride,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -258,10 +248,6 @@ extern "C" int64_t mnrf_train_save_floats(int64_t B) { return (int64_t)SAVE_FLOA
 extern "C" int64_t mnrf_train_mask_words(int64_t B) { return train_tiles(B) * N_MASKS * s2::S * s2::WG_THREADS; }
 extern "C" int64_t mnrf_train_workspace_floats(int64_t B) { return (int64_t)DY_FLOATS * B + dw_workspace_floats(B); }
 
-#ifdef MNRF_EXP_CYCLES      // experiment builds only (scripts/exp_train_marks.py): where the s_memtime marks of the training forward go
-static void* g_exp_marks = nullptr;
-extern "C" void mnrf_exp_set_marks(void* p) { g_exp_marks = p; }
-#endif
 static int field_forward_train_impl(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                     const float* rays, const float* z_vals, int spr, const float* dir_emb,
                                     int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
@@ -282,12 +268,9 @@ static int field_forward_train_impl(float* packed, int64_t B, const float* xyz, 
                 (long long)dir_stride, sigma, rgb, pred_normal, is_mirror, normal, nullptr,
                 planes ? nullptr : save_x, (unsigned long long*)save_mask, save_inv, save_invj, planes ? (char*)save_x : nullptr};
     A.n_live = n_live;
-#ifdef MNRF_EXP_CYCLES
-    A.geo_feat = (float*)g_exp_marks;
-#endif
     // always a 128-sample tiling with the mask-producing (GRAD) body: the backward kernel shares its tile map.
     // MNRF_SPLIT_F16: the split-f16 tuning (same saved quantities, fp32 activations from its fp32 accumulators)
-    const int rc = (flags & MNRF_SPLIT_F16) ? launch_split(A, false, true, 0, (hipStream_t)stream)
+    const int rc = (flags & MNRF_SPLIT_F16) ? launch_split(A, false, true, (hipStream_t)stream)
                                             : s2::launch(A, false, true, (hipStream_t)stream);
     if (rc != 0)
         return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_forward_train: too many samples for one launch");

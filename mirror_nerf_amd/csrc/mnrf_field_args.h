@@ -102,23 +102,18 @@ struct FieldBwd2Args {
     const int* n_live;         // live rows (B = capacity): see FieldArgs::n_live; planes route only
 };
 
-// split-f16 tunings (mnrf_field_split.hip).  variant: 0 = default.
-int launch_split(const FieldArgs& A, bool sigma_only, bool grad, int variant, hipStream_t s);
+// split-f16 tunings (mnrf_field_split.hip)
+int launch_split(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s);
 // builds the split streams of a packed image from its fp32 streams (same stream, after pack_kernel)
 void launch_split_pack(float* const* packed, int n_images, hipStream_t s);      // up to 4 images per launch
 // builds the folded forward stream and its bias block (mnrf_layout.h OFF_FOLD_*) from the split stream and the fp32 bias block of
 // each image and from its state_dict-ordered parameter pointers (n_images x 32 of them); same stream, after launch_split_pack
 void launch_split_fold(const float* const* params, float* const* packed, int n_images, hipStream_t s);      // up to 4 images
 int launch_split_bwd(const FieldBwdArgs& A, hipStream_t s);
-// 32x32x16 tuning of the forward-only split kernels (mnrf_field_split32.hip) and the packer of its stream (from the
-// state_dict-ordered parameter pointers)
 // 48-samples-per-wave tuning of the forward-only split kernels (mnrf_field_split3.hip), MNRF_SPLIT48=1
 bool split48_enabled();
 int launch_split48(const FieldArgs& A, bool sigma_only, hipStream_t s);
 int split48_ray_samples();      // samples of one workgroup of that tuning = samples per ray of the ray-fused fine pass (192)
-bool split32_enabled();      // MNRF_SPLIT32=1
-int launch_split32(const FieldArgs& A, bool sigma_only, hipStream_t s);
-void launch_split32_pack(const float* const* params, float* packed, hipStream_t s);
 int launch_split_bwd2(const FieldBwd2Args& A, hipStream_t s);
 
 }  // namespace mnrf

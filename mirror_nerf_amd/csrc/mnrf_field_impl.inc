@@ -38,10 +38,6 @@ constexpr int NBUF = PF + U;
 // 16-bit offset field, so a chunk needs one address register and no per-tile VALU add (every
 // non-MFMA issue state between two MFMAs costs matrix-pipe time).
 __device__ __forceinline__ void lds_read_tile(f32x4& dst, unsigned addr, int off) {
-#ifdef MNRF_EXP_NO_READ
-    asm volatile("v_mov_b32 %0, %1" : "=v"(dst.x) : "v"(addr));
-    return;
-#endif
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off) : "memory");
 }
 
@@ -202,13 +198,6 @@ __device__ __forceinline__ void save_bform(float* sec, long long B, int width, c
 }
 
 // ------------------------------------------------------------------ the kernel
-#ifdef MNRF_EXP_MARKS
-#define MNRF_MARK(k) do { if (A.geo_feat == nullptr && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) \
-    ((long long*)A.normal)[k] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define MNRF_MARK(k) do { } while (0)
-#endif
-
 template <bool SIGMA_ONLY, bool GRAD>
 __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(FieldArgs A) {
     const int tid = threadIdx.x;
@@ -217,7 +206,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
     const int g = lane >> 4;     // lane group = k-slot / row quad
     const int m = lane & 15;     // sample within the group
     const int lane16 = lane * 16;
-    MNRF_MARK(0);
 
     // bias block -> LDS (read by init_bias, visible after the first advance() barrier)
     {
@@ -229,7 +217,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
     Stream st;
     open_stream(st, A.packed + OFF_FWD, SIGMA_ONLY ? FWD_TILES_SIGMA : FWD_TILES, wave, lane);
 
-    MNRF_MARK(1);
     // ---- sample positions (rendering.py:302: multiply, then add -- no FMA)
     long long idx[S];
     bool valid[S];
@@ -253,7 +240,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
     }
 
     // ---- xyz encoding, this lane's 16 of the 64 (padded) channels: pairs P = 8g + pp
-    MNRF_MARK(2);
     float enc[S][16];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -274,7 +260,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
         }
     }
 
-    MNRF_MARK(3);
     unsigned long long* gmask = A.save_mask ? A.save_mask + (long long)blockIdx.x * (N_MASKS * S * WG_THREADS) : nullptr;
     if (A.save_x) save_bform(A.save_x + (long long)SEC_ENC * A.B, A.B, 64, enc, idx, valid, g);
     int tile0 = 0;
@@ -287,7 +272,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
         gemm_part<4, 16>(acc, enc, st, tile0, wave, lane16);
         relu_to<GRAD>(h, acc, 0, tid, gmask);
         if (A.save_x) save_bform(A.save_x + (long long)SEC_H * A.B, A.B, 256, h, idx, valid, g);
-    MNRF_MARK(4);
         // ---- L2..L4
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
@@ -296,14 +280,12 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
             relu_to<GRAD>(h, acc, 1 + l, tid, gmask);
             if (A.save_x) save_bform(A.save_x + (long long)(SEC_H + 256 * (1 + l)) * A.B, A.B, 256, h, idx, valid, g);
         }
-    MNRF_MARK(5);
         // ---- L5: cat[enc, h] -> 256  (encoding first: mirror_nerf.py:192-193)
         init_bias<16>(acc, BIAS_L + 256 * 4, g);
         gemm_part<4, 16>(acc, enc, st, tile0, wave, lane16);
         gemm_part<16, 16>(acc, h, st, tile0, wave, lane16);
         relu_to<GRAD>(h, acc, 4, tid, gmask);
         if (A.save_x) save_bform(A.save_x + (long long)(SEC_H + 256 * 4) * A.B, A.B, 256, h, idx, valid, g);
-    MNRF_MARK(6);
         // ---- L6..L8
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
@@ -313,7 +295,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
             if (A.save_x) save_bform(A.save_x + (long long)(SEC_H + 256 * (5 + l)) * A.B, A.B, 256, h, idx, valid, g);
         }
     }
-    MNRF_MARK(7);
     // h = geo_feat (mirror_nerf.py:195)
     if (A.geo_feat) {
 #pragma unroll
@@ -339,7 +320,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
     }
 
     if (!SIGMA_ONLY) {
-    MNRF_MARK(8);
         // ---- predicted normal: 256 -> 128 -> 3, no activation in between (mirror_nerf.py:85-88)
         {
             float hn[S][32];
@@ -372,7 +352,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
                     }
             }
         }
-    MNRF_MARK(9);
         // ---- mirror probability: 256 -> 128 LeakyReLU(0.01) -> 1 sigmoid (mirror_nerf.py:94-99)
         {
             float hm[S][32];
@@ -409,7 +388,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
                     if (valid[s]) A.is_mirror[idx[s]] = sigmoidf_(acc[s][0][0]);
             }
         }
-    MNRF_MARK(10);
         // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid
         {
             float fin[S][64];
@@ -425,7 +403,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
                         for (int r = 0; r < 4; ++r) fin[s][4 * nb + r] = acc[s][nb][r];
                 if (A.save_x) save_bform(A.save_x + (long long)SEC_FIN * A.B, A.B, 256, fin, idx, valid, g);
             }
-    MNRF_MARK(11);
             float de[S][8];
 #pragma unroll
             for (int s = 0; s < S; ++s) {
@@ -476,7 +453,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_kernel(F
         }
     }
 
-    MNRF_MARK(12);
     if (GRAD) {
         // ---- d sigma / d xyz in closed form (SURVEY 8a): g = w_sigma; for i = 8..1:
         //      g = (g * relu_mask_i) W_i, the 63 encoding columns of layer 5 and layer 1 feed g_enc.

@@ -32,38 +32,18 @@ constexpr int RING_SLOTS = 3;
 #include "mnrf_field_split.inc"
 #include "mnrf_field_split_bwd.inc"
 }  // namespace h2x
-#ifdef MNRF_EXP_H1
-// experiment: 16 samples per wave, <= 256 registers, two workgroups per CU (two waves share each SIMD's matrix pipe)
-namespace h1 {
-constexpr int S = 1;
-constexpr int MIN_WAVES_PER_SIMD = 2;
-constexpr int CHUNK_PAIRS = 8;
-constexpr int RING_SLOTS = 3;
-#define MNRF_SPLIT_NO_GRAD
-#include "mnrf_field_split.inc"
-#undef MNRF_SPLIT_NO_GRAD
-}  // namespace h1
-#endif
 
-int launch_split(const FieldArgs& A, bool sigma_only, bool grad, int variant, hipStream_t s) {
-#ifdef MNRF_EXP_H1
-    if (variant == 3 && !grad) return h1::launch(A, sigma_only, grad, s);
-#endif
-    // variant 0: measured default -- 16 KiB chunks for the forward-only kernels (17.2 vs 17.3 ms per 6.29 M full
-    // samples), 32 KiB chunks when the density-gradient pass is on (32.1 vs 34.1 ms); 1 / 2 force h2 / h2x.
+int launch_split(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s) {
+    // measured: 16 KiB chunks for the forward-only kernels (17.2 vs 17.3 ms per 6.29 M full samples), 32 KiB chunks when the
+    // density-gradient pass is on (32.1 vs 34.1 ms).
     // A 16-samples-per-wave tuning with two workgroups per CU (as s1 of the fp32 kernel) was tried and dropped:
     // 18.2 / 32.5 ms -- it hides the waits but issues twice the LDS-DMA per sample.  So was a 48-samples-per-wave tuning
     // (a third less LDS-DMA per sample): it needs all 512 registers, spills 200 bytes and ends up 1 % slower.
-    // MNRF_SPLIT32=1: the forward-only launches on the 32x32x16 tuning (mnrf_field_split32.inc)
-    if (!grad && variant == 0 && split32_enabled()) return launch_split32(A, sigma_only, s);
-    // the full forward-only kernels read the folded stream (mnrf_layout.h OFF_FOLD_FWD), whose region holds the 32x32x16 stream
-    // instead under MNRF_SPLIT32=1: a forced h2 / h2x variant cannot run there
-    if (!grad && !sigma_only && split32_enabled()) return -2;
+    if (grad) return h2x::launch(A, sigma_only, grad, s);
     // default of the forward-only launches: 48 samples per wave (mnrf_field_split3.hip); geo_feat needs both halves of L8
     // in registers, which that tuning cannot afford
-    if (!grad && variant == 0 && !A.geo_feat && split48_enabled()) return launch_split48(A, sigma_only, s);
-    const bool big = variant == 0 ? grad : variant == 2;
-    return big ? h2x::launch(A, sigma_only, grad, s) : h2::launch(A, sigma_only, grad, s);
+    if (!A.geo_feat && split48_enabled()) return launch_split48(A, sigma_only, s);
+    return h2::launch(A, sigma_only, grad, s);
 }
 
 int launch_split_bwd(const FieldBwdArgs& A, hipStream_t s) { return h2x::launch_bwd(A, s); }

@@ -38,7 +38,8 @@ struct StoreCtx {
     __amdgpu_buffer_rsrc_t rsrc_lo;  // the same for the lo tiles -- or, with MNRF_PLANES_Y_HALF, a descriptor of ZERO records: the
                                    // store is issued (the counted vmcnt waits of the weight stream count it) and dropped by the
                                    // hardware's range check: no write traffic
-    char* base;                    // the same as a pointer (MNRF_EXP_GLOBAL_STORES)
+    char* base;                    // the same as a pointer.  Nothing reads it, but without it hipcc schedules
+                                   // field_split_bwd2_kernel differently
     int lane;                      // 32 m + 8 g: row m of the sample group, features 4 g .. 4 g + 3 of a tile
     int soff;                      // byte offset of the first tile the part stores
     h2v fac[S];                    // backward kernel: 2^(K - k_s + boost) per sample group (mnrf_dwp.h "scale")
@@ -302,20 +303,6 @@ __device__ __forceinline__ void gemm_part_impl(f32x4 (&acc)[S][NACC], const u32x
                     }
                     u32x4& d_ = sg % 2 == 0 ? (r < NPAIRS ? ah[r % NBUF] : st.ch[(r - NPAIRS) % PF])
                                             : (r < NPAIRS ? al[r % NBUF] : st.cl[(r - NPAIRS) % PF]);
-#if defined(MNRF_EXP_NO_LO_READ) || defined(MNRF_EXP_HALF_LO_READ)
-                    // experiment (round 6, VERDICT r5 item 7; wrong numerics, same MFMA count): the ds_read of the LO A tile left out --
-                    // always, or for every other pair -- an upper bound of what any scheme that reads lo tiles less often could
-                    // save in time, clock and watts (scripts/exp_lo_reads.sh)
-#ifdef MNRF_EXP_NO_LO_READ
-                    constexpr bool SKIP = true;
-#else
-                    const bool SKIP = (r & 1) != 0;
-#endif
-                    // (a 4-byte read instead of the 16-byte one: still ONE LDS instruction, so the counted lgkmcnt waits stay exact)
-                    if (sg % 2 == 1 && SKIP)
-                        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d_.x) : "v"(base), "i"(((START + r) % CHUNK_PAIRS) * PAIR_BYTES + TILE_BYTES) : "memory");
-                    else
-#endif
                     lds_read_half_tile(d_, base, ((START + r) % CHUNK_PAIRS) * PAIR_BYTES + (sg % 2) * TILE_BYTES);
                 } else {
                     const int piece = ((POS + t) / U) % PIECES;
@@ -391,24 +378,15 @@ __device__ __forceinline__ void store_mask(const uint64_t (&mk)[S], int layer, i
     }
 }
 
-// per-sample outputs (sigma, rgb, predicted normal, mirror probability): plain stores unless the experiment flag asks for
-// non-temporal ones
+// per-sample outputs (sigma, rgb, predicted normal, mirror probability): plain stores
 __device__ __forceinline__ void out_store(float* p, float v) {
-#ifdef MNRF_EXP_OUT_NT
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
 // fp32 rows kept for a later kernel (row route of the weight gradients, second-order pass): non-temporal like the operand planes
 // (mnrf_dwp.h PL_STORE_AUX) -- gigabytes per step whose write-back otherwise stalls the L2's memory side
 __device__ __forceinline__ void row_store(f32x4* p, const f32x4 v) {
-#ifdef MNRF_EXP_ROWS_TEMPORAL
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 
 // ---- training forward: activations kept for the backward pass, [section][sample][width] in B-form column order
@@ -457,9 +435,6 @@ __device__ __forceinline__ void save_acc(float* sec, int width, int nb0, const f
 template <int NT, int NTA>
 __device__ __forceinline__ void store_planes(const StoreCtx& sc, int fb0, const u32x4 (&hi)[S][NTA], const u32x4 (&lo)[S][NTA]) {
     static_assert(S == 2, "a sample block is one wave of two 16-sample groups");
-#ifdef MNRF_EXP_NO_PLANE_STORES      // experiment: what the plane stores cost the training forward
-    return;
-#endif
 #pragma unroll
     for (int T = 0; T < NT; ++T)
 #pragma unroll
@@ -467,13 +442,8 @@ __device__ __forceinline__ void store_planes(const StoreCtx& sc, int fb0, const 
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 const int off = (fb0 + 2 * T + h) * PL_FB_BYTES + s * 512;
-#ifdef MNRF_EXP_GLOBAL_STORES      // experiment: per-lane 64-bit pointers instead of buffer stores
-                *(u32x2*)(sc.base + off + sc.lane) = u32x2{hi[s][T][2 * h], hi[s][T][2 * h + 1]};
-                *(u32x2*)(sc.base + off + PL_TILE_BYTES + sc.lane) = u32x2{lo[s][T][2 * h], lo[s][T][2 * h + 1]};
-#else
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{hi[s][T][2 * h], hi[s][T][2 * h + 1]}, sc.rsrc, sc.lane, off, PL_STORE_AUX);
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo[s][T][2 * h], lo[s][T][2 * h + 1]}, sc.rsrc_lo, sc.lane, off + PL_TILE_BYTES, PL_STORE_AUX);
-#endif
             }
 }
 
@@ -601,26 +571,18 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     // training forward, operand planes: this lane's corner of the wave's sample block (S == 2: 32 samples per wave)
     char* const pl = (PLANES || (GRAD && S == 2 && A.save_planes))
                          ? A.save_planes + ((long long)blockIdx.x * WAVES + wave) * PLX_SB_BYTES : nullptr;      // wave-uniform
-    // WEAVE (default since round 5; -DMNRF_EXP_NO_WEAVE_FWD restores the bursts): the 64 stores of every hidden section ride inside
+    // WEAVE (default since round 5): the 64 stores of every hidden section ride inside
     // the MFMA streams of the GEMMs that read the same operands (gemm_part_impl STB), one behind each unit, instead of going out in
     // one burst between two GEMMs.  Round 3 measured it EQUAL (5.96-5.99 against 5.94-5.97 ms per step on the host-driven step of
-    // that time).  Round 5 (scripts/exp_train_marks.py, exp_libs variants, one box, alternating): the kernel alone 897-924 against
+    // that time).  Round 5 (experiment builds, one box, alternating): the kernel alone 897-924 against
     // 931-949 us per 1024 x 128 launch (the same without any plane store: 781-796; with every store landing in one L2-resident
     // block: 829-834 woven, 864-872 in bursts -- so half of the stores' cost is issue / data path, which weaving halves, and half is
     // the memory system's write side, which it does not touch); in the training step 4.38-4.40 against 4.44-4.50 ms with this kernel
     // woven, 4.26-4.28 with the activation-gradient kernel woven too.
-#ifndef MNRF_EXP_NO_WEAVE_FWD
     constexpr bool WEAVE = PLANES;
-#else
-    constexpr bool WEAVE = false;
-#endif
     constexpr int ST0 = WEAVE ? 0 : -1, ST4 = WEAVE ? 4 : -1;      // store operands 0..3 / 4..7 inside a GEMM part
     StoreCtx sc;
-#ifdef MNRF_EXP_STORE_SAME_ADDR      // experiment: every workgroup's plane stores land in ONE sample block (L2-resident): issue cost without HBM writes
-    sc.rsrc = plane_rsrc(pl ? A.save_planes + (long long)wave * PLX_SB_BYTES : nullptr);
-#else
     sc.rsrc = plane_rsrc(pl);
-#endif
     sc.rsrc_lo = sc.rsrc;
     sc.base = pl;
     sc.lane = 32 * m + 8 * g;
@@ -630,12 +592,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         sc.soff = (SEC_H / 16 + 16 * sec + 2 * T0) * PL_FB_BYTES;
         return sc;
     };
-#ifdef MNRF_EXP_CYCLES
-#define MNRF_MARK(k) do { if (tid == 0 && A.geo_feat) ((long long*)A.geo_feat)[tile * 16 + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define MNRF_MARK(k) do { } while (0)
-#endif
-    MNRF_MARK(0);
 
     // the weight stream starts first: its first two chunks travel while the positions are fetched and encoded
     Stream st;
@@ -703,10 +659,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 x[s][0] = p[0]; x[s][1] = p[1]; x[s][2] = p[2];
             } else {
                 const int ray = sidx(s) / spr;      // 32-bit: B < 2^31
-#ifdef MNRF_EXP_NO_POSLOAD      // experiment: upper bound of what prefetching the next tile's positions could save
-                x[s][0] = (float)(ray & 7) * 0.25f - 1.f; x[s][1] = (float)(sidx(s) & 15) * 0.125f - 1.f; x[s][2] = (float)(i & 3);
-                continue;
-#endif
                 const float* r = A.rays + (long long)ray * 8;
                 const float z = A.z_vals[i];
 #pragma unroll
@@ -737,11 +689,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 const int a = P - 3 * f;
                 const float xa = a == 0 ? x[s][0] : (a == 1 ? x[s][1] : x[s][2]);
                 float sn, cs;
-#ifdef MNRF_EXP_NO_ENC
-                sn = xa; cs = xa * 0.5f;
-#else
                 fast_sincos(ldexpf(xa, f), sn, cs);   // 2^f * x is exact (mirror_nerf.py:17, 36)
-#endif
                 if (P >= 30) {                       // raw coordinates ride in the last two pairs
                     sn = P == 30 ? x[s][0] : x[s][2];
                     cs = P == 30 ? x[s][1] : 0.f;
@@ -769,7 +717,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     const bool keep = !PLANES && GRAD && A.save_x != nullptr;     // training forward, fp32 rows (MNRF_DW_PLANES=0; tests)
     uint64_t unused_bits[S];
 
-    MNRF_MARK(1);   // prologue: bias copy, stream open, positions, encoding
     u32x4 hh[S][8], hl[S][8];
     f32x4 accA[S][8], accB[S][8];   // the two halves (row blocks 0-7, 8-15) of the layer in flight
     {
@@ -788,7 +735,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         init_bias_half(accB, BIAS_L, 1, gq());
         gemm_half<2, 2, GRAD, 0, 2 * S, 16>(accB, eh, el, st, wave, lane16, accA, hh, hl, 0, 0, mk);
         if (keep) save_acc<8, 1>(A.save_x + (long long)SEC_H * A.B, 256, 8, accB, idx, valid, g, unused_bits);
-        MNRF_MARK(2);   // L1
         // ---- L2..L4
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
@@ -803,7 +749,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             gemm_half<8, 8, GRAD, 4, S, 96, ST4>(accB, hh, hl, st, wave, lane16, accA, hh, hl, 0, 0, mk, at_h(l, 4));   // + half 1 of this layer
             if (keep) save_acc<8, 1>(A.save_x + (long long)(SEC_H + 256 * (1 + l)) * A.B, 256, 8, accB, idx, valid, g, unused_bits);
         }
-        MNRF_MARK(3);   // L2..L4
         // ---- L5: cat[enc, h] -> 256  (encoding first: mirror_nerf.py:192-193); the jobs ride on the 256-wide parts
         init_bias_half(accA, BIAS_L + 256 * 4, 0, gq());
         if (S == 3) {
@@ -845,7 +790,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         }
         gemm_half<8, 8, GRAD, 4, S, 512, ST4>(accB, hh, hl, st, wave, lane16, accA, hh, hl, 0, 0, mk, at_h(3, 4));
         if (keep) save_acc<8, 1>(A.save_x + (long long)(SEC_H + 256 * 4) * A.B, 256, 8, accB, idx, valid, g, unused_bits);
-        MNRF_MARK(4);   // L5
         // ---- L6..L8
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
@@ -869,7 +813,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 for (int s = 0; s < S; ++s) park[(T * S + s) * WG_THREADS + tid] = hl[s][T];
         }
         if (GRAD) store_mask(mk, 7, tid, gmask);
-#ifndef MNRF_EXP_CYCLES
         if (S != 3 && A.geo_feat) {     // (the 48-sample tuning has no registers to keep both halves: its launcher declines geo_feat)
             // h8 = geo_feat (mirror_nerf.py:195), fp32: the accumulators of both halves are still intact
 #pragma unroll
@@ -884,9 +827,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 }
             }
         }
-#endif
     }
-    MNRF_MARK(5);   // L6..L8
     // predicted normal = l2_normalize of registers R0 .. R0 + 2 of lane group 0 (mirror_nerf.py:85-88)
     const auto put_normal = [&](const f32x4 (&acc)[S][1], auto r0) {
         constexpr int R0 = decltype(r0)::value;
@@ -932,7 +873,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         if constexpr (FOLD) put_normal(acc, std::integral_constant<int, 1>{});
     }
 
-    MNRF_MARK(6);   // sigma head
     if (!SIGMA_ONLY) {
         // ---- predicted normal: 256 -> 128 -> 3, no activation in between (mirror_nerf.py:85-88); FOLD: done above
         if constexpr (!FOLD) {
@@ -950,7 +890,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             gemm_part<4, 1, 1032>(acc, nh, nl, st, wave, lane16);
             put_normal(acc, std::integral_constant<int, 0>{});
         }
-        MNRF_MARK(7);   // normal head
         // ---- mirror probability: 256 -> 128 LeakyReLU(0.01) -> 1 sigmoid (mirror_nerf.py:94-99)
         {
             u32x4 mh[S][4], ml[S][4];
@@ -983,7 +922,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                     if (sval(s)) out_store(A.is_mirror + sidx(s), sigmoidf_(acc[s][0][0]));
             }
         }
-        MNRF_MARK(8);   // mirror head
         // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid.  FOLD: dir_encoding reads h8
         //      through the folded map (final's 256 outputs are never formed)
         // view-encoding B operands (32 padded columns: one k-step)
@@ -1009,7 +947,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             if constexpr (FOLD) {
                 u32x4 vh[S][1], vl[S][1];
                 view_operands(vh, vl);
-                MNRF_MARK(9);   // view encoding load
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_DIR, gq());
                 gemm_part<8, 8, 1036, HP>(acc, hh, hl, st, wave, lane16);
@@ -1027,7 +964,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 }
                 u32x4 vh[S][1], vl[S][1];
                 view_operands(vh, vl);
-                MNRF_MARK(9);   // xyz_encoding_final + view encoding load
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_DIR, gq());
                 gemm_part<8, 8, 1232>(acc, fh, fl, st, wave, lane16);
@@ -1069,7 +1005,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         }
     }
 
-    MNRF_MARK(10);  // dir_encoding + rgb
     if (GRAD) {
         // ---- d sigma / d xyz in closed form (SURVEY 8a): g = w_sigma; for i = 8..1:
         //      g = (g * relu_mask_i) W_i, the 63 encoding columns of layer 5 and layer 1 feed g_enc.
@@ -1127,7 +1062,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                         for (int r = 0; r < 4; ++r) gr[s][4 * nb + r] = acc[s][nb][r];
             }
         }
-        MNRF_MARK(11);  // density-gradient pass (transposed trunk)
         // encoding Jacobian: d/dx_a = g[x_a] + sum_f 2^f (g[sin] cos - g[cos] sin)
         float x[S][3];
         fetch_positions(x);
@@ -1184,7 +1118,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             composite_ray(src, WG_SAMPLES, cl, ray, out);
         }
     }
-    MNRF_MARK(15);
     if (!queued) break;
     close_stream();
     __syncthreads();      // every wave is done with the ring, the parked operands and the head outputs of this tile
@@ -1203,7 +1136,6 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             atomicExch(A.tile_queue + 1, 0);
         }
     }
-#undef MNRF_MARK
 }
 
 inline int launch(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s) {

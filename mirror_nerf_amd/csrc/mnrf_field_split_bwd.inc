@@ -62,14 +62,9 @@ __device__ __forceinline__ void store_dy_planes(const StoreCtx& sc, int fb0, con
                 // (built element by element in an unrolled loop, `a[c] = ...`, hipcc 7.2 kept only element 0 of every operand:
                 // caught in the ISA, hence the explicit constructors)
                 const auto mul = [&](unsigned w) { return __builtin_bit_cast(unsigned, __builtin_bit_cast(h2v, w) * sc.fac[s]); };
-#ifdef MNRF_EXP_GLOBAL_STORES
-                *(u32x2*)(sc.base + off + sc.lane) = u32x2{mul(hi[s][T][2 * h]), mul(hi[s][T][2 * h + 1])};
-                *(u32x2*)(sc.base + off + PL_TILE_BYTES + sc.lane) = u32x2{mul(lo[s][T][2 * h]), mul(lo[s][T][2 * h + 1])};
-#else
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{mul(hi[s][T][2 * h]), mul(hi[s][T][2 * h + 1])}, sc.rsrc, sc.lane, off, PL_STORE_AUX);
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{mul(lo[s][T][2 * h]), mul(lo[s][T][2 * h + 1])}, sc.rsrc_lo, sc.lane,
                                                       off + PL_TILE_BYTES, PL_STORE_AUX);
-#endif
             }
 }
 
@@ -158,11 +153,9 @@ __global__ __launch_bounds__(WG_THREADS, 1) void field_split_bwd_kernel(FieldBwd
     }
 
     // operand planes: this lane's corner of the wave's sample block, and every sample's factor 2^(K - k_s)
-#ifndef MNRF_EXP_NO_WEAVE_BWD      // dY plane stores inside the GEMMs that read the same operands (default since round 5, see mnrf_field_split.inc:
-    constexpr bool WEAVE = PLANES;      // 4.34-4.36 against 4.44-4.50 ms per training step with only this kernel woven; round 3 measured a loss)
-#else
-    constexpr bool WEAVE = false;
-#endif
+    // dY plane stores inside the GEMMs that read the same operands (default since round 5, see mnrf_field_split.inc: 4.34-4.36
+    // against 4.44-4.50 ms per training step with only this kernel woven; round 3 measured a loss)
+    constexpr bool WEAVE = PLANES;
     char* const pl = PLANES ? A.dY_planes + ((long long)blockIdx.x * WAVES + wave) * PLY_SB_BYTES : nullptr;      // wave-uniform
     h2v fac[S];
     {
@@ -581,14 +574,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void field_split_bwd2_kernel(FieldBw
             int d = K2 - k[s];
             d = d > 0 ? 0 : d;      // (K2 <= k_s by construction; a zero / non-finite J^ keeps k_s = 0 and has zero tangents)
             const _Float16 f = d < -24 ? (_Float16)0.f : (_Float16)ldexpf(1.f, d);
-#ifdef MNRF_EXP_SO_FAC_ON_B      // experiment: the factor on the signals (tangent planes stored as they are); same accuracy measured
-            const _Float16 fb = d + PL_BOOST_LOG2 < -24 ? (_Float16)0.f : (_Float16)ldexpf(1.f, d + PL_BOOST_LOG2);
-            scx.fac[s] = h2v{(_Float16)1.f, (_Float16)1.f};
-            scy.fac[s] = h2v{fb, fb};
-#else
             scx.fac[s] = h2v{f, f};
             scy.fac[s] = h2v{(_Float16)(1 << PL_BOOST_LOG2), (_Float16)(1 << PL_BOOST_LOG2)};
-#endif
         }
         scx.rsrc = plane_rsrc(plx); scx.rsrc_lo = scx.rsrc; scx.base = plx; scx.lane = 32 * m + 8 * g; scx.soff = 0;
         scy.rsrc = plane_rsrc(ply); scy.rsrc_lo = scy.rsrc; scy.base = ply; scy.lane = 32 * m + 8 * g; scy.soff = 0;
@@ -611,21 +598,13 @@ __global__ __launch_bounds__(WG_THREADS, 1) void field_split_bwd2_kernel(FieldBw
     // ---- tangent forward pass (no bias; ReLU replaced by the saved masks), two halves of 8 row blocks per layer
     u32x4 eh[S][2], el[S][2];
     split_b<16>(te, eh, el, st.sat);
-#ifdef MNRF_EXP_SO_FAC_ON_B
-    if constexpr (PLANES) store_planes<2, 2>(scx, TA_ENC / 16, eh, el);
-#else
     if constexpr (PLANES) store_dy_planes<2, 2, 2>(scx, TA_ENC / 16, eh, el);
-#endif
     float t[S][64];
     u32x4 th[S][8], tl[S][8];
     // WEAVE2 (round 5, as in the first-order kernels): the 64 plane stores of a 256-wide section ride in the MFMA stream of the GEMM
     // that reads the same operands instead of going out in one burst; sections without such a GEMM behind them (the last tangent,
-    // the signal of layer 1) keep the burst.  -DMNRF_EXP_NO_WEAVE_BWD2 restores the bursts everywhere.
-#if !defined(MNRF_EXP_NO_WEAVE_BWD2) && !defined(MNRF_EXP_SO_FAC_ON_B)
+    // the signal of layer 1) keep the burst.
     constexpr bool WEAVE2 = PLANES;
-#else
-    constexpr bool WEAVE2 = false;
-#endif
     constexpr int SX0 = WEAVE2 ? 0 : -1, SX4 = WEAVE2 ? 4 : -1, SY0 = WEAVE2 ? 0 : -1;
     const auto at_x = [&](int layer, int T0) -> const StoreCtx& {      // operand T0 of tangent section `layer` (a'_(layer+1))
         scx.soff = (TA_H / 16 + 16 * layer + 2 * T0) * PL_FB_BYTES;
@@ -649,11 +628,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void field_split_bwd2_kernel(FieldBw
         }
         if constexpr (!PLANES) save_scaled<64>(A.so + (long long)(TA_H + 256 * layer) * A.B, 256, t, k, idx, valid, g);
         split_b<64>(t, th, tl, st.sat);
-#ifdef MNRF_EXP_SO_FAC_ON_B
-        if constexpr (PLANES) store_planes<8, 8>(scx, TA_H / 16 + 16 * layer, th, tl);
-#else
         if constexpr (PLANES) { if (!WEAVE2 || layer == 7) store_dy_planes<8, 2, 8>(scx, TA_H / 16 + 16 * layer, th, tl); }
-#endif
     };
     {
         f32x4 a0[S][8], a1[S][8];

@@ -1,6 +1,5 @@
-// mnrf_field_split_common.inc -- pieces shared by the split-f16 field kernels (mnrf_field_split.inc: 16x16x32 MFMAs,
-// mnrf_field_split32.inc: 32x32x16 MFMAs): the LDS-DMA weight stream, fast sincos, fp32 -> (hi, lo) conversion, the range
-// guard, hand-placed LDS reads.  Included inside a namespace that defines CHUNK_BYTES, CHUNK_PAIRS, RING_SLOTS, PIECES,
+// mnrf_field_split_common.inc -- pieces shared by the split-f16 field kernels (mnrf_field_split.inc, mnrf_field_split_bwd.inc):
+// the LDS-DMA weight stream, fast sincos, fp32 -> (hi, lo) conversion, the range guard, hand-placed LDS reads.  Included inside a namespace that defines CHUNK_BYTES, CHUNK_PAIRS, RING_SLOTS, PIECES,
 // WAVES, PF (and `smem`).
 // ------------------------------------------------------------------ weight stream
 // The f16 pipe consumes a 16 KiB chunk in ~800 cycles (the fp32 kernel: 4096), so the cost of issuing
@@ -39,7 +38,6 @@ struct Stream {
 
 template <int I>
 __device__ __forceinline__ void issue_piece(Stream& st) {
-#ifndef MNRF_EXP_NO_DMA
     const unsigned lds = st.wave_lds + st.fill_slot * CHUNK_BYTES + (I / 4) * 4096;   // the immediate is 13-bit signed
     const unsigned long long src = st.fill_src + (I / 4) * 4096;
     // The instruction's immediate offset is added to BOTH the global and the LDS address, so the four pieces of a 4 KiB
@@ -50,7 +48,6 @@ __device__ __forceinline__ void issue_piece(Stream& st) {
     // before a VMEM read; padding it with s_nop 3 cost 4 % (an extra issue state between MFMAs is a cliff, not a slope).
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)src + st.lane_off),
                                      (__attribute__((address_space(3))) void*)(size_t)lds, 16, (I % 4) * TILE_BYTES, 0);
-#endif
     if (I == PIECES - 1) {
         st.fill_src += CHUNK_BYTES;
         st.fill_slot = st.fill_slot == RING_SLOTS - 1 ? 0 : st.fill_slot + 1;
@@ -77,14 +74,10 @@ static_assert(PIECES == 4 || PIECES == 8, "issue_rest");
 // Make the next chunk readable; YOUNGER = pieces this wave has issued after that chunk's.
 template <int YOUNGER>
 __device__ __forceinline__ void seam(Stream& st) {
-#if !defined(MNRF_EXP_NO_DMA) && !defined(MNRF_EXP_NO_SYNC)
-#ifndef MNRF_EXP_NO_VMWAIT
     asm volatile("s_waitcnt vmcnt(%0)" : : "n"(YOUNGER) : "memory");
-#endif
     // raw s_barrier, not __syncthreads(): LDS reads of the previous chunk may stay in flight across it
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#endif
     st.rd_slot = st.rd_slot == RING_SLOTS - 1 ? 0 : st.rd_slot + 1;
 }
 
@@ -135,11 +128,6 @@ __device__ __forceinline__ void fast_sincos(float a, float& sn, float& cs) {
 // v_cvt_pkrtz_f16_f32 rounds toward zero, so lo = x - hi has the sign of x: |x - hi - lo| < 2^-20 |x|.
 __device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigned& lo) {
     const auto h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-#ifdef MNRF_EXP_NO_CONV
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = 0x04000400u;
-    return;
-#endif
     const float r0 = x0 - (float)h[0];
     const float r1 = x1 - (float)h[1];
     const auto l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
@@ -160,15 +148,11 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigne
 constexpr float F16_MAX = 65504.f;
 template <bool NONNEG>
 __device__ __forceinline__ void sat_track(float& tmax, float a, float b) {
-#ifndef MNRF_EXP_NO_GUARD
     tmax = NONNEG ? __builtin_fmaxf(__builtin_fmaxf(tmax, a), b) : __builtin_fmaxf(__builtin_fmaxf(tmax, fabsf(a)), fabsf(b));
-#endif
 }
 __device__ __forceinline__ void sat_flush(unsigned long long& sat, float& tmax, float limit = F16_MAX) {
-#ifndef MNRF_EXP_NO_GUARD
     sat |= __builtin_amdgcn_ballot_w64(!(tmax < limit));
     tmax = 0.f;
-#endif
 }
 // `who`: which pass saturated (MNRF_GUARD_IN_*: diagnostics only -- the host reports it with the warning)
 __device__ __forceinline__ void guard_report(const float* packed, unsigned long long sat, unsigned long long enc_range, unsigned who = 0u) {
@@ -185,10 +169,6 @@ __device__ __forceinline__ void guard_report(const float* packed, unsigned long 
 // for why the wait carries the tiles as in/out operands).
 
 __device__ __forceinline__ void lds_read_half_tile(u32x4& dst, unsigned addr, int off) {
-#ifdef MNRF_EXP_NO_READ
-    asm volatile("v_mov_b32 %0, %1" : "=v"(dst.x) : "v"(addr));
-    return;
-#endif
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off) : "memory");
 }
 

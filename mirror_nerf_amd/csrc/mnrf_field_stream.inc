@@ -26,11 +26,6 @@ __device__ __forceinline__ void issue_chunk(const Stream& st, int chunk, int wav
 // Make chunk (st.next-1) readable and start the copy of chunk st.next.  The slot that copy
 // overwrites held chunk st.next-3, which every wave finished before reaching this barrier.
 __device__ __forceinline__ void advance(Stream& st, int wave) {
-#ifdef MNRF_EXP_NO_DMA
-    st.rd_slot = st.rd_slot == RING_SLOTS - 1 ? 0 : st.rd_slot + 1;
-    st.next += 1;
-    return;
-#endif
     // My pieces of chunk next-1 have landed (vmcnt); everybody's have (barrier).  A raw s_barrier,
     // not __syncthreads(): LDS reads of the current chunk may stay in flight across it (they target
     // a slot that is not rewritten before the next advance), so lgkmcnt is deliberately not drained.

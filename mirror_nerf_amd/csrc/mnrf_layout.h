@@ -126,30 +126,8 @@ constexpr int SPLIT_HBWD_PAIRS = padded_pairs(8 + 64 + 8 + 128 + 8 + 64 + 8 + 64
 constexpr int64_t OFF_SPLIT_FWD = PACKED_F32_FLOATS;
 constexpr int64_t OFF_SPLIT_BWD = OFF_SPLIT_FWD + (int64_t)SPLIT_FWD_PAIRS * (PAIR_BYTES / 4);
 constexpr int64_t OFF_SPLIT_HBWD = OFF_SPLIT_BWD + (int64_t)SPLIT_BWD_PAIRS * (PAIR_BYTES / 4);
-// ---- forward stream of the 32x32x16 tuning (mnrf_field_split32.inc; inference only).  One MFMA there contracts 16 columns
-//      for a block of 32 rows: a pair = [hi tile][lo tile] of a 32-row x 16-column block, half e (0..7) of lane l =
-//      W[32*nb + (l&31)][col32(T, l>>5, e)].  The accumulator of a 32x32 MFMA holds, in register r of lane half h = l>>5,
-//      row 8*(r>>2) + 4*h + (r&3) of its block, so registers 8c..8c+7 of block nb ARE the lane's 8 halves of k-step
-//      T = 2*nb + c of the next layer -- col32_h(T, h, e) = 16*T + 8*(e>>2) + 4*h + (e&3) -- and activations stay in
-//      their lanes exactly as in the 16x16 layout.  Same part sequence as the 16x16 stream (trunk layers in two halves of
-//      four 32-row blocks); 1- and 3-row heads are padded to 32 rows.  Positions (pairs): trunk as above (L1 0|16 ...
-//      L8 832|896), sigma 960, normal_net.0 976, normal_net.1 1040, is_mirror_net.0 1048, is_mirror_net.2 1112,
-//      xyz_encoding_final 1120, dir_encoding 1248 (final) 1312 (view), rgb 1320, end 1328.
-constexpr int SPLIT32_FWD_USED_SIGMA = 960 + 16;
-constexpr int SPLIT32_FWD_USED = SPLIT32_FWD_USED_SIGMA + 64 + 8 + 64 + 8 + 128 + 64 + 8 + 8;      // 1328
-constexpr int SPLIT32_FWD_PAIRS = padded_pairs(SPLIT32_FWD_USED);
-constexpr int64_t OFF_SPLIT32_FWD = OFF_SPLIT_HBWD + (int64_t)SPLIT_HBWD_PAIRS * (PAIR_BYTES / 4);
-// xyz encoding column held by lane half h at k-step T (0..3), half e of a 32x32x16 ENC part: pair P = 16*h + 4*T + (e>>1)
-__host__ __device__ inline int enc_col32(int T, int h, int e) {
-    const int P = 16 * h + 4 * T + (e >> 1);
-    const int s = e & 1;
-    if (P < 30) return 3 + 6 * (P / 3) + 3 * s + (P % 3);
-    if (P == 30) return s;
-    return s == 0 ? 2 : -1;
-}
 // tail pad: the split kernel's static LDS-DMA schedule reads two chunks (of up to 32 KiB) past the end of a stream
 constexpr int64_t SPLIT_TAIL_FLOATS = 2 * 16 * (PAIR_BYTES / 4);
-constexpr int64_t PACKED_FLOATS = OFF_SPLIT32_FWD + (int64_t)SPLIT32_FWD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
 // ---- FOLDED forward stream of the forward-only split kernels (mnrf_field_split.inc FOLD).  Two head Linears of the model have
 //      no activation behind them: normal_net = Linear(256,128) -> Linear(128,3) is one 3 x 256 map W2.W1 (bias W2.b1 + b2), and
 //      xyz_encoding_final only feeds dir_encoding, whose first 256 columns Wd times it are one 128 x 256 map Wd.Wf on h8 (bias
@@ -158,11 +136,14 @@ constexpr int64_t PACKED_FLOATS = OFF_SPLIT32_FWD + (int64_t)SPLIT32_FWD_PAIRS *
 //      the folded normal in rows 1..3), is_mirror_net.0 968, is_mirror_net.2 1032, dir_encoding 1036 (folded h8 columns) 1100
 //      (view), rgb 1108, end 1112 -- 1112 pairs per full sample instead of 1308.  Behind its read-ahead tail lies a copy of the
 //      bias block with the folded biases in place (normal at BIAS_SIG + 1..3, dir_encoding at BIAS_DIR).
-//      It occupies the region of the 32x32x16 tuning's stream, so it exists only while MNRF_SPLIT32 is off (the default).
+//      The region is reserved at FOLD_REGION_PAIRS pairs, more than the stream needs: the image keeps its size and the device-state
+//      words at its end keep their offsets (shrinking it would move them and change the kernels' immediates).
+constexpr int FOLD_REGION_PAIRS = 1328;
 constexpr int SPLIT_FOLD_USED = 960 + 8 + 64 + 4 + 64 + 8 + 4;                                      // 1112
 constexpr int SPLIT_FOLD_PAIRS = padded_pairs(SPLIT_FOLD_USED);                                      // 1120
-constexpr int64_t OFF_FOLD_FWD = OFF_SPLIT32_FWD;
+constexpr int64_t OFF_FOLD_FWD = OFF_SPLIT_HBWD + (int64_t)SPLIT_HBWD_PAIRS * (PAIR_BYTES / 4);
 constexpr int64_t OFF_FOLD_BIAS = OFF_FOLD_FWD + (int64_t)SPLIT_FOLD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
+constexpr int64_t PACKED_FLOATS = OFF_FOLD_FWD + (int64_t)FOLD_REGION_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
 // The last words of the image (inside the tail pad, whose contents no kernel consumes) are CALLER-OWNED device state of the
 // launches that use this image: [PACKED_FLOATS - 1] the range-guard word (mnrf.h), before it TQ_PAIRS {next, done} counter
 // pairs of the dynamic tile queue (mnrf_field_split3.hip).  mnrf_pack_weights zeroes all of them.
@@ -173,7 +154,7 @@ constexpr int64_t OFF_TILE_QUEUE = PACKED_FLOATS - 1 - 2 * TQ_PAIRS;
 // workgroup out hands the value over and resets both words -- so a reduction needs no zero-fill launch in front of it
 constexpr int64_t OFF_REDUCE_PAIR = OFF_TILE_QUEUE - 2;
 constexpr int DEVICE_STATE_WORDS = 2 + 2 * TQ_PAIRS + 1;      // what mnrf_pack_weights zeroes, from OFF_REDUCE_PAIR on
-static_assert(OFF_FOLD_BIAS + BIAS_FLOATS <= OFF_REDUCE_PAIR, "the folded stream and its bias block fit the 32x32x16 region");
+static_assert(OFF_FOLD_BIAS + BIAS_FLOATS <= OFF_REDUCE_PAIR, "the folded stream, its read-ahead tail and its bias block fit the reserved region");
 
 // ---- activations saved by the training forward, [section][sample][width], B-form column order
 constexpr int SEC_ENC = 0;            // 64   xyz encoding in (sin,cos)-pair order (enc_col)

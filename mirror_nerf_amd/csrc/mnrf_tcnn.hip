@@ -20,15 +20,8 @@
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
 
-// per-sample outputs of the matrix-pipe kernel: -DMNRF_EXP_TCNN_OUT_NT stores them non-temporally (experiment: 201 MB of outputs
-// per launch compete with the 53 MB table for the 256 MB Infinity Cache)
-#ifdef MNRF_EXP_TCNN_OUT_NT
-#define TOUT(p, v) __builtin_nontemporal_store((float)(v), (float*)(p))
-#elif defined(MNRF_EXP_TCNN_NO_STORES)      // experiment: the MLP launch without its output traffic (the compiler must keep the arithmetic)
-#define TOUT(p, v) do { const float tout_v = (v); if (tout_v == 1234.56787109375f) *(p) = tout_v; } while (0)
-#else
+// per-sample outputs of the matrix-pipe kernel: plain stores
 #define TOUT(p, v) (*(p) = (v))
-#endif
 
 namespace {
 
@@ -424,20 +417,12 @@ namespace mf {
 // Waves per workgroup.  Round 6: EIGHT (was six).  A CU has four SIMDs and a workgroup's waves are dealt to them in turn: six waves
 // leave two SIMDs with two waves and two with one, and the kernel -- bound by its own VALU / MFMA instruction stream, not by memory
 //  -- then runs at the pace of the loaded pair.  One 32768-ray chunk's fine pass, encoding + MLP launch, alternating
-// libraries on one box (scripts/exp_tcnn_mlp_parts.py, profiles/r06_tcnn_waves.txt): 6 waves 2.24 ms (hi/lo) / 1.76 (f16 MLPs),
+// libraries on one box (profiles/r06_tcnn_waves.txt): 6 waves 2.24 ms (hi/lo) / 1.76 (f16 MLPs),
 // 4 waves 2.10 / 1.72, **8 waves 2.05 / 1.63**, 10 waves 2.12 / 1.73, 12 waves 2.02 / 1.66, 16 waves 2.03 / 1.62: every multiple
 // of four beats its neighbours; 8 is the smallest workgroup of the fast group for both arithmetics.
-#ifndef MNRF_EXP_TCNN_WAVES
-#define MNRF_EXP_TCNN_WAVES 8
-#endif
-#ifndef MNRF_EXP_TCNN_MINWG
-#define MNRF_EXP_TCNN_MINWG 2
-#endif
-constexpr int WAVES = MNRF_EXP_TCNN_WAVES;
-#ifndef MNRF_EXP_TCNN_NG
-#define MNRF_EXP_TCNN_NG 2
-#endif
-constexpr int NG = MNRF_EXP_TCNN_NG;                // groups of 16 samples per wave iteration (4: 800 B/lane of spills at 256 registers)
+constexpr int WAVES = 8;
+constexpr int MIN_WG = 2;                           // second __launch_bounds__ argument of tcnn_mfma_kernel
+constexpr int NG = 2;                               // groups of 16 samples per wave iteration (4: 800 B/lane of spills at 256 registers)
 constexpr int TILE = WAVES * NG * 16;               // samples per workgroup iteration
 constexpr int NT_FWD = 29;                          // tile pairs
 constexpr int PAIR_B = 2048;
@@ -614,13 +599,10 @@ __device__ __forceinline__ void encode_level_p(const float* table, const LevelP&
 // two rays, 256 depths.  ENC_PATCH_RAYS = R > 1: a PATCH of R consecutive rays x 256 / R consecutive depths: neighbouring rays of a
 // chunk are neighbouring pixels, whose samples at equal depth share grid cells up to the middle levels, so the lanes of a wave
 // instruction fall on fewer distinct cache lines (the launch is bound by the vector L1's requests to the L2, not by bytes: 4.3).
-// Measured on one 32768-ray chunk of the bench frame, fine pass (scripts/exp_tcnn_encode.py, alternating libraries, identical
+// Measured on one 32768-ray chunk of the bench frame, fine pass (alternating libraries, identical
 // outputs): 1.68 ms per launch flat, 1.55 with 4 rays x 64 depths, 1.32 with 8 x 32, 1.28 with 16 x 16, **1.27 with 32 x 8** (a wave = 8
 // rays x 8 depths), 1.45 with 64 x 4.  Falls back to the flat map when the shape does not tile (spr % 8, rays % 32) or with xyz input.
-#ifndef MNRF_EXP_ENC_PATCH_RAYS
-#define MNRF_EXP_ENC_PATCH_RAYS 32
-#endif
-constexpr int ENC_PATCH_RAYS = MNRF_EXP_ENC_PATCH_RAYS;
+constexpr int ENC_PATCH_RAYS = 32;
 __global__ __launch_bounds__(256) void tcnn_encode_kernel(TcnnArgs A) {
     live_rows(A);
     const int lv = blockIdx.y;
@@ -629,13 +611,11 @@ __global__ __launch_bounds__(256) void tcnn_encode_kernel(TcnnArgs A) {
         constexpr int PS = 256 / ENC_PATCH_RAYS;                  // depths per patch
         const int groups = A.spr / PS;                            // patches along a ray
         long long patch = blockIdx.x;
-#ifndef MNRF_EXP_ENC_NO_XCD
         // workgroups go round-robin over the 8 XCDs, each with its own L2: XCD k takes the k-th contiguous eighth of the patches (a
         // contiguous range of rays with all their depths) instead of every eighth patch.  Same chunk as above, alternating libraries:
         // 1.27 -> 1.24 ms per launch with the float2 table, 1.23 -> 1.13 ms with the half2 table.  (Patches ordered depth slab by
         // depth slab instead: 1.26 / 1.16 ms without this map, 1.37 / 1.30 with it.)
         if (gridDim.x % 8 == 0) patch = (patch % 8) * (gridDim.x / 8) + patch / 8;
-#endif
         const long long ray0 = patch / groups * ENC_PATCH_RAYS;
         const int s0 = (int)(patch % groups) * PS;
         // lanes: depth fastest within PS, then ray -- a wave of 64 covers 64 / PS rays x PS depths (PS < 64) or one ray (PS >= 64)
@@ -671,7 +651,7 @@ __global__ __launch_bounds__(256) void tcnn_encode_kernel(TcnnArgs A) {
 }
 
 template <int MODE, bool PLANES = false>
-__global__ __launch_bounds__(64 * WAVES, MNRF_EXP_TCNN_MINWG) void tcnn_mfma_kernel(TcnnArgs A, int n_tiles) {
+__global__ __launch_bounds__(64 * WAVES, MIN_WG) void tcnn_mfma_kernel(TcnnArgs A, int n_tiles) {
     live_rows(A);
     if (A.n_live) n_tiles = (int)((A.B + TILE - 1) / TILE);
     if (n_tiles <= 0) return;
@@ -741,11 +721,7 @@ __global__ __launch_bounds__(64 * WAVES, MNRF_EXP_TCNN_MINWG) void tcnn_mfma_ker
             for (int q = 0; q < 4; ++q) {
                 float g0[3], g1[3];
                 if (PLANES) {      // written level by level by tcnn_encode_kernel
-#ifdef MNRF_EXP_TCNN_NO_PLANE_LOADS      // experiment: the MLP launch without its input traffic
-                    const float2 v = make_float2(0.01f * (float)((idx[gi] + q) & 63), 0.02f * (float)((idx[gi] >> 3) & 31));
-#else
                     const float2 v = ((const float2*)A.enc)[(long long)(4 * g + q) * A.Bs + idx[gi]];
-#endif
                     f8[2 * q] = v.x; f8[2 * q + 1] = v.y;
                 } else {
                     encode_level_p<false>(A.table, lvl[q], u[gi], oob[gi], f8[2 * q], f8[2 * q + 1], g0, g1, A.table_f16);
@@ -914,7 +890,6 @@ struct TcnnBwdArgs {
     int cp_n[NL];                                // copies of level lv (0: straight into d_table)
     long long cp_off[NL];                        // float offset of the level's first copy in `copies`
     int agg_levels;                              // levels [0, agg_levels) sum runs of equal cells inside the wave first
-    int exp_noscatter;                           // experiment (MNRF_EXP_TCNN_NOSCATTER): skip the table atomics
     // gradient steering (models/mirror_nerf_tcnn.py:186-215, the --detach_density_* options): a head that sees geo_feat.detach()
     // still gets its own weight gradients but adds nothing to dL/d geo_feat
     unsigned cut;                                // MNRF_CUT_NORMAL_HEAD | MNRF_CUT_MIRROR_HEAD
@@ -1060,7 +1035,7 @@ __device__ __forceinline__ void scatter_corners(const TcnnBwdArgs& P, int lv, co
                                                 bool active, int lane, float* dtab, unsigned hsize, unsigned res, int own = -1) {
     const TcnnArgs& A = P.f;
     const bool head = aggregate_runs(P, lv, pg, v0, v1, active, lane);
-    if (active && head && !P.exp_noscatter && P.g16 && !P.cp_n[lv]) {      // (wave-uniform choice)
+    if (active && head && P.g16 && !P.cp_n[lv]) {      // (wave-uniform choice)
         __half2* h = P.g16 + A.off[lv];
         const float k = P.g16_scale;
 #pragma unroll
@@ -1068,14 +1043,12 @@ __device__ __forceinline__ void scatter_corners(const TcnnBwdArgs& P, int lv, co
             const unsigned idx = grid_index(pg[0] + (c & 1), pg[1] + ((c >> 1) & 1), pg[2] + ((c >> 2) & 1), hsize, res, A.mode[lv]);
             unsafeAtomicAdd(h + idx, __floats2half2_rn(v0[c] * k, v1[c] * k));
         }
-    } else if (active && head && !P.exp_noscatter) {
+    } else if (active && head) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const unsigned idx = grid_index(pg[0] + (c & 1), pg[1] + ((c >> 1) & 1), pg[2] + ((c >> 2) & 1), hsize, res, A.mode[lv]);
             fadd(dtab + 2ll * idx, v0[c]);
-#ifndef MNRF_EXP_TCNN_HALF_SCATTER      // experiment (wrong gradients): is the scatter bound by the NUMBER of atomics?  If so, one packed
-            fadd(dtab + 2ll * idx + 1, v1[c]);      // 2 x f16 atomic per entry (tinycudann's choice) would halve it.
-#endif
+            fadd(dtab + 2ll * idx + 1, v1[c]);
         }
     }
 }
@@ -1696,7 +1669,7 @@ __global__ __launch_bounds__(256) void tcnn_scatter_fx_kernel(TcnnBwdArgs P) {
             }
             const bool head = aggregate_runs(P, lv, pg, v0, v1, active, lane);
             const float k = fx_scale(P.ssum[lv]);
-            if (!(active && head) || k == 0.f || P.exp_noscatter) continue;
+            if (!(active && head) || k == 0.f) continue;
             unsigned long long* fx = P.fx + A.off[lv];
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
@@ -2005,7 +1978,6 @@ static int tcnn_backward_impl(const float* table, const int64_t* offsets17_host,
         static const float scale = [] { const char* e = getenv("MNRF_TCNN_GRAD_SCALE"); return e && atof(e) > 0 ? (float)atof(e) : 1024.f; }();
         P.g16_scale = scale;       // tinycudann's loss scale is 128; 1024 keeps 1e-7-sized contributions above f16's subnormal step
     }
-    P.exp_noscatter = getenv("MNRF_EXP_TCNN_NOSCATTER") != nullptr;
     P.agg_levels = 0;
     // measured (1 M samples, bound 6): 15.96 / 15.00 / 14.12 / 13.77 / 13.70 ms per step with runs summed up to resolution
     // 64 / 128 / 256 / 512 / 1000 -- the shuffles are cheap next to an atomic, so every level the key can hold takes part

@@ -48,7 +48,7 @@ PRECISION = os.environ.get("MNRF_PRECISION", "split")
 def set_precision(mode):
     """Select the arithmetic of the inference field kernel: "fp32" or "split"."""
     global PRECISION
-    if mode not in ("fp32", "split", "split_h2", "split_h2x", "split_h1"):
+    if mode not in ("fp32", "split"):
         raise ValueError("precision must be 'fp32' or 'split'")
     PRECISION = mode
 
@@ -100,11 +100,11 @@ def check_guard(modules):
     `.models` dict).  Returns True when a module running the split arithmetic tripped: it has then been switched to the
     fp32 kernels (sticky, see reset_guard) and the caller must repeat the work whose results it was about to use.
     Custom training loops call it after `loss.backward()`; the drivers of this package call it themselves."""
-    if not GUARD or not PRECISION.startswith("split"):
+    if not GUARD or PRECISION != "split":
         return False
     if hasattr(modules, "models"):
         modules = list(modules.models.values())
-    modules = [m for m in dict.fromkeys(modules) if isinstance(m, MirrorNeRF) and precision_of(m).startswith("split")]
+    modules = [m for m in dict.fromkeys(modules) if isinstance(m, MirrorNeRF) and precision_of(m) == "split"]
     if not modules:
         return False
     tripped = False
@@ -153,11 +153,11 @@ def guard_async_begin(modules):
     """Training: start an asynchronous read of the guard words (device -> pinned host memory on the current stream) and
     return a token for guard_async_end.  Unlike check_guard this does not drain the GPU queue: the host keeps running ahead
     of the device across the optimizer step (a synchronous read costs ~0.5 ms of an 8 ms step)."""
-    if not GUARD or not PRECISION.startswith("split"):
+    if not GUARD or PRECISION != "split":
         return None
     if hasattr(modules, "models"):
         modules = list(modules.models.values())
-    modules = [m for m in dict.fromkeys(modules) if isinstance(m, MirrorNeRF) and precision_of(m).startswith("split")
+    modules = [m for m in dict.fromkeys(modules) if isinstance(m, MirrorNeRF) and precision_of(m) == "split"
                and m.__dict__.get("_mnrf_packed") is not None and m.__dict__["_mnrf_packed"].packed is not None]
     if not modules:
         return None
@@ -212,7 +212,7 @@ def guard_async_end(token, adapt=False):
     ev.synchronize()
     tripped = False
     for m, w, r0 in zip(modules, host.tolist(), issued_with):
-        if w and precision_of(m).startswith("split"):
+        if w and precision_of(m) == "split":
             if adapt and r0 is not None and m.__dict__.get("_mnrf_seed_reduction", 0) > r0 and (w & 256) and not (w & (2 | 4 | 128 | 512)):
                 # the step behind this token was queued before the previous trip's adaptation took effect (flags are settled one
                 # step late): its backward overflowed at the OLD scale -- the update was vetoed on the device like the first one's,
@@ -276,7 +276,7 @@ def field_forward(module, B, *, xyz=None, xyz_stride=3, rays=None, z_vals=None, 
                   dir_stride=27, sigma_only=False, grad_normal=False, want_geo=False, device=None):
     """Run the fused field kernel; returns flat per-sample tensors (sigma (B,), rgb (B,3), ...)."""
     # (the full forward-only split launches read the image's folded head stream: weights.folded_of)
-    packed = folded_of(module) if precision_of(module).startswith("split") and not sigma_only and not grad_normal else packed_of(module)
+    packed = folded_of(module) if precision_of(module) == "split" and not sigma_only and not grad_normal else packed_of(module)
     dev = packed.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
     out = {"sigma": f(B)}
@@ -295,12 +295,6 @@ def field_forward(module, B, *, xyz=None, xyz_stride=3, rays=None, z_vals=None, 
     prec = precision_of(module)
     if prec == "split":
         flags |= _lib.MNRF_SPLIT_F16
-    elif prec == "split_h2":    # experiments only: force 16 KiB chunks
-        flags |= _lib.MNRF_SPLIT_F16 | 8
-    elif prec == "split_h2x":   # experiments only: force 32 KiB chunks
-        flags |= _lib.MNRF_SPLIT_F16 | 16
-    elif prec == "split_h1":    # experiments only (library built with -DMNRF_EXP_H1)
-        flags |= _lib.MNRF_SPLIT_F16 | 24
     p = _lib.ptr
     if LAUNCH_LOG is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

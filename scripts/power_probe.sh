@@ -1,6 +1,6 @@
 #!/bin/bash
-# Board power and shader clock (rocm-smi) while the dominant kernels run back to back: split-f16 (default and 32x32x16 tuning)
-# and the bit-exact fp32 kernels.  One sample per second over ~8 s of rendering each.
+# Board power and shader clock (rocm-smi) while the dominant kernels run back to back: split-f16 and the bit-exact fp32 kernels.
+# One sample per second over ~8 s of rendering each.
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/power_probe
@@ -30,6 +30,5 @@ PY
   done
   wait $pid
 }
-probe split PREC=split MNRF_SPLIT32=0
-probe split32 PREC=split MNRF_SPLIT32=1
+probe split PREC=split
 probe fp32 PREC=fp32

@@ -869,22 +869,19 @@ def test_verify_split_reports_range_problems(precision):
     assert MN.PRECISION == "split"
 
 
-@pytest.mark.parametrize("switch", ["MNRF_SPLIT32=1", "MNRF_SPLIT48=0"])
-def test_split32_tuning_passes_the_parity_suite(switch):
+def test_split48_off_passes_the_parity_suite():
     """The forward-only split launches run on the 48-samples-per-wave tuning by default (csrc/mnrf_field_split3.hip, DESIGN
-    9.2).  MNRF_SPLIT48=0 puts them back on the 32-samples-per-wave kernels (still the ones a geo_feat request gets),
-    MNRF_SPLIT32=1 on the 32x32x16 tuning (csrc/mnrf_field_split32.inc: fewer cycles, lower clock -- DESIGN 9.1).  The
-    switches are read once per process, so the field / render / recursion parity tests, the random-shape schedule check and
-    the range-guard tests run again in a child process for each."""
+    9.2).  MNRF_SPLIT48=0 puts them back on the 32-samples-per-wave kernels (still the ones a geo_feat request gets).  The
+    switch is read once per process, so the field / render / recursion parity tests, the random-shape schedule check and
+    the range-guard tests run again in a child process with it."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    name, val = switch.split("=")
-    env = dict(os.environ, **{name: val})
+    env = dict(os.environ, MNRF_SPLIT48="0")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(root, "tests", "test_hip_parity.py"),
                         os.path.join(root, "tests", "test_hip_guard.py"), "-k",
-                        "split and not split32 or field_golden or render_rays_golden or recursion_eval or trained_weights_eval "
+                        "split and not split48_off or field_golden or render_rays_golden or recursion_eval or trained_weights_eval "
                         "or ragged or threshold or saturation or falls_back"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
@@ -914,7 +911,7 @@ def test_fused_fine_pass_gives_the_same_maps_bit_for_bit(name, precision):
     fused = render(rays, _maps_only=True)
     for k in MAP_KEYS:
         assert np.array_equal(fused[k], got[k]), k
-    fusable = precision == "split" and os.environ.get("MNRF_SPLIT32", "0") != "1" and os.environ.get("MNRF_SPLIT48", "1") != "0"
+    fusable = precision == "split" and os.environ.get("MNRF_SPLIT48", "1") != "0"
     if fusable:      # (other tunings of the field kernel: the request falls back to the two-kernel path, keys and all)
         assert "weights_fine" not in fused and "pred_normal_fine" not in fused
     assert "weights_coarse" in fused and "z_vals_fine" in fused
@@ -957,7 +954,7 @@ def test_fused_eval_through_the_recursion(precision):
     assert other["rgb_fine"].shape[0] == 300 and not other["rgb_fine"].is_pinned()
     for k, v in host.items():
         assert torch.equal(v, keep[k]), k
-    if precision == "split" and os.environ.get("MNRF_SPLIT32", "0") != "1" and os.environ.get("MNRF_SPLIT48", "1") != "0":
+    if precision == "split" and os.environ.get("MNRF_SPLIT48", "1") != "0":
         assert "weights_fine" not in maps
     # N_importance = 64 (128 samples per ray) is not the fused launch class: the request is honoured by the two-kernel path
     a = M.batched_inference(models, _emb(), rays, 64, 64, False, 200, args=args, trace_secondary_rays=True, to_cpu=False)
