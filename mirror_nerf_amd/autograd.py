@@ -9,16 +9,11 @@ import os
 
 # MNRF_FOLD_GRADS=0: leave the accumulation of a module's parameter gradients over its evaluations to autograd
 FOLD_GRADS = os.environ.get("MNRF_FOLD_GRADS", "1") != "0"
-# MNRF_DW_PLANES=0: the round-1/2 weight-gradient route of the split arithmetic (fp32 rows of saved activations and of dY, one
-# set of bf16 x 6 GEMM launches per evaluation) instead of operand planes + ONE GEMM launch per module and pass (mnrf_dwp.h)
-RAY_GRADS_KERNEL = os.environ.get("MNRF_RAY_GRADS", "1") != "0"      # 0: the torch ops it replaced (A/B measurements)
-DW_PLANES = os.environ.get("MNRF_DW_PLANES", "1") != "0"
 # MNRF_DW_PLANES_HALF=1 (round 6, opt-in, NOT exact): the activation gradients travel to the weight-gradient GEMM as one f16 per
 # element instead of a hi/lo pair (include/mnrf.h MNRF_PLANES_Y_HALF): half the backward kernel's plane traffic, 3/4 of the GEMM's.
 # Emulated on the reference in float64 first (scripts/exp_half_planes.py): 1.2e-4 .. 7.4e-4 of a tensor's largest entry, inside the
 # 1e-3 bar of the gradient fixtures with a margin of 1.3 x at worst -- which is why it is not the default.
 DW_PLANES_HALF = os.environ.get("MNRF_DW_PLANES_HALF", "0") == "1"
-DW2_PLANES = os.environ.get("MNRF_DW2_PLANES", "1") != "0"    # 0: the second-order term on fp32 rows (mnrf_field_backward2)
 
 
 def _c(t):
@@ -147,7 +142,7 @@ class FieldFn(torch.autograd.Function):
         sigma, rgb, pn, mir = f(B), f(B, 3), f(B, 3), f(B)
         normal = f(B, 3) if want_normal else None
         split = _mn.precision_of(module) == "split"
-        planes = split and DW_PLANES
+        planes = split      # the split arithmetic saves operand planes (mnrf_dwp.h), the fp32 one fp32 rows
         if ctx.n_live is not None and not planes:
             raise RuntimeError("a live row count (static training step) needs the split arithmetic with operand planes")
         if planes:     # the inputs of every Linear as hi/lo f16 operand tiles of the weight-gradient GEMM (mnrf_dwp.h)
@@ -213,7 +208,7 @@ class FieldFn(torch.autograd.Function):
         # outputs never reached the loss): gradients still pending then are added to `.grad` directly.
         #   planes route (split arithmetic, default): an evaluation only runs its activation-gradient kernel and leaves
         #   its operand planes on the module's TAPE; the last one launches the weight-gradient GEMM once over the whole tape;
-        #   rows route (fp32 arithmetic, MNRF_DW_PLANES=0): every evaluation runs its own GEMMs, adding into the tensors.
+        #   rows route (fp32 arithmetic): every evaluation runs its own GEMMs, adding into the tensors.
         mod = ctx.module
         uses = max(0, mod.__dict__.get("_mnrf_uses", 1) - 1)
         mod.__dict__["_mnrf_uses"] = uses
@@ -253,7 +248,7 @@ class FieldFn(torch.autograd.Function):
                 (_lib.MNRF_SPLIT_F16 if ctx.split else 0) | ctx.cut | (_lib.MNRF_DW_ACCUMULATE if st.dirty else 0), _lib.stream()),
                 "mnrf_field_backward")
             st.dirty = True
-        if B and g_normal is not None and normal is not None and ctx.planes and DW2_PLANES:
+        if B and g_normal is not None and normal is not None and ctx.planes:
             # second-order term through the density-gradient normal, planes route (round 4): the tangent pass leaves its
             # operands on the tape as one more entry (kind 1); the module's ONE weight-gradient GEMM contracts them too
             x2 = torch.empty(max(16, L.mnrf_train_planes2_bytes(B)), dtype=torch.uint8, device=dev)
@@ -263,7 +258,7 @@ class FieldFn(torch.autograd.Function):
                 p(packed), B, p(xyz), xs, p(rays), p(z_vals), spr, p(g_normal.contiguous().float()), p(normal),
                 p(save_invj), p(save_mask), p(x2), p(y2), p(jmax), p(d_xyz), p(ctx.n_live), _lib.stream()), "mnrf_field_backward2_planes")
             st.tape.append((x2, y2, B, jmax, 1, ctx.n_live, spr))
-        elif B and g_normal is not None and normal is not None:   # rows route (fp32 arithmetic, MNRF_DW2_PLANES=0)
+        elif B and g_normal is not None and normal is not None:   # rows route (fp32 arithmetic)
             if not st.dirty:         # it ADDS to the gradients (trunk weights, sigma.weight): they start from zero then
                 st.flat.zero_()
                 st.dirty = True
@@ -301,7 +296,7 @@ class FieldFn(torch.autograd.Function):
             if xyz is not None:
                 g_xyz = torch.zeros_like(xyz)
                 g_xyz[:, :3] = d_xyz
-            elif rays.shape[1] == 8 and RAY_GRADS_KERNEL:   # x = o + d*z  (rendering.py:302): dL/do = sum_s dL/dx, dL/dd = sum_s z dL/dx -- one kernel,
+            elif rays.shape[1] == 8:   # x = o + d*z  (rendering.py:302): dL/do = sum_s dL/dx, dL/dd = sum_s z dL/dx -- one kernel,
                 g_rays = torch.empty_like(rays)      # together with the per-ray sum of the view-encoding gradient
                 if d_dir is not None:
                     g_de = f(rays.shape[0], 27)
@@ -314,7 +309,7 @@ class FieldFn(torch.autograd.Function):
                 g_rays[:, 0:3] = dx.sum(1)
                 g_rays[:, 3:6] = (dx * z_vals.view(N, spr, 1)).sum(1)
         if d_dir is not None and g_de is None:
-            if rays is not None and xyz is None and B and RAY_GRADS_KERNEL:
+            if rays is not None and xyz is None and B:
                 g_de = f(rays.shape[0], 27)
                 _lib.check(L.mnrf_ray_grads_n(None, None, p(d_dir), rays.shape[0], spr, None, p(g_de), p(ctx.n_live), _lib.stream()),
                            "mnrf_ray_grads")

@@ -4,16 +4,14 @@
 // [samples][N] and the training forward leaves its input X [samples][K], both row-major in HBM
 // (288 GB of HBM3E make keeping ~22 KB per sample affordable; recomputing them would cost another
 // forward).  dW[n][k] = sum_s dY[s][n] X[s][k] is a GEMM whose contraction runs over samples:
-//   * dw_gemm_kernel: 128 x TK output tile per workgroup, v_mfma_f32_16x16x4_f32 with the sample
-//     axis as the MFMA k axis (A operand = 4 rows x 16 columns of dY, B operand = 4 rows x 16
-//     columns of X, straight out of padded LDS tiles, bank-conflict free), split over the sample
-//     range; bias gradients (column sums of dY) fall out of the A operands already in registers;
+//   * dw_gemm_bf16_kernel (64- and 32-wide tiles) / dw_gemm_bf16p_kernel (128-wide tiles): 128 x TK output tile per
+//     workgroup on the bf16 matrix pipe at fp32 accuracy, split over the sample range; bias gradients (column sums of
+//     dY) ride along;
 //   * dw_small_kernel: the 1- and 3-row Linears (sigma, rgb, normal_net.1, is_mirror_net.2);
 //   * dw_finish_kernel: sums the split partials and writes gradients in nn.Linear (out,in) layout.
 // Autograd equivalent: the .grad accumulation of loss.backward() for models/mirror_nerf.py:59-99.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "../../include/mnrf.h"
@@ -26,92 +24,9 @@ namespace mnrf {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DW_TN = 128;
-constexpr int DW_CH = 32;          // samples per LDS stage
-constexpr int DW_PAD = 16;         // row stride = width + 16 floats: lanes of rows r and r+1 hit different bank halves
-
-template <int TK>
-__global__ __launch_bounds__(256) void dw_gemm_kernel(const float* __restrict__ A, int lda, const float* __restrict__ X, int ldx,
-                                                      long long B, int splits, int N, int K, float* __restrict__ Cpart,
-                                                      float* __restrict__ bpart) {
-    constexpr int LDA = DW_TN + DW_PAD;
-    constexpr int LDX = TK + DW_PAD;
-    __shared__ float As[DW_CH * LDA];
-    __shared__ float Xs[DW_CH * LDX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int wn = wave >> 1, wk = wave & 1;
-    constexpr int MB = 4;              // 64 rows of dW per wave
-    constexpr int KB = TK / 32;        // TK/2 columns per wave
-    const int n0 = blockIdx.x * DW_TN, k0 = blockIdx.y * TK, split = blockIdx.z;
-    const long long per = (B + splits - 1) / splits;
-    const long long s_begin = split * per;
-    const long long s_end = s_begin + per < B ? s_begin + per : B;
-
-    f32x4 acc[MB][KB];
-#pragma unroll
-    for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < KB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bsum[MB] = {0.f, 0.f, 0.f, 0.f};
-
-    for (long long s0 = s_begin; s0 < s_end; s0 += DW_CH) {
-        __syncthreads();
-        // stage DW_CH rows of dY (128 columns) and X (TK columns); rows past the range are zero
-        for (int v = tid; v < DW_CH * (DW_TN / 4); v += 256) {
-            const int r = v / (DW_TN / 4), c4 = v % (DW_TN / 4);
-            f32x4 val = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (s0 + r < s_end) val = *(const f32x4*)(A + (s0 + r) * lda + n0 + c4 * 4);
-            *(f32x4*)(As + r * LDA + c4 * 4) = val;
-        }
-        for (int v = tid; v < DW_CH * (TK / 4); v += 256) {
-            const int r = v / (TK / 4), c4 = v % (TK / 4);
-            f32x4 val = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (s0 + r < s_end) val = *(const f32x4*)(X + (s0 + r) * ldx + k0 + c4 * 4);
-            *(f32x4*)(Xs + r * LDX + c4 * 4) = val;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < DW_CH / 4; ++ks) {
-            float a[MB], b[KB];
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) a[mb] = As[(ks * 4 + g) * LDA + wn * 64 + mb * 16 + i];
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) b[kb] = Xs[(ks * 4 + g) * LDX + wk * (TK / 2) + kb * 16 + i];
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) {
-                bsum[mb] += a[mb];
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb)
-                    acc[mb][kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb], b[kb], acc[mb][kb], 0, 0, 0);
-            }
-        }
-    }
-    // partial tile: C[n = 4g + r][k = i] of every 16x16 block
-    float* C = Cpart + (long long)split * N * K;
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + wn * 64 + mb * 16 + 4 * g + r;
-                const int k = k0 + wk * (TK / 2) + kb * 16 + i;
-                C[(long long)n * K + k] = acc[mb][kb][r];
-            }
-    if (bpart && blockIdx.y == 0 && wk == 0) {
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-            float v = bsum[mb];
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
-            if (g == 0) bpart[(long long)split * N + n0 + wn * 64 + mb * 16 + i] = v;
-        }
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------------------
-// The same GEMM on the bf16 matrix pipe at fp32 accuracy.  A fp32 number is EXACTLY the sum of three bf16 numbers
+// The GEMM on the bf16 matrix pipe at fp32 accuracy.  A fp32 number is EXACTLY the sum of three bf16 numbers
 // obtained by truncation (8 + 8 + 8 significand bits, fp32's exponent range -- gradients of 1e-10 are as safe as
 // activations of 100, which is why this kernel does not use the f16 split of the field kernel):
 //     v = hi + mid + lo,   hi = trunc16(v), mid = trunc16(v - hi), lo = trunc16(v - hi - mid)   (both subtractions exact)
@@ -285,9 +200,9 @@ __global__ __launch_bounds__(256) void dw_gemm_bf16_kernel(DwJobs J, long long B
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Pipelined version of dw_gemm_bf16_kernel<128> (round 2).  The kernel above runs in phases -- wait for the stage's rows,
-// convert and store them, barrier, MFMAs, barrier -- and leans on a second resident workgroup to fill the matrix pipe
-// while one converts.  Here ONE workgroup of EIGHT waves per CU owns two LDS buffers and four register sets, and every
+// Pipelined version of dw_gemm_bf16_kernel for the 128-wide tiles (round 2).  The kernel above runs in phases -- wait for
+// the stage's rows, convert and store them, barrier, MFMAs, barrier -- and leans on a second resident workgroup to fill the
+// matrix pipe while one converts.  Here ONE workgroup of EIGHT waves per CU owns two LDS buffers and four register sets, and every
 // wave overlaps the three activities itself:
 //   stage i:  global loads of stage i+4 -> register set i % 4            (three stages of load latency hidden)
 //             MFMAs on LDS buffer i % 2, and BETWEEN them the conversion of stage i+1 (register set (i+1) % 4) into
@@ -297,7 +212,9 @@ __global__ __launch_bounds__(256) void dw_gemm_bf16_kernel(DwJobs J, long long B
 // a time (measured with 4 waves: 2400 cycles per stage with the MFMAs compiled out, whatever the prefetch depth).
 // Sample ranges of the splits are multiples of 32; the one partial stage of a launch is done behind the pipeline.
 // OUTCOME (profiles/r02i_dw_ab.txt): the largest launch of a 1024-ray step takes 1.23 ms against 1.12 ms of the phased
-// kernel, the step 7.96 vs 7.73 ms -- no gain, so the phased kernel stays the default (MNRF_DW_PIPE=1 selects this one).
+// kernel, the step 7.96 vs 7.73 ms -- no gain then.  Since round 4 it takes every 128-wide tile: what is left on this route
+// is the second-order pass of TotalLoss (the first-order GEMMs run from operand planes, mnrf_dwp.hip), and there it measured
+// 8.26-8.40 against 8.35-8.87 ms per step of the phased kernel in alternating runs (half the HBM traffic).
 // What the exercise established: both kernels sit at ~2500-2800 cycles per 32-sample stage against 1536 cycles of MFMA
 // time because the fp32 -> 3 x bf16 conversion (5.5 VALU per element, 832 VALU cycles per SIMD and stage) plus the
 // MFMA issue slots fill the vector issue port to ~80 %; the XCD-aware tile placement halves the L2 misses (5.2 GB per
@@ -318,7 +235,6 @@ __device__ __forceinline__ void stage_col(char* plane0, int plane_bytes, int col
     *(unsigned*)(w + 2 * plane_bytes) = (l0 >> 16) | l1;
 }
 
-template <bool HINT>
 __global__ __launch_bounds__(64 * DWP_WAVES, 1) void dw_gemm_bf16p_kernel(DwJobs J, long long B, int splits, int njobs) {
     constexpr int TK = DWP_TK;
     // Workgroup -> (job, split, tile).  The up-to-four tiles of one (job, split) read the same 32 rows of dY and X per
@@ -430,14 +346,12 @@ __global__ __launch_bounds__(64 * DWP_WAVES, 1) void dw_gemm_bf16p_kernel(DwJobs
 #pragma unroll
                 for (int t = 0; t < NTASK / MB; ++t) task(R, nxt, mb * (NTASK / MB) + t, bw);
             }
-            if (HINT) {
-                // one MFMA, then the conversion instructions that fit its shadow; 6 * KB MFMAs per row block
+            // one MFMA, then the conversion instructions that fit its shadow; 6 * KB MFMAs per row block
 #pragma unroll
-                for (int m = 0; m < 6 * KB; ++m) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-                    if (m % 2 == 0) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                }
+            for (int m = 0; m < 6 * KB; ++m) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+                if (m % 2 == 0) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
             }
         }
     };
@@ -601,17 +515,9 @@ __global__ void dw_finish_kernel(DwFinishArgs F) {
 
 namespace mnrf {
 
-// MNRF_DW=fp32 selects the v_mfma_f32_16x16x4_f32 kernel (bit-for-bit fp32 fmaf chains, one launch per GEMM); default:
-// bf16 x 6, batched per TK
-static bool dw_fp32() {
-    static const bool v = [] { const char* e = getenv("MNRF_DW"); return e && e[0] == 'f'; }();
-    return v;
-}
-
 // Split counts: enough workgroups to fill 256 CUs even for a 1024-ray training batch.
-int dw_splits(long long B) {          // MFMA GEMMs, batched launches: >= 512 samples per workgroup, <= 64 splits: 11.4 ms/step (48: 11.9, 32: 11.7, 96 x 256: 11.6; un-batched fp32 path: 256 / 256)
-    static const int cap = [] { const char* e = getenv("MNRF_DW_SPLITS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 512 ? v : (dw_fp32() ? 256 : 64); }();
-    static const int per = [] { const char* e = getenv("MNRF_DW_PER"); const int v = e ? atoi(e) : 0; return v >= 32 ? v : (dw_fp32() ? 256 : 512); }();
+int dw_splits(long long B) {          // batched launches: >= 512 samples per workgroup, <= 64 splits: 11.4 ms/step (48: 11.9, 32: 11.7, 96 x 256: 11.6)
+    constexpr int cap = 64, per = 512;
     long long s = (B + per - 1) / per;
     return (int)(s < 1 ? 1 : (s > cap ? cap : s));
 }
@@ -643,31 +549,13 @@ long long dw_workspace_floats(long long B) {
     return (long long)dw_splits(B) * DW_PER_SPLIT + (long long)dw_small_splits(B) * DW_PER_SMALL_SPLIT;
 }
 
-// MNRF_DW_PIPE: 1 (default since round 4) = pipelined kernel for the 128-wide tiles, 0 = the phased kernels everywhere.  Round 2
-// measured the two equal on the first-order GEMMs; those run from operand planes now (mnrf_dwp.hip), what is left on this route
-// is the second-order pass of TotalLoss, and there the pipelined kernel measured 8.26-8.40 against 8.35-8.87 ms per step in
-// alternating runs (half the HBM traffic: see the kernel's header);
-// MNRF_DW_HINT=0 drops the scheduling-group hints of the pipelined kernel
-static int dw_pipe() {
-    static const int v = [] { const char* e = getenv("MNRF_DW_PIPE"); return e ? atoi(e) : 1; }();
-    return v;
-}
-static bool dw_hint() {
-    static const bool v = [] { const char* e = getenv("MNRF_DW_HINT"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 struct DwBatch {
     DwJobs j128, j64, j32;
     int n128 = 0, n64 = 0, n32 = 0;
     long long B;
-    int splits;          // of the phased kernels (and of the fp32 path)
-    int splits_p;        // of the pipelined kernels
+    int splits;          // of the phased kernels
+    int splits_p;        // of the pipelined kernel
     hipStream_t s;
-    template <int TK>
-    static bool pipelined() { return !dw_fp32() && TK == DWP_TK && dw_pipe() >= 1; }
-    template <int TK>
-    int splits_of() const { return pipelined<TK>() ? splits_p : splits; }
     template <int TK>
     void launch(const DwJobs& J, int n) {
         if (n) hipLaunchKernelGGL((dw_gemm_bf16_kernel<TK>), dim3(4, splits, n), dim3(256), 3 * (DW_TN + TK) * DWS_STRIDE, s, J, B, splits);
@@ -676,18 +564,15 @@ struct DwBatch {
         if (!n) return;
         constexpr int lds = 2 * 3 * (DW_TN + DWP_TK) * DWS_STRIDE;
         static const bool once = [] {
-            (void)hipFuncSetAttribute((const void*)dw_gemm_bf16p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)dw_gemm_bf16p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute((const void*)dw_gemm_bf16p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             return true;
         }();
         (void)once;
         const int grid = 32 * ((splits_p * n + 7) / 8);      // 8 XCDs x 4 tiles per group of 8 (job, split) pairs
-        if (dw_hint()) hipLaunchKernelGGL((dw_gemm_bf16p_kernel<true>), dim3(grid), dim3(64 * DWP_WAVES), lds, s, J, B, splits_p, n);
-        else hipLaunchKernelGGL((dw_gemm_bf16p_kernel<false>), dim3(grid), dim3(64 * DWP_WAVES), lds, s, J, B, splits_p, n);
+        hipLaunchKernelGGL(dw_gemm_bf16p_kernel, dim3(grid), dim3(64 * DWP_WAVES), lds, s, J, B, splits_p, n);
     }
     void flush() {
-        if (pipelined<128>()) launch_pipelined(j128, n128);
-        else launch<128>(j128, n128);
+        launch_pipelined(j128, n128);
         launch<64>(j64, n64);
         launch<32>(j32, n32);
         n128 = n64 = n32 = 0;
@@ -696,11 +581,6 @@ struct DwBatch {
 
 template <int TK>
 static void gemm(DwBatch& bt, const float* A, int lda, int N, const float* X, int ldx, int K, float* C, float* bp) {
-    if (dw_fp32()) {
-        dim3 grid(N / DW_TN, K / TK, bt.splits);
-        hipLaunchKernelGGL((dw_gemm_kernel<TK>), grid, dim3(256), 0, bt.s, A, lda, X, ldx, bt.B, bt.splits, N, K, C, bp);
-        return;
-    }
     const DwJob jb{A, X, C, bp, lda, ldx, N, K};
     if (TK == 128) bt.j128.job[bt.n128++] = jb;
     else if (TK == 64) bt.j64.job[bt.n64++] = jb;
@@ -714,7 +594,7 @@ int launch_dw(const float* save_x, const float* dY, const float* g_sigma, long l
     DwBatch bt;
     bt.B = B; bt.splits = splits; bt.s = s;
     bt.splits_p = dw_splits_rounds(B, 8 * 4 + 3 * 2);      // 8 GEMMs of four 128 x 128 tiles, 3 of two
-    const int s128 = bt.splits_of<128>(), s64 = bt.splits_of<64>();
+    const int s128 = bt.splits_p, s64 = splits;
     float* p = ws;
     auto take = [&](long long n) { float* r = p; p += n * splits; return r; };      // sized for the larger split count
     auto take_small = [&](long long n) { float* r = p; p += n * ssplits; return r; };
@@ -813,7 +693,7 @@ int launch_dw2(const float* so, long long B, float* ws, float* const* d_params, 
     DwBatch bt;
     bt.B = B; bt.splits = splits; bt.s = s;
     bt.splits_p = dw_splits_rounds(B, 7 * 4);
-    const int s128 = bt.splits_of<128>(), s64 = bt.splits_of<64>();
+    const int s128 = bt.splits_p, s64 = splits;
     float* p = ws;
     auto take = [&](long long n) { float* r = p; p += n * splits; return r; };
     auto sec = [&](int off) { return so + (long long)off * B; };

@@ -3,7 +3,7 @@
 //   dwp_gemm_kernel    persistent workgroups (one per CU, 8 waves): each owns a contiguous span of the cost line of
 //                      mnrf_dwp.h, i.e. consecutive 32-sample stages of one or a few (job, evaluation) pairs; per stage the
 //                      operand tiles of the job (up to 32 KiB of dY + 32 KiB of X, hi and lo planes) travel HBM -> LDS by
-//                      LDS-DMA into a double buffer, MFMA operands come out of LDS through ds_read_b64_tr_b16, three
+//                      LDS-DMA into a ring of half-stages, MFMA operands come out of LDS through ds_read_b64_tr_b16, three
 //                      v_mfma_f32_16x16x32_f16 per 16 x 16 x 32 block (hi.hi + hi.lo + lo.hi) into a 256 x 256 fp32 tile
 //                      held in registers (wave (wn, wk): rows 64 wn .., columns 128 wk ..); one partial tile per span piece.
 //   dwp_finish_kernel  sums the partial tiles of every Linear over workgroups and evaluations (each evaluation with its own
@@ -12,7 +12,6 @@
 // Autograd equivalent: the .grad accumulation of loss.backward() for models/mirror_nerf.py:59-99.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
@@ -30,10 +29,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 extern __shared__ __attribute__((aligned(16))) char dwp_smem[];
-
-constexpr int DWP_BUF = 64 * 1024;         // one stage: [A tiles: 32 KiB][X tiles: 32 KiB]
-constexpr int DWP_XOFF = 32 * 1024;
-constexpr int DWP_LDS = 2 * DWP_BUF;
 
 struct DwpEval {
     const char* X;            // X planes of the evaluation  [n_sb][PLX_FB][2][1 KiB]
@@ -53,117 +48,15 @@ __device__ __forceinline__ f32x4 mfma_h(const u32x4& a, const u32x4& b, const f3
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
 }
 
-// one MFMA operand = feature (lane & 15) of a tile, k slots 8 gg .. 8 gg + 7 = rows {4 gg .. 4 gg + 3} and {16 + 4 gg ..}:
-// two transposing reads with lane-linear addresses (tile + 8 lane, tile + 512 + 8 lane)
-__device__ __forceinline__ u32x4 read_operand(const char* tile, int lane8) {
-    typedef __attribute__((address_space(3))) h4 lds_h4;
-    const h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4*)(tile + lane8));
-    const h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4*)(tile + 512 + lane8));
-    const u32x2 l = __builtin_bit_cast(u32x2, lo), h = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l.x, l.y, h.x, h.y};
-}
-
-// tile t (1 KiB, lane-linear) of a contiguous run of tiles: global -> LDS by LDS-DMA
-__device__ __forceinline__ void dma_tile(const char* src, char* dst, int lane16) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane16),
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, PL_LOAD_AUX);
-}
-
-// MB: dY blocks per wave row (wn), KB: X blocks per wave column (wk); NA / NX: blocks of the job's operands
-template <int MB, int KB, int NA, int NX>
-__device__ __forceinline__ void dwp_segment_run(const char* __restrict__ Yb, const char* __restrict__ Xb, long long ysb, long long xsb,
-                                                int s_lo, int s_hi, bool bias, float* __restrict__ slot) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 3, wk = wave >> 2;
-    const int lane8 = lane * 8, lane16 = lane * 16;
-    const bool has_a = wn * MB < NA;         // NA = 1: only wn = 0 owns a row block
-    constexpr int NT = 2 * NA + 2 * NX;      // 1-KiB tiles per stage
-    char* const lds = dwp_smem;
-
-    f32x4 acc[MB][KB], bacc[MB];
-#pragma unroll
-    for (int a = 0; a < MB; ++a) {
-        bacc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int b = 0; b < KB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const u32x4 ones = u32x4{0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};      // f16 1.0 in every k slot
-
-    // the wave's share of a stage's tiles: t = wave, wave + 8, ...  (A tiles first, then X tiles at DWP_XOFF)
-    auto issue = [&](int s, int buf) {
-        const char* ya = Yb + (long long)s * ysb;
-        const char* xa = Xb + (long long)s * xsb;
-        char* base = lds + buf * DWP_BUF;
-#pragma unroll
-        for (int q = 0; q < (NT + 7) / 8; ++q) {
-            const int t = wave + 8 * q;
-            if (t < 2 * NA) dma_tile(ya + t * PL_TILE_BYTES, base + t * PL_TILE_BYTES, lane16);
-            else if (t < NT) dma_tile(xa + (t - 2 * NA) * PL_TILE_BYTES, base + DWP_XOFF + (t - 2 * NA) * PL_TILE_BYTES, lane16);
-        }
-    };
-
-    __syncthreads();                 // the previous segment's last stage has been read by every wave
-    issue(s_lo, 0);
-    for (int s = s_lo; s < s_hi; ++s) {
-        const int buf = (s - s_lo) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's tiles of stage s have landed ...
-        __syncthreads();                                      // ... and everybody's; buffer buf ^ 1 is free (stage s - 1 consumed)
-        if (s + 1 < s_hi) issue(s + 1, buf ^ 1);
-        const char* A = lds + buf * DWP_BUF;
-        const char* X = A + DWP_XOFF;
-        if (has_a) {
-            u32x4 ah[MB], al[MB];
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) {
-                ah[mb] = read_operand(A + (wn * MB + mb) * PL_FB_BYTES, lane8);
-                al[mb] = read_operand(A + (wn * MB + mb) * PL_FB_BYTES + PL_TILE_BYTES, lane8);
-            }
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                const u32x4 bh = read_operand(X + (wk * KB + kb) * PL_FB_BYTES, lane8);
-                const u32x4 bl = read_operand(X + (wk * KB + kb) * PL_FB_BYTES + PL_TILE_BYTES, lane8);
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) {
-                    f32x4 c = acc[mb][kb];
-                    c = mfma_h(al[mb], bh, c);      // lo . hi
-                    c = mfma_h(ah[mb], bl, c);      // hi . lo
-                    c = mfma_h(ah[mb], bh, c);      // hi . hi
-                    acc[mb][kb] = c;
-                }
-            }
-            if (bias && wk == 0) {                  // column sums of dY: the same operands against a row of ones
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) {
-                    bacc[mb] = mfma_h(al[mb], ones, bacc[mb]);
-                    bacc[mb] = mfma_h(ah[mb], ones, bacc[mb]);
-                }
-            }
-        }
-    }
-    // partial tile, fragment order: block (nb, kb) = 1 KiB, lane-linear float4 (row 4 g + r, column lane & 15 of the block)
-    if (has_a) {
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb)
-                ((f32x4*)slot)[((wn * MB + mb) * NX + (wk * KB + kb)) * 64 + lane] = acc[mb][kb];
-        if (bias && wk == 0 && (lane & 15) == 0) {
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) ((f32x4*)(slot + 256 * 256))[(wn * MB + mb) * 4 + (lane >> 4)] = bacc[mb];
-        }
-    }
-}
-
-// ---- the same segment through a RING of half-stages (round 4; the default).  What capped the two-buffer version above was not
-// the memory system: a streaming reader with the same instruction gets 6.06 TB/s (default policy) / 6.87 TB/s (nt) out of these
-// buffers (mnrf_bench_stream, scripts/bw_probe.py) where that loop got 4.5 -- and 4.67 with its LDS reads and MFMAs compiled out.
-// It refills a whole stage at a time: nothing new is requested until the LAST byte of a stage has landed and every wave has
-// passed the barrier, so the bytes in flight swing between 0 and one stage (64 KiB for the big jobs, 18 KiB for the small ones)
-// and the memory pipe of the CU runs dry once per stage.  Here a stage travels as two HALF-STAGES (rows 0-15 / 16-31 of every
+// ---- a segment of one job: its stages travel through a RING of half-stages (round 4).  What capped round 3's loop over two
+// whole-stage buffers was not the memory system: a streaming reader with the same instruction got 6.06 TB/s (default policy) /
+// 6.87 TB/s (nt) out of these buffers where that loop got 4.5 -- and 4.67 with its LDS reads and MFMAs compiled out.  It refilled
+// a whole stage at a time: nothing new was requested until the LAST byte of a stage had landed and every wave had passed the
+// barrier, so the bytes in flight swung between 0 and one stage (64 KiB for the big jobs, 18 KiB for the small ones) and the
+// memory pipe of the CU ran dry once per stage.  Here a stage travels as two HALF-STAGES (rows 0-15 / 16-31 of every
 // tile: one LDS-DMA instruction brings the hi and the lo half-tile of a feature block, lanes 0-31 / 32-63, two 512-byte runs in
 // memory, 1 KiB lane-linear in LDS) through a ring of D slots of NP KiB; the stage being multiplied occupies two slots (its two
-// halves are read by ONE transposing operand read each and multiplied with the K = 32 MFMA, as above -- a first build of this
+// halves are read by ONE transposing operand read each and multiplied with the K = 32 MFMA -- a first build of this
 // ring multiplied half-stages with the K = 16 MFMA, which runs at half the rate and then bound the loop), D - 2 half-stages are
 // on their way, and two more are requested as soon as a stage has been consumed: the bytes in flight swing between D - 4 and
 // D - 2 half-stages.  D = 5 for the 16 x 16-block jobs (160 KiB of LDS), up to 12 for the small ones.  Every wave issues the
@@ -366,7 +259,7 @@ __device__ __forceinline__ int plan_word(const void* base, int byte_off) {
 }
 
 // DEV: the plan was made on the device (DwpDevPlan, live row counts); the launch has one workgroup per CU
-template <bool HALF, bool DEV = false>
+template <bool DEV = false>
 __global__ __launch_bounds__(DWP_WG_THREADS, 1) void dwp_gemm_kernel(DwpArgs A) {
     const int g = blockIdx.x;
     DwpPlan hd;      // n_eval, G, T: what the interval needs (the per-evaluation entries are read where they are used)
@@ -396,24 +289,13 @@ __global__ __launch_bounds__(DWP_WG_THREADS, 1) void dwp_gemm_kernel(DwpArgs A) 
             const char* Xb = A.ev[e].X + (long long)jb.xa * PL_FB_BYTES;
             float* slot = A.part + (long long)(g + j * hd.n_eval + e) * DWP_SLOT_FLOATS;
             const bool y_half = kind == 0 && A.ev[e].y_half != 0;      // (the second-order planes stay hi / lo)
-            if constexpr (HALF) {
-                switch (jb.shape) {
-                case 0: dwp_segment_run_h<4, 8, 16, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                case 1: dwp_segment_run_h<4, 2, 16, 4>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                case 2: dwp_segment_run_h<2, 8, 8, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                case 3: dwp_segment_run_h<2, 1, 8, 2>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                case 4: dwp_segment_run_h<1, 8, 1, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                default: dwp_segment_run_h<1, 4, 1, 8>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
-                }
-            } else {
-                switch (jb.shape) {
-                case 0: dwp_segment_run<4, 8, 16, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                case 1: dwp_segment_run<4, 2, 16, 4>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                case 2: dwp_segment_run<2, 8, 8, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                case 3: dwp_segment_run<2, 1, 8, 2>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                case 4: dwp_segment_run<1, 8, 1, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                default: dwp_segment_run<1, 4, 1, 8>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot); break;
-                }
+            switch (jb.shape) {
+            case 0: dwp_segment_run_h<4, 8, 16, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
+            case 1: dwp_segment_run_h<4, 2, 16, 4>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
+            case 2: dwp_segment_run_h<2, 8, 8, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
+            case 3: dwp_segment_run_h<2, 1, 8, 2>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
+            case 4: dwp_segment_run_h<1, 8, 1, 16>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
+            default: dwp_segment_run_h<1, 4, 1, 8>(Yb, Xb, ysb, xsb, s_lo, s_hi, jb.bias, slot, y_half); break;
             }
         }
     }
@@ -487,7 +369,7 @@ __global__ void dwp_finish_kernel(DwpFinishArgs F) {
     }
     if (job < 0) return;
     const DwpJob jb = dwp_job(job);
-    // position inside a partial slot (fragment order of dwp_segment_run): float4 = rows 4 (row >> 2) .. + 3 of column col
+    // position inside a partial slot (fragment order of dwp_segment_run_h): float4 = rows 4 (row >> 2) .. + 3 of column col
     long long idx;
     if (!is_bias) idx = ((long long)((row >> 4) * jb.nx + (col >> 4)) * 64 + ((row & 15) >> 2) * 16 + (col & 15)) * 4;
     else idx = 256 * 256 + row;
@@ -641,8 +523,6 @@ void launch_jhat_max(const float* g_normal, const float* normal, const float* sa
 // ---------------------------------------------------------------------------------------------------------- driver
 static int dwp_cus() {
     static const int v = [] {
-        const char* e = getenv("MNRF_DWP_G");
-        if (e && atoi(e) > 0) return atoi(e);
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
@@ -729,32 +609,19 @@ static int dwp_run(const DwpPlan& plan, const DwpDevPlan* dev, int n_eval, const
     DwpArgs A;
     A.plan = plan;
     A.dev = dev;
-    bool any_half = false;
-    for (int e = 0; e < n_eval; ++e) {
+    for (int e = 0; e < n_eval; ++e)
         A.ev[e] = DwpEval{(const char*)x_planes[e], (const char*)dy_planes[e], seedmax[e], (kinds && (kinds[e] & 0x1000)) ? 1 : 0};
-        any_half |= A.ev[e].y_half != 0;
-    }
     for (int e = n_eval; e < DWP_MAX_EVAL; ++e) A.ev[e] = DwpEval{nullptr, nullptr, nullptr, 0};
     A.part = part;
     static const bool once = [] {
-        (void)hipFuncSetAttribute((const void*)dwp_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DWP_LDS);
+        (void)hipFuncSetAttribute((const void*)dwp_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DWP_RING_LDS);
         (void)hipFuncSetAttribute((const void*)dwp_gemm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DWP_RING_LDS);
-        (void)hipFuncSetAttribute((const void*)dwp_gemm_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DWP_LDS);
-        (void)hipFuncSetAttribute((const void*)dwp_gemm_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DWP_RING_LDS);
         return true;
     }();
     (void)once;
-    // the ring of half-stages (dwp_segment_run_h) is the default; MNRF_DWP_RING=0 (read once) selects the two-buffer version
-    static const bool ring = [] { const char* e = getenv("MNRF_DWP_RING"); return !(e && atoi(e) == 0); }();
-    if (any_half && !ring) return -2;      // (the two-buffer loop fetches whole stages)
     const int G = dev ? dwp_cus() : plan.G;
-    if (dev) {
-        if (ring) hipLaunchKernelGGL((dwp_gemm_kernel<true, true>), dim3(G), dim3(DWP_WG_THREADS), DWP_RING_LDS, s, A);
-        else hipLaunchKernelGGL((dwp_gemm_kernel<false, true>), dim3(G), dim3(DWP_WG_THREADS), DWP_LDS, s, A);
-    } else {
-        if (ring) hipLaunchKernelGGL(dwp_gemm_kernel<true>, dim3(G), dim3(DWP_WG_THREADS), DWP_RING_LDS, s, A);
-        else hipLaunchKernelGGL(dwp_gemm_kernel<false>, dim3(G), dim3(DWP_WG_THREADS), DWP_LDS, s, A);
-    }
+    if (dev) hipLaunchKernelGGL(dwp_gemm_kernel<true>, dim3(G), dim3(DWP_WG_THREADS), DWP_RING_LDS, s, A);
+    else hipLaunchKernelGGL(dwp_gemm_kernel<false>, dim3(G), dim3(DWP_WG_THREADS), DWP_RING_LDS, s, A);
 
     DwpFinishArgs F;
     F.part = part;
@@ -842,116 +709,3 @@ int launch_dwp_n(int n_eval, const void* const* x_planes, const void* const* dy_
 }
 
 }  // namespace mnrf
-
-// ---------------------------------------------------------------------------------------------------------- streaming-read probe
-// What does the memory system deliver to the instruction dwp_gemm_kernel streams with?  One persistent 8-wave workgroup per CU
-// reads its contiguous share of `buf` with global_load_lds_dwordx4 (1 KiB per wave-instruction, lane-linear), `depth`
-// instructions in flight per wave, into a ring it never reads; aux = 0 (default policy) or 2 (nt).  scripts/bw_probe.py prints
-// the rate next to the GEMM's (MI355X_MICROARCH.md quotes 6.4 TB/s default / 6.5-6.8 nt for this instruction chip-wide).
-namespace mnrf {
-template <int AUX, int DEPTH>
-__global__ __launch_bounds__(512, 1) void stream_probe_kernel(const char* __restrict__ buf, long long share) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const char* src = buf + (long long)blockIdx.x * share + wave * 1024 + lane * 16;
-    char* dst = dwp_smem + wave * (DEPTH * 1024);
-    const int n = (int)(share / 8192);
-    for (int k = 0; k < n; ++k) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (long long)k * 8192),
-                                         (__attribute__((address_space(3))) void*)(dst + (k % DEPTH) * 1024), 16, 0, AUX);
-        if (k >= DEPTH - 1) {
-            if constexpr (DEPTH == 8) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-}  // namespace mnrf
-
-namespace mnrf {
-// The same reader with the GEMM's ADDRESS PATTERN: a workgroup walks consecutive 32-sample stages and takes chunk_a bytes at
-// a + s * stride_a and chunk_x bytes at x + s * stride_x per stage (chunks of 1 KiB pieces dealt to the 8 waves), 16 pieces in
-// flight per wave, optionally with the GEMM's raw barrier per stage.  Separates "strided chunks instead of one contiguous run" and
-// "eight waves in lock step" from everything else that distinguishes dwp_gemm_kernel from the contiguous probe above.
-// HALVES: the GEMM ring's lane pattern -- a stage travels as two half-stages, an instruction takes rows 0-15 (or 16-31) of the hi
-// tile (lanes 0-31) and of the lo tile (lanes 32-63) of a feature block: two 512-byte runs instead of 1 KiB contiguous
-// BULK (1: the GEMM ring with D = 5, 2: a deeper one): the wave does not wait instruction by instruction for its oldest request but,
-// once per stage, until all but 4 (12) of its requests have landed -- the stage is complete -- then the barrier, then the next
-// stage's 8 requests in one burst
-template <bool BARRIER, bool HALVES, int BULK = 0>
-__global__ __launch_bounds__(512, 1) void stream_probe2_kernel(const char* __restrict__ a, const char* __restrict__ x, int n_stages,
-                                                               long long stride_a, long long stride_x, int pieces_a, int pieces_x,
-                                                               int windows) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // `windows` jobs, job-major like the GEMM's cost line: job w reads the w-th chunk-sized window of every stage's stride
-    const long long units = (long long)windows * n_stages;
-    const long long u0 = blockIdx.x * units / gridDim.x, u1 = (blockIdx.x + 1) * units / gridDim.x;
-    char* dst = dwp_smem + wave * (16 * 1024);
-    const int per_wave = (pieces_a + pieces_x + 7) / 8;      // pieces per wave and stage (a wave past the end re-loads piece 0)
-    int k = 0;
-    for (long long u = u0; u < u1; ++u) {
-        const int w = (int)(u / n_stages), s = (int)(u - (long long)w * n_stages);
-        const int lsrc = HALVES ? (lane >> 5) * 1024 + (lane & 31) * 16 : lane * 16;
-        const char* pa = a + (long long)s * stride_a + (long long)w * pieces_a * 1024 + lsrc;
-        const char* px = x + (long long)s * stride_x + (long long)w * pieces_x * 1024 + lsrc;
-        for (int q = 0; q < per_wave; ++q, ++k) {
-            int pc = wave + 8 * q;
-            if (pc >= pieces_a + pieces_x) pc = 0;
-            const char* src = pc < pieces_a ? pa : px;
-            if (pc >= pieces_a) pc -= pieces_a;
-            // HALVES: piece pc = half h of feature block fb of the chunk (all blocks' half 0 first: a half-stage), else KiB pc
-            const int np = pc < pieces_a && src == pa ? pieces_a : pieces_x;
-            src += HALVES ? (pc % (np / 2)) * 2048 + (pc / (np / 2)) * 512 : pc * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dst + (k & 15) * 1024), 16, 0, PL_LOAD_AUX);
-            if (BULK == 0 && k >= 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-        }
-        if (BULK == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        if (BULK == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        if (BARRIER) __builtin_amdgcn_s_barrier();
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-}  // namespace mnrf
-
-extern "C" int mnrf_bench_stream2(const void* a, const void* x, int n_stages, int64_t stride_a, int64_t stride_x, int chunk_a, int chunk_x,
-                                  int windows, int barrier, void* stream) {
-    using namespace mnrf;
-    if (!a || !x || n_stages < 256 || chunk_a < 1024 || chunk_x < 0 || (chunk_a & 1023) || (chunk_x & 1023) || windows < 1 ||
-        (int64_t)windows * chunk_a > stride_a || (int64_t)windows * chunk_x > stride_x)
-        return mnrf_fail(MNRF_ERR_ARG, "mnrf_bench_stream2: chunks in whole KiB, at least 256 stages");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    hipStream_t s = (hipStream_t)stream;
-    const bool halves = (barrier & 2) != 0;
-    if (barrier & 4) hipLaunchKernelGGL((stream_probe2_kernel<true, true, 1>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                                    (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    else if (barrier & 8) hipLaunchKernelGGL((stream_probe2_kernel<true, true, 2>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                                    (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    else if ((barrier & 1) && halves) hipLaunchKernelGGL((stream_probe2_kernel<true, true>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                                    (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    else if (barrier & 1) hipLaunchKernelGGL((stream_probe2_kernel<true, false>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                                    (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    else if (halves) hipLaunchKernelGGL((stream_probe2_kernel<false, true>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                            (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    else hipLaunchKernelGGL((stream_probe2_kernel<false, false>), dim3(cus), dim3(512), 128 * 1024, s, (const char*)a, (const char*)x, n_stages,
-                            (long long)stride_a, (long long)stride_x, chunk_a / 1024, chunk_x / 1024, windows);
-    return mnrf_check_launch("mnrf_bench_stream2");
-}
-
-extern "C" int mnrf_bench_stream(const void* buf, int64_t bytes, int aux, int depth, void* stream) {
-    using namespace mnrf;
-    if (!buf || bytes < (int64_t)256 * 8192) return mnrf_fail(MNRF_ERR_ARG, "mnrf_bench_stream: buffer too small");
-    if ((aux != 0 && aux != 2) || (depth != 8 && depth != 16)) return mnrf_fail(MNRF_ERR_ARG, "mnrf_bench_stream: aux 0|2, depth 8|16");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long long share = bytes / cus / 8192 * 8192;
-    const size_t lds = (size_t)8 * depth * 1024;
-    hipStream_t s = (hipStream_t)stream;
-    if (aux == 0 && depth == 8) hipLaunchKernelGGL((stream_probe_kernel<0, 8>), dim3(cus), dim3(512), lds, s, (const char*)buf, share);
-    else if (aux == 2 && depth == 8) hipLaunchKernelGGL((stream_probe_kernel<2, 8>), dim3(cus), dim3(512), lds, s, (const char*)buf, share);
-    else if (aux == 0) hipLaunchKernelGGL((stream_probe_kernel<0, 16>), dim3(cus), dim3(512), lds, s, (const char*)buf, share);
-    else hipLaunchKernelGGL((stream_probe_kernel<2, 16>), dim3(cus), dim3(512), lds, s, (const char*)buf, share);
-    return mnrf_check_launch("mnrf_bench_stream");
-}

@@ -714,7 +714,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         }
     }
     unsigned long long* gmask = (GRAD && A.save_mask) ? A.save_mask + (long long)tile * (N_MASKS * S * WG_THREADS) : nullptr;
-    const bool keep = !PLANES && GRAD && A.save_x != nullptr;     // training forward, fp32 rows (MNRF_DW_PLANES=0; tests)
+    const bool keep = !PLANES && GRAD && A.save_x != nullptr;     // training forward, fp32 rows (no MNRF_TRAIN_PLANES: the fp32 arithmetic; tests)
     uint64_t unused_bits[S];
 
     u32x4 hh[S][8], hl[S][8];

@@ -41,15 +41,10 @@ bool split48_enabled() {
 // mnrf_pack_weights): the library allocates nothing and keeps no device state.  Every launch leaves its pair at zero again (the
 // last workgroup out resets it); consecutive launches on an image rotate through the TQ_PAIRS pairs, so up to TQ_PAIRS launches
 // that share an image may be in flight on different streams (launches on one stream are ordered anyway).
-// MNRF_TILE_QUEUE=0 (read once) keeps the static one-workgroup-per-tile grid.
 namespace {
 constexpr int TQ_DEVICES = 64;
 int g_resident[TQ_DEVICES];          // host-side cache of the CU count per device (0 = not asked yet)
 unsigned g_next_pair = 0;
-bool tile_queue_enabled() {
-    static const bool v = [] { const char* e = getenv("MNRF_TILE_QUEUE"); return !(e && atoi(e) == 0); }();
-    return v;
-}
 }  // namespace
 
 static bool tile_queue_slot(FieldArgs& A) {
@@ -72,7 +67,7 @@ static bool tile_queue_slot(FieldArgs& A) {
 int launch_split48(const FieldArgs& A0, bool sigma_only, hipStream_t s) {
     FieldArgs A = A0;
     A.tile_queue = nullptr;
-    if (tile_queue_enabled() && tile_queue_slot(A)) {
+    if (tile_queue_slot(A)) {
         // the pair is zeroed on the launch stream and not only by the last workgroup of the previous launch that used it: a kernel
         // that aborted would otherwise leave it non-zero and the next launch on that pair would skip or repeat tiles
         if (hipMemsetAsync(A.tile_queue, 0, 2 * sizeof(int), s) != hipSuccess) A.tile_queue = nullptr;

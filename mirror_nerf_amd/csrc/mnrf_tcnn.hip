@@ -15,7 +15,6 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
@@ -1818,8 +1817,7 @@ static int tcnn_forward_impl(const float* table, const int64_t* offsets17_host, 
     A.enc = enc_workspace;
     A.table_f16 = (flags & MNRF_TCNN_TABLE_F16) ? 1u : 0u;
     hipStream_t s = (hipStream_t)stream;
-    // MLPs on the matrix pipe (default); MNRF_TCNN_VALU=1 selects the one-thread-per-sample VALU kernel (A/B measurements)
-    static const bool env_valu = [] { const char* e = getenv("MNRF_TCNN_VALU"); return e && e[0] == '1'; }();
+    // MLPs on the matrix pipe (default); the flag MNRF_TCNN_VALU selects the one-thread-per-sample VALU kernel
     bool any_modulo = false;
     for (int l = 0; l < NL; ++l) any_modulo |= A.mode[l] == 2u;
     // The matrix-pipe kernel takes the full evaluations without the density-gradient normal (see its header for the
@@ -1830,7 +1828,7 @@ static int tcnn_forward_impl(const float* table, const int64_t* offsets17_host, 
     // kernel; behind the level-major encoding launch (enc_workspace) the sigma-only MLPs take the matrix pipe in both arithmetics
     const bool f16 = (flags & MNRF_TCNN_F16) != 0;
     const bool encode_only = (flags & 0x80000000u) != 0;       // internal: mnrf_tcnn_encode
-    const bool valu = !encode_only && (env_valu || (flags & MNRF_TCNN_VALU) || any_modulo || (sigma_only && !f16 && !enc_workspace) || grad);
+    const bool valu = !encode_only && ((flags & MNRF_TCNN_VALU) || any_modulo || (sigma_only && !f16 && !enc_workspace) || grad);
     if (encode_only && any_modulo) return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_tcnn_encode: hashed level of a non-power-of-two size");
     if (!valu) {
         const long long n_tiles = (B + mf::TILE - 1) / mf::TILE;
@@ -1975,17 +1973,16 @@ static int tcnn_backward_impl(const float* table, const int64_t* offsets17_host,
     }
     if ((flags & MNRF_TCNN_GRAD_F16) && workspace) {
         P.g16 = (__half2*)(workspace + mnrf_tcnn_backward_workspace_floats(offsets17_host));
-        static const float scale = [] { const char* e = getenv("MNRF_TCNN_GRAD_SCALE"); return e && atof(e) > 0 ? (float)atof(e) : 1024.f; }();
-        P.g16_scale = scale;       // tinycudann's loss scale is 128; 1024 keeps 1e-7-sized contributions above f16's subnormal step
+        P.g16_scale = 1024.f;      // tinycudann's loss scale is 128; 1024 keeps 1e-7-sized contributions above f16's subnormal step
     }
     P.agg_levels = 0;
     // measured (1 M samples, bound 6): 15.96 / 15.00 / 14.12 / 13.77 / 13.70 ms per step with runs summed up to resolution
     // 64 / 128 / 256 / 512 / 1000 -- the shuffles are cheap next to an atomic, so every level the key can hold takes part
-    const int agg_res = getenv("MNRF_TCNN_AGG_RES") ? atoi(getenv("MNRF_TCNN_AGG_RES")) : 1022;
+    constexpr int agg_res = 1022;
     while (P.agg_levels < NL && (int)A.res[P.agg_levels] <= agg_res && A.res[P.agg_levels] < 1023u) ++P.agg_levels;
     long long folded = 0;
     plan_copies(offsets17_host, P.cp_n, P.cp_off, &folded);
-    if (!workspace || getenv("MNRF_TCNN_NO_COPIES")) {         // (null workspace: every level straight into d_table)
+    if (!workspace) {         // every level straight into d_table
         for (int l = 0; l < NL; ++l) P.cp_n[l] = 0;
         folded = 0;
     }

@@ -549,7 +549,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     # per-ray maps only (the per-sample tensors are neither copied nor, in the final pass, produced at all: render_rays
     # `_maps_only`): what to_cpu="maps" returns anyway; with to_cpu=False it is opt-in (maps_only=True), the full dict stays
     # the default contract
-    maps_only = bool(kwargs.get("maps_only", to_cpu == "maps")) and os.environ.get("MNRF_FUSED_EVAL", "1") != "0"
+    maps_only = bool(kwargs.get("maps_only", to_cpu == "maps"))
     rough = getattr(args, "app_control_mirror_roughness", False)
     batch_jitter = kwargs.get("batch_jitter", noise_iter is None)   # see the roughness branch of recurse()
     one_field = getattr(args, "only_one_field", False)
@@ -621,8 +621,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                 r2 = render_rays(system_sub.models, system_sub.embeddings, sec.contiguous(), N_samples, use_disp, 0, 0,
                                  N_importance, chunk, white_back, test_time=test_time, compute_normal=False,
                                  only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
-                                 current_epoch=fine_epoch + 1, _guard=False,
-                                 _maps_only=os.environ.get("MNRF_FUSED_EVAL", "1") != "0")
+                                 current_epoch=fine_epoch + 1, _guard=False, _maps_only=True)
             else:
                 r2 = recurse(sec.contiguous(), level + 1)
             if rough:                                                     # eval.py:622-674

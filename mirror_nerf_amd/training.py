@@ -104,19 +104,13 @@ def stage_target(hparams, target, gt_mask, gt_valid):
 def static_step_ok(system):
     """Can `system` take the static training route (recursion.render_rays_chunk_recursively "STATIC STEP": the reflected-ray
     count never visits the host)?  MirrorNeRF fields on the split arithmetic with operand planes, or -- round 6 -- hash-grid fields
-    (mnrf_tcnn_forward_n / _backward_n); a model the range guard has pinned to fp32 and MNRF_DW_PLANES=0 use the host-driven route."""
-    from . import autograd as AG
+    (mnrf_tcnn_forward_n / _backward_n); a model the range guard has pinned to fp32 uses the host-driven route."""
     from .mirror_nerf import MirrorNeRF, precision_of
     from .mirror_nerf_tcnn import MirrorNeRFTcnn
     models = list(system.models.values())
     if models and all(isinstance(m, MirrorNeRFTcnn) for m in models):
         return True      # round 6: the hash-grid field takes the live count too (mnrf_tcnn_forward_n / _backward_n)
-    return AG.DW_PLANES and all(isinstance(m, MirrorNeRF) and precision_of(m) == "split" for m in models)
-
-
-# MNRF_STATIC_STEP=0: train_step keeps the host-driven route (one device->host read of the reflected-ray count per level and step,
-# like train.py:175) even when the caller states `gt_valid`
-STATIC_STEP = os.environ.get("MNRF_STATIC_STEP", "1") != "0"
+    return all(isinstance(m, MirrorNeRF) and precision_of(m) == "split" for m in models)
 
 
 def extra_info(hp, gt_mask, epoch=0, train_geometry_stage=False):
@@ -140,9 +134,6 @@ def extra_info(hp, gt_mask, epoch=0, train_geometry_stage=False):
 GUARD_MODE = os.environ.get("MNRF_GUARD_MODE") or ("sync" if os.environ.get("MNRF_GUARD_SYNC", "0") == "1" else "skip")
 if GUARD_MODE not in ("skip", "sync"):
     raise ValueError(f"MNRF_GUARD_MODE={GUARD_MODE!r}: 'skip' or 'sync'")
-
-
-_SETTLE_LATE = os.environ.get("MNRF_GUARD_SETTLE_LATE", "1") != "0"      # 0: read the previous step's flags at the start of a step (A/B)
 
 
 _STATE_FLAGS = {}
@@ -169,7 +160,7 @@ def train_step(system, optimizer, rays, target, gt_mask, loss_fn=color_mask_loss
     module attribute -- no reflections are traced, the target inside the mirror is black (stage_target); the loss function built by
     total_loss_fn(..., train_geometry_stage=True) carries the stage's flag (train.py:439-446).
     gt_valid: the caller's statement that every entry of gt_mask is valid (>= 0; True) or that some are not (False) -- what
-    train.py:153 reads from the device.  With it (and MNRF_STATIC_STEP != 0, MirrorNeRF fields on the split arithmetic) the step
+    train.py:153 reads from the device.  With it (and fields that static_step_ok accepts) the step
     takes the STATIC route: no device->host read at all, the reflected-ray count stays on the device (recursion.py)."""
     from .mirror_nerf import check_guard, guard_async_begin, guard_async_end, pin_fp32
     rank, world = D.world()
@@ -199,11 +190,11 @@ def train_step(system, optimizer, rays, target, gt_mask, loss_fn=color_mask_loss
     # the first launches arrive.  On one rank the flags are settled after this step's forward has been queued -- the host waits
     # there anyway (the reflected-ray count) -- unless they have arrived already; with more than one rank they are settled
     # now (the pinning decision must reach every rank before any of them issues this step's collectives).
-    late = _SETTLE_LATE and token is not None and token[0] is not None and not collective and mode == "skip" and not token[0][2].query()
+    late = token is not None and token[0] is not None and not collective and mode == "skip" and not token[0][2].query()
     if token is not None and not late:
         settle(token)
 
-    static = STATIC_STEP and gt_valid is not None and static_step_ok(system)
+    static = gt_valid is not None and static_step_ok(system)
 
     stage = bool(getattr(system, "train_geometry_stage", False))
     if stage:
@@ -295,12 +286,12 @@ class FlatAdam:
     already produced (autograd._Pending: the `.grad`s of the parameters are views of one buffer), so nothing is gathered or
     copied.  The update is torch.optim.Adam's (same arithmetic, same `found_inf` contract: train_step's range guard) from
     `mnrf_adam_step`, one thread per four elements: torch's fused multi-tensor kernel deals 65 536-element chunks to blocks, TEN
-    blocks for a model, 46 us per model and step against 6 (round 4).  `kernel=False` (or MNRF_FLAT_ADAM_KERNEL=0) keeps torch's
+    blocks for a model, 46 us per model and step against 6 (round 4).  `kernel=False` keeps torch's
     fused Adam over the flat tensors.  Build it AFTER moving the models to their device (step() raises when a parameter no longer
     aliases its flat tensor).  Not a torch.optim.Optimizer: lr_scheduler constructors reject it -- schedule by writing
     `param_groups[0]["lr"]` (read at every step; GraphedTrainStep copies it to the device between replays)."""
 
-    def __init__(self, modules, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel=None):
+    def __init__(self, modules, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel=True):
         from .weights import param_refs
         self.modules, self.flats = list(modules), []
         for m in self.modules:
@@ -316,7 +307,7 @@ class FlatAdam:
                 flat[o:o + k].copy_(q.data.reshape(-1))
                 q.data = flat[o:o + k].view(q.shape)
             self.flats.append(torch.nn.Parameter(flat))
-        self.kernel = (os.environ.get("MNRF_FLAT_ADAM_KERNEL", "1") != "0") if kernel is None else bool(kernel)
+        self.kernel = bool(kernel)
         self.inner = torch.optim.Adam(self.flats, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fused=True)
         self.defaults = dict(self.inner.defaults)
         self.param_groups = self.inner.param_groups      # (lr / betas / eps / weight_decay are read from here at every step)
@@ -690,14 +681,9 @@ def synthetic_train_bench(dev, all_rays, steps=10, warmup=3, batch=1024, seed=0,
             m.sigma.weight.mul_(20.0)
             m.sigma.bias.fill_(1.0)
     import os
-    # fused Adam: one kernel per step instead of the foreach kernels, same arithmetic; measured 8.0 vs 8.9 ms per step on the
-    # same box (the kernels of a step take 7.9 ms; this removes launch bubbles).  MNRF_ADAM_FUSED=0 selects the foreach implementation.
-    # MNRF_FLAT_ADAM=0: torch's fused Adam over the 64 parameter tensors (rounds 2-3); default: the same over one flat tensor per model
-    flat_adam = os.environ.get("MNRF_FLAT_ADAM", "1") != "0"
-    if flat_adam:
-        opt = FlatAdam(list(system.models.values()), lr=5e-4)
-    else:
-        opt = torch.optim.Adam(list(system.parameters()), lr=5e-4, fused=os.environ.get("MNRF_ADAM_FUSED", "1") == "1")
+    # Adam over one flat tensor per model (rounds 2-3: torch's fused Adam over the 64 parameter tensors; fused rather than foreach
+    # measured 8.0 vs 8.9 ms per step on the same box: the kernels of a step take 7.9 ms, fusing removed launch bubbles)
+    opt = FlatAdam(list(system.models.values()), lr=5e-4)
     g = torch.Generator(device=dev)
     g.manual_seed(1 + rank)
     # "run_sh": run.sh:259-280's recipe after its geometry stage -- TotalLoss with all five terms (--use_plane_consistent_loss; epoch
@@ -720,7 +706,7 @@ def synthetic_train_bench(dev, all_rays, steps=10, warmup=3, batch=1024, seed=0,
     # reflected-ray count is read by the host in the middle of the step (train.py:175).  MNRF_TRAIN_ROUTE overrides.
     # With more than one rank the graph holds the collectives too (round 6); a stack that cannot capture them falls back to "static".
     route = os.environ.get("MNRF_TRAIN_ROUTE") or route_arg or "graph"
-    if route != "host" and not (flat_adam and static_step_ok(system)):
+    if route != "host" and not static_step_ok(system):
         route = "host"
     if route == "graph" and (world > 1 or D.forced()) and torch.distributed.get_backend() != "nccl":
         route = "static"      # (gloo stages through the host: nothing to capture; the CPU / shared-GPU test transports)
@@ -796,7 +782,7 @@ def synthetic_train_bench(dev, all_rays, steps=10, warmup=3, batch=1024, seed=0,
                        else route + " (ended by a range-guard trip)")),
             "collectives_in_graph": bool(graphed is not None and graphed.collective and not graphed.ended),
             "optimizer": ("training.FlatAdam (Adam over one flat parameter tensor per model, " +
-                          ("mnrf_adam_step" if getattr(opt, "kernel", False) else "torch's fused kernel") + ")") if flat_adam else "torch.optim.Adam(fused=True)",
+                          ("mnrf_adam_step" if opt.kernel else "torch's fused kernel") + ")"),
             "loss": float(loss.item()),
             "loss_fn": "losses.TotalLoss (colour, mask, normal, normal_reg; fused HIP kernels; second-order pass on)" if loss_name == "total"
                        else "losses.TotalLoss as run.sh:259-280 trains (colour, mask, plane-consistent with device-side draws, normal, normal_reg)"

@@ -459,36 +459,6 @@ def test_optimizer_steps_are_seen_by_the_next_launch(fused):
     assert all(not torch.equal(images[i], images[i + 1]) for i in range(1, 11)), "the packed image does not follow the optimizer"
 
 
-def test_pipelined_weight_gradient_kernel_matches_autograd():
-    """MNRF_DW_PIPE=1 (the pipelined 128-wide weight-gradient GEMM, non-default: csrc/mnrf_dw.hip) is read once per
-    process, so the gradient tests run again in a child process with it set (ragged sizes: partial last stage, fewer
-    stages than the pipeline is deep, the second-order pass)."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, MNRF_DW_PIPE="1", MNRF_DW_PLANES="0")      # (the rows route: planes have their own GEMM)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k",
-                        "field_backward_matches_autograd or second_order or train_step_gradients_golden"],
-                       cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-
-
-def test_rows_route_of_the_weight_gradients_still_works():
-    """MNRF_DW_PLANES=0 (read at import): the round-1/2 route of the split arithmetic -- fp32 rows of saved activations and
-    dY, bf16 x 6 GEMMs per evaluation -- stays selectable; the gradient tests run on it in a child process."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, MNRF_DW_PLANES="0")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k",
-                        "field_backward_matches_autograd or cut_heads or accumulates_over_samples or train_step_gradients_golden "
-                        "or folded_gradient"],
-                       cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-
-
 @pytest.mark.parametrize("B,n_eval", [(200, 1), (4096 + 77, 2)])
 def test_planes_route_agrees_with_rows_route(B, n_eval, precision):
     """Through the C ABI on the same samples and seeds (eight orders of magnitude apart): mnrf_field_forward_train with
@@ -703,20 +673,6 @@ def test_second_order_planes_route_agrees_with_rows_route(B, ray_mode):
     torch.cuda.synchronize()
     for n, a, b, c in zip(PARAM_NAMES, d_m, d_1, d_p):
         assert _rel(a, b + c) <= 1e-5, (n, _rel(a, b + c))      # (another plan deals the stages differently: another summation order)
-
-
-def test_two_buffer_loop_of_the_weight_gradient_gemm():
-    """MNRF_DWP_RING=0 (read once by the library) selects the round-3 loop of mnrf_dwp.hip -- two whole-stage buffers instead of
-    the ring of half-stages -- which computes the same gradients; the plane-route tests run on it in a child process."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, MNRF_DWP_RING="0")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k",
-                        "planes_route_agrees or field_backward_matches_autograd"],
-                       cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
 
 
 def _two_evals(model, x1, x2, d):
