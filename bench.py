@@ -11,12 +11,17 @@ A "step" is one frame.  Inputs (rays, packed weights) are resident in HBM when t
 result maps stay on the GPU (`to_cpu=False`; the reference's per-chunk D2H of every dict entry
 is caller-side data movement).
 
+A plain run sets up, warms up, times the frames, writes --dump-outputs and prints the line: `value`, `ms_per_step` and the
+`roofline` of the timed frames.  `--full` adds the secondary legs after the timed frames (the other arithmetic, host maps, the
+ray-fused pass, training steps, configs 1, 4 and 5, the trained pair, the CPU baselines, strong scaling with more than one
+rank); MNRF_BENCH_LEGS picks among them.
+
 Multi-GPU (`--gpus N`): one process per GPU over RCCL.  Launched by `python -m torch.distributed.run ...
 bench.py --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) -- or plainly as `python bench.py
 --gpus N`, in which case it re-executes itself under torch.distributed.run on 127.0.0.1.  Frames are
 independent units: every rank renders its own frame (weak scaling), no collective on the data path,
 barrier + max-over-ranks timing; value = rays of all ranks / slowest rank's time.  With more than one
-rank the line also carries `strong_scaling` (ONE frame dealt to the ranks in interleaved 4096-ray tiles,
+rank and --full the line also carries `strong_scaling` (ONE frame dealt to the ranks in interleaved 4096-ray tiles,
 dist.render_sharded, + the optional gather of the maps to rank 0) and `train_step` (the 1024-ray
 training step per rank with one flat RCCL all-reduce of the 5.3 MB gradient, train.py:577-584).
 """
@@ -280,9 +285,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames, also run the secondary legs: the other arithmetic, host maps, the ray-fused "
+                         "pass, training steps, configs 1, 4 and 5, the trained pair, the CPU baselines and, with more than one "
+                         "rank, strong scaling")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU time budget of the cpu_baseline leg")
-    ap.add_argument("--no-train", action="store_true", help="skip the short training-step measurement")
+    ap.add_argument("--no-train", action="store_true", help="--full without the training and config 1, 4, 5 legs")
     ap.add_argument("--precision", choices=("split", "fp32"), default="split",
                     help="arithmetic of the field kernel's Linears: fp32 operands as hi/lo f16 pairs on the f16 matrix "
                          "pipe (default, ~1e-6 of fp32) or the bit-exact fp32 MFMA chain")
@@ -292,11 +301,16 @@ def main():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
-    # MNRF_BENCH_LEGS=headline,strong,other,host_maps,fused,train,train_total,config3,hash_grid,rough,trained,config1,cpu : run only
-    # these secondary legs (default: all that apply) -- an 8-rank run can be bounded to "headline,strong,train"
+    # secondary legs run with --full only.  MNRF_BENCH_LEGS=headline,strong,other,host_maps,fused,train,train_total,config3,hash_grid,
+    # rough,trained,config1,cpu : run only these of them (default: all that apply) -- an 8-rank run can be bounded to
+    # "headline,strong,train"
     want = os.environ.get("MNRF_BENCH_LEGS")
     want = None if not want else {w.strip() for w in want.split(",") if w.strip()}
-    leg = (lambda name: True) if want is None else (lambda name: name in want)
+    if want is not None and not a.full:
+        print("bench.py: MNRF_BENCH_LEGS picks among the --full legs; without --full none of them runs", file=sys.stderr)
+
+    def leg(name):
+        return a.full and (want is None or name in want)
 
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or os.environ.get("MNRF_BENCH_SPAWN") == "1"):
         _respawn(a)          # MNRF_BENCH_SPAWN=1: take the launcher path at N = 1 too (tests on a 1-GPU box)
@@ -379,10 +393,10 @@ def main():
     legs_done = []
 
     def emit(incomplete=None, early=False):
-        """Rank 0 prints the line.  N = 1: ONE line, at the end.  N > 1: the headline line goes out RIGHT AFTER the weak-scaling
-        measurement (`"line": "headline"`, flushed), the complete one replaces it at the end (`"line": "complete"`): a harness
-        takes the last parseable line, and a stall in a secondary leg cannot cost the run its number.  `incomplete`: legs cut
-        short by the deadline below."""
+        """Rank 0 prints the line.  N = 1, or N > 1 without --full: ONE line, at the end.  N > 1 with --full: the headline line
+        goes out RIGHT AFTER the weak-scaling measurement (`"line": "headline"`, flushed), the complete one replaces it at the end
+        (`"line": "complete"`): a harness takes the last parseable line, and a stall in a secondary leg cannot cost the run its
+        number.  `incomplete`: legs cut short by the deadline below."""
         if rank == 0:
             split = a.precision == "split"
             peak = PEAK_F16_MFMA_TFLOPS if split else PEAK_FP32_MFMA_TFLOPS
@@ -486,16 +500,16 @@ def main():
                 res["incomplete_legs"] = incomplete
             if multi:
                 res["line"] = "headline" if early else "complete"
-            if want is not None:
+            if a.full and want is not None:
                 res["legs_requested"] = sorted(want)
             print(json.dumps(res), flush=True)
 
 
-    # N > 1: the legs after the headline measurement are bounded.  A rank that stalls in a secondary leg (a collective that never
-    # completes) must not cost the run its line: after MNRF_BENCH_LEG_DEADLINE seconds (default 900) rank 0 prints what was
-    # measured, names the legs that did not finish, and every rank leaves.  `value` was measured above, before any of this.
+    # N > 1 with --full: the legs after the headline measurement are bounded.  A rank that stalls in a secondary leg (a collective
+    # that never completes) must not cost the run its line: after MNRF_BENCH_LEG_DEADLINE seconds (default 900) rank 0 prints what
+    # was measured, names the legs that did not finish, and every rank leaves.  `value` was measured above, before any of this.
     deadline = None
-    if multi:
+    if multi and a.full:
         import threading
 
         def _expired():

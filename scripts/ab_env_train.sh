@@ -5,7 +5,7 @@ out=gpurun_out/$1; var=$2; a=$3; b=$4; rounds=${5:-2}
 mkdir -p "$out"
 for i in $(seq 1 "$rounds"); do
   for v in "$a" "$b"; do
-    env "$var=$v" MNRF_BENCH_LEGS=train,train_total,config3 python bench.py --steps 1 --warmup 0 > "$out/line_${v}_$i.json" 2> "$out/err_${v}_$i.log"
+    env "$var=$v" MNRF_BENCH_LEGS=train,train_total,config3 python bench.py --steps 1 --warmup 0 --full > "$out/line_${v}_$i.json" 2> "$out/err_${v}_$i.log"
     python - "$out/line_${v}_$i.json" "$var=$v" <<'P' >> "$out/ab.log"
 import json, sys
 d = None

@@ -327,12 +327,12 @@ def test_one_rank_pinned_outside_the_training_step(mode):
 
 
 def test_bench_with_two_ranks_sharing_the_gpu():
-    """`bench.py --gpus 2` end to end (launcher path, weak + strong scaling legs, training step with the all-reduce,
+    """`bench.py --gpus 2 --full` end to end (launcher path, weak + strong scaling legs, training step with the all-reduce,
     the hash-grid leg across ranks) on one GPU shared by both ranks; the numbers are void, the line's shape is not."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MNRF_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env = _share_env(env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     import json
@@ -357,7 +357,7 @@ def test_bench_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MNRF_FORCE_COLLECTIVES="1", MNRF_BENCH_SPAWN="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     import json
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
