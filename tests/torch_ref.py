@@ -1,5 +1,6 @@
-"""Plain-torch fp32 restatements of the two floating-point kernels that have a backward pass
-(field MLP, compositing).  TEST INFRASTRUCTURE ONLY: the GPU tests differentiate these with
+"""Plain-torch restatements of the two floating-point kernels that have a backward pass
+(field MLP, compositing), in the dtype of their inputs (fp32, or float64 with the kernel's own
+activation masks: `field(..., masks=)`).  TEST INFRASTRUCTURE ONLY: the GPU tests differentiate these with
 torch.autograd to check the hand-written HIP backward kernels; the product never imports this."""
 import torch
 
@@ -16,29 +17,61 @@ def embed(x, n):
     return torch.cat(out, -1)
 
 
-def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False, keep_mirror=None):
+# the activations of the field MLP: ReLU behind L1..L8 and dir_encoding, LeakyReLU(0.01) behind is_mirror_net.0
+MASK_NAMES = tuple(f"L{i + 1}" for i in range(8)) + ("dir", "mir")
+
+
+def masks_of(pre):
+    """Activation masks of pre-activations (dict name -> tensor, MASK_NAMES): 1 where y > 0, else 0 (ReLU) or 0.01 (the
+    LeakyReLU of is_mirror_net.0).  torch's own convention at y == 0: the gradient there is 0 (ReLU) or 0.01."""
+    out = {}
+    for n, y in pre.items():
+        pos = y > 0
+        out[n] = pos.to(y.dtype) if n != "mir" else torch.where(pos, torch.ones_like(y), torch.full_like(y, 0.01))
+    return out
+
+
+def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False, keep_mirror=None, masks=None, acts=None):
     """w: dict name -> tensor (reference parameter names); returns sigma (B), rgb, pred_normal, is_mirror (B)
     [, normal = l2n(-d sigma/d xyz) built with create_graph=True like utils/func.py:10-25].
-    cut_normal / cut_mirror / keep_mirror (B, bool): the heads see geo_feat.detach() (mirror_nerf.py:154-183)."""
+    cut_normal / cut_mirror / keep_mirror (B, bool): the heads see geo_feat.detach() (mirror_nerf.py:154-183).
+    masks (dict MASK_NAMES -> tensor shaped like the pre-activation, held constant): every activation becomes y * mask, so
+    that the function is the piecewise-linear piece a kernel's own ReLU masks select (pre-activations within rounding of 0
+    then cannot flip between the kernel and this reference).  acts: a dict, filled with the pre-activations (MASK_NAMES) and
+    the inputs of the Linears ("enc", "h1".."h8", "fin", "hd", "hn", "hm")."""
     if with_normal and not xyz.requires_grad:
         xyz = xyz.requires_grad_(True)
+    keep = acts if acts is not None else {}
+
+    def act(name, y):
+        keep[name] = y
+        if masks is not None:
+            return y * masks[name]
+        return torch.nn.functional.leaky_relu(y, 0.01) if name == "mir" else torch.relu(y)
+
     enc = embed(xyz, 10)
+    keep["enc"] = enc
     h = enc
     for i in range(8):
         if i == 4:
             h = torch.cat([enc, h], -1)
-        h = torch.relu(h @ w[f"xyz_encoding_{i+1}.0.weight"].T + w[f"xyz_encoding_{i+1}.0.bias"])
+        h = act(f"L{i + 1}", h @ w[f"xyz_encoding_{i+1}.0.weight"].T + w[f"xyz_encoding_{i+1}.0.bias"])
+        keep[f"h{i + 1}"] = h
     sigma = (h @ w["sigma.weight"].T + w["sigma.bias"])[:, 0]
     fin = h @ w["xyz_encoding_final.weight"].T + w["xyz_encoding_final.bias"]
-    hd = torch.relu(torch.cat([fin, dir_emb], -1) @ w["dir_encoding.0.weight"].T + w["dir_encoding.0.bias"])
+    keep["fin"] = fin
+    hd = act("dir", torch.cat([fin, dir_emb], -1) @ w["dir_encoding.0.weight"].T + w["dir_encoding.0.bias"])
+    keep["hd"] = hd
     rgb = torch.sigmoid(hd @ w["rgb.0.weight"].T + w["rgb.0.bias"])
     hN = h.detach() if cut_normal else h
     hM = h.detach() if cut_mirror else h
     if keep_mirror is not None and not cut_mirror:
         hM = torch.where(keep_mirror[:, None], h, h.detach())
     hn = hN @ w["normal_net.0.weight"].T + w["normal_net.0.bias"]
+    keep["hn"] = hn
     pn = l2n(hn @ w["normal_net.1.weight"].T + w["normal_net.1.bias"])
-    hm = torch.nn.functional.leaky_relu(hM @ w["is_mirror_net.0.weight"].T + w["is_mirror_net.0.bias"], 0.01)
+    hm = act("mir", hM @ w["is_mirror_net.0.weight"].T + w["is_mirror_net.0.bias"])
+    keep["hm"] = hm
     m = torch.sigmoid(hm @ w["is_mirror_net.2.weight"].T + w["is_mirror_net.2.bias"])[:, 0]
     if with_normal:
         (grad,) = torch.autograd.grad(sigma, xyz, torch.ones_like(sigma), create_graph=True, retain_graph=True)
