@@ -322,10 +322,17 @@ int mnrf_bench_gather(const void* table, int64_t table_bytes, int bytes_per_gath
  * no per-sample tensor (36 B per sample written and read back otherwise) touches HBM.  What the reference's eval caller
  * copies to the CPU and nobody reads (eval.py:735-736, SURVEY 3 "result-dict contract") is simply never produced.
  * noise_std = 0 (test_time), no density-gradient normal.  Null map pointers are skipped; weights (n_rays, 192) optional.
+ * flags: MNRF_FUSED_WHITE_BACK (the white_back of mnrf_composite; this argument used to be that int, 0 or 1) |
+ * MNRF_FUSED_RGB_DEPTH: the caller reads colour and depth only (the last reflection level of a frame, eval.py:676-697) -- the
+ * mirror head is not evaluated (the folded stream puts it last and the launch stops in front of it, 1044 instead of 1112 tile
+ * pairs per sample) and the compositing forms rgb, depth and opacity alone (weights and x_surface on request); mirror_mask and
+ * surf_normal must be null.  The maps it writes equal those of the full launch bit for bit.
  * Returns MNRF_ERR_UNSUPPORTED when the 48-samples-per-wave tuning is off (MNRF_SPLIT48=0). */
+#define MNRF_FUSED_WHITE_BACK 1u
+#define MNRF_FUSED_RGB_DEPTH 2u
 int mnrf_fused_samples_per_ray(void);
 int mnrf_field_composite_fused(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
-                               const float* dir_emb, int64_t dir_stride, int white_back,
+                               const float* dir_emb, int64_t dir_stride, int flags,
                                float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
                                float* surf_normal, float* x_surface, void* stream);
 

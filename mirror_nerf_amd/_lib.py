@@ -26,6 +26,8 @@ _str = ctypes.c_void_p      # hipStream_t
 MNRF_SIGMA_ONLY = 1
 MNRF_GRAD_NORMAL = 2
 MNRF_SPLIT_F16 = 4
+MNRF_FUSED_WHITE_BACK = 1      # flags of mnrf_field_composite_fused
+MNRF_FUSED_RGB_DEPTH = 2
 MNRF_TCNN_VALU = 8
 MNRF_TCNN_F16 = 256
 MNRF_TCNN_GRAD_FIXED = 512

@@ -61,12 +61,18 @@ __device__ __forceinline__ void composite_ray(const Src& src, int S, int lane, l
             }
         }
     }
+    // (a sum whose input the source does not have stays 0 without its reduction: with a source that knows this at compile time,
+    // as the rgb / depth variant of the ray-fused pass does, those shuffles are not even emitted)
     a_op = wave_sum(a_op);
     a_d = wave_sum(a_d);
-    a_m = wave_sum(a_m);
-    a_nd = wave_sum(a_nd);
+    if (src.has_mirror()) a_m = wave_sum(a_m);
+    if (src.has_pn() && src.has_gn()) a_nd = wave_sum(a_nd);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { a_c[k] = wave_sum(a_c[k]); a_n[k] = wave_sum(a_n[k]); a_g[k] = wave_sum(a_g[k]); }
+    for (int k = 0; k < 3; ++k) {
+        if (src.has_rgb()) a_c[k] = wave_sum(a_c[k]);
+        if (src.has_pn()) a_n[k] = wave_sum(a_n[k]);
+        if (src.has_gn()) a_g[k] = wave_sum(a_g[k]);
+    }
     if (lane == 0) {
         if (A.opacity) A.opacity[ray] = a_op;
         if (A.rgb_map) {

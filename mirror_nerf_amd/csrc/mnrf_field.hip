@@ -221,19 +221,23 @@ extern "C" int mnrf_field_forward(float* packed, unsigned flags, int64_t B, cons
 extern "C" int mnrf_fused_samples_per_ray(void) { return split48_ray_samples(); }
 
 extern "C" int mnrf_field_composite_fused(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
-                                          const float* dir_emb, int64_t dir_stride, int white_back,
+                                          const float* dir_emb, int64_t dir_stride, int flags,
                                           float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
                                           float* surf_normal, float* x_surface, void* stream) {
     if (!packed || !rays || !z_vals || !dir_emb) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: null pointer");
     if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: negative ray count");
+    if (flags & ~(int)(MNRF_FUSED_WHITE_BACK | MNRF_FUSED_RGB_DEPTH)) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: unknown flag bits");
+    const bool rgb_depth = flags & MNRF_FUSED_RGB_DEPTH;
+    if (rgb_depth && (mirror_mask || surf_normal))
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: MNRF_FUSED_RGB_DEPTH evaluates neither the mirror head nor the normal map");
     if (n_rays == 0) return MNRF_OK;
     if (!split48_enabled())
         return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_composite_fused: needs the 48-samples-per-wave tuning (MNRF_SPLIT48 != 0)");
     const int spr = split48_ray_samples();
     FieldArgs A{packed, MNRF_SPLIT_F16, (long long)n_rays * spr, nullptr, 3, rays, z_vals, spr, dir_emb, (long long)dir_stride,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    A.fuse = 1;
-    A.white_back = white_back;
+    A.fuse = rgb_depth ? 2 : 1;
+    A.white_back = (flags & MNRF_FUSED_WHITE_BACK) != 0;
     A.f_weights = weights; A.f_opacity = opacity; A.f_rgb_map = rgb_map; A.f_depth = depth; A.f_mirror_mask = mirror_mask;
     A.f_surf_normal = surf_normal; A.f_x_surface = x_surface;
     if (launch_split48(A, false, (hipStream_t)stream) != 0)

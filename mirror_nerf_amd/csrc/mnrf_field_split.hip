@@ -174,20 +174,23 @@ __global__ void split_fold_kernel(FoldImages I) {
     typedef _Float16 h8v __attribute__((ext_vector_type(8)));
     h8v hi, lo;
     for (int j = 0; j < 8; ++j) hi[j] = lo[j] = (_Float16)0.f;
-    // source pair in the split stream: trunk and sigma block (its rows 1..3 are replaced below), mirror head, view columns and rgb
-    const int sp = pair < 968 ? pair : (pair < 1036 ? pair + (1036 - 968) : (pair >= 1100 && pair < 1112 ? pair + (1296 - 1100) : -1));
+    // source pair in the split stream: trunk and sigma block (its rows 1..3 are replaced below), view columns and rgb, mirror head
+    const int sp = pair < FOLD_POS_DIR ? pair
+                 : pair < FOLD_POS_VIEW ? -1
+                 : pair < FOLD_POS_MIR1 ? pair + (1296 - FOLD_POS_VIEW)
+                 : pair < SPLIT_FOLD_USED ? pair + (1036 - FOLD_POS_MIR1) : -1;
     if (sp >= 0) {
         const char* src = (const char*)(packed + OFF_SPLIT_FWD) + (long long)sp * PAIR_BYTES + lane * 16;
         hi = *(const h8v*)src;
         lo = *(const h8v*)(src + PAIR_BYTES / 2);
     }
     const bool fold_nrm = pair >= 960 && pair < 968 && row >= 1 && row <= 3;
-    const bool fold_dir = pair >= 1036 && pair < 1100;
+    const bool fold_dir = pair >= FOLD_POS_DIR && pair < FOLD_POS_VIEW;
     if (fold_nrm || fold_dir) {
-        const int T = fold_nrm ? pair - 960 : (pair - 1036) / 8;
+        const int T = fold_nrm ? pair - 960 : (pair - FOLD_POS_DIR) / 8;
         const int c0 = 32 * T + 4 * (lane >> 4);      // columns c0 + 0..3 (halves 0..3) and c0 + 16 + 0..3 (halves 4..7)
         // out[n][c] = sum_k A[n][k] B[k][c], k ascending
-        const float* a = fold_nrm ? I.wn2[blockIdx.y] + (row - 1) * 128 : I.wdir[blockIdx.y] + (16 * ((pair - 1036) % 8) + row) * (W + ENC_DIR);
+        const float* a = fold_nrm ? I.wn2[blockIdx.y] + (row - 1) * 128 : I.wdir[blockIdx.y] + (16 * ((pair - FOLD_POS_DIR) % 8) + row) * (W + ENC_DIR);
         const float* bm = fold_nrm ? I.wn1[blockIdx.y] : I.wfin[blockIdx.y];
         const int K = fold_nrm ? 128 : W;
         double acc[8];

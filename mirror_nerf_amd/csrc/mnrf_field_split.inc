@@ -90,6 +90,12 @@ struct CompLdsSrc {
     __device__ __forceinline__ float pn(int s, int k) const { return f[(4 + k) * WG_SAMPLES + s]; }
     __device__ __forceinline__ float gn(int, int) const { return 0.f; }
 };
+// ... of the rgb / depth variant (RGB_DEPTH): no mirror head, no normal map -- known at compile time, so the compositing forms
+// the colour, depth and opacity sums alone
+struct CompLdsSrcRgbDepth : CompLdsSrc {
+    __device__ __forceinline__ bool has_mirror() const { return false; }
+    __device__ __forceinline__ bool has_pn() const { return false; }
+};
 
 __device__ __forceinline__ unsigned long long enc_out_of_range(const float (&x)[S][3]) {
     bool big = false;
@@ -527,10 +533,14 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // 1..3 of the sigma block, xyz_encoding_final folded into dir_encoding's h8 columns: 1112 instead of 1308 pairs per sample.  The
 // kernels that keep activations for a backward pass (GRAD) need the unfolded heads; the sigma-only ones stay on the split stream
 // (same trunk, same sigma row).
-template <bool SIGMA_ONLY, bool GRAD, bool PLANES = false, bool FUSE = false>
-__global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_kernel(FieldArgs A) {
+// RGB_DEPTH (FUSE only): the caller reads colour and depth alone (the last reflection level of a frame): the stream stops in front
+// of the mirror head, which the folded order puts last (mnrf_layout.h FOLD_POS_MIR1), and the compositing wave forms only the
+// rgb / depth / opacity sums.
+template <bool SIGMA_ONLY, bool GRAD, bool PLANES, bool FUSE, bool RGB_DEPTH>
+__device__ __forceinline__ void field_split_body(FieldArgs A) {
     static_assert(!PLANES || (GRAD && !SIGMA_ONLY && S == 2), "operand planes: the training forward (32 samples per wave)");
     static_assert(!FUSE || (S == 3 && !SIGMA_ONLY && !GRAD), "ray-fused compositing: the 192-sample fine pass");
+    static_assert(!RGB_DEPTH || FUSE, "rgb / depth only: a variant of the ray-fused pass");
     constexpr bool FOLD = !SIGMA_ONLY && !GRAD;
     float* const fz = (float*)(smem + LDS_FUSE);      // FUSE: [9][WG_SAMPLES]
     // Dynamic tile queue (S = 3, FieldArgs::tile_queue): the launch has one workgroup per CU; the first tile is the workgroup's
@@ -870,7 +880,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             for (int s = 0; s < S; ++s)
                 if (sval(s)) out_store(A.sigma + sidx(s), acc[s][0][0]);
         }
-        if constexpr (FOLD) put_normal(acc, std::integral_constant<int, 1>{});
+        if constexpr (FOLD && !RGB_DEPTH) put_normal(acc, std::integral_constant<int, 1>{});
     }
 
     if (!SIGMA_ONLY) {
@@ -890,13 +900,14 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             gemm_part<4, 1, 1032>(acc, nh, nl, st, wave, lane16);
             put_normal(acc, std::integral_constant<int, 0>{});
         }
-        // ---- mirror probability: 256 -> 128 LeakyReLU(0.01) -> 1 sigmoid (mirror_nerf.py:94-99)
-        {
+        // ---- mirror probability: 256 -> 128 LeakyReLU(0.01) -> 1 sigmoid (mirror_nerf.py:94-99).  FOLD: behind the colour
+        //      branch, where the folded stream has it; RGB_DEPTH: never evaluated (its stream ends in front of it)
+        const auto mirror_head = [&]() {
             u32x4 mh[S][4], ml[S][4];
             {
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_MIR1, gq());
-                gemm_part<8, 8, FOLD ? 968 : 1036, HP, ST4>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
+                gemm_part<8, 8, FOLD ? FOLD_POS_MIR1 : 1036, HP, ST4>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
                 if (keep) {
                     uint64_t bits[S];
                     save_acc<8, 2>(A.save_x + (long long)SEC_HM * A.B, 128, 0, acc, idx, valid, g, bits);
@@ -910,7 +921,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_MIR2, gq());
-            gemm_part<4, 1, FOLD ? 1032 : 1100>(acc, mh, ml, st, wave, lane16);
+            gemm_part<4, 1, FOLD ? FOLD_POS_MIR2 : 1100>(acc, mh, ml, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll
@@ -921,7 +932,8 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 for (int s = 0; s < S; ++s)
                     if (sval(s)) out_store(A.is_mirror + sidx(s), sigmoidf_(acc[s][0][0]));
             }
-        }
+        };
+        if constexpr (!FOLD) mirror_head();
         // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid.  FOLD: dir_encoding reads h8
         //      through the folded map (final's 256 outputs are never formed)
         // view-encoding B operands (32 padded columns: one k-step)
@@ -949,8 +961,8 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                 view_operands(vh, vl);
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_DIR, gq());
-                gemm_part<8, 8, 1036, HP>(acc, hh, hl, st, wave, lane16);
-                gemm_part<1, 8, 1100>(acc, vh, vl, st, wave, lane16);
+                gemm_part<8, 8, FOLD_POS_DIR, HP>(acc, hh, hl, st, wave, lane16);
+                gemm_part<1, 8, FOLD_POS_VIEW>(acc, vh, vl, st, wave, lane16);
                 acc_to_b<8, 1, false>(dh, dl, acc, 0, tid, st.sat);
             } else {
                 u32x4 fh[S][8], fl[S][8];
@@ -981,7 +993,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_RGB, gq());
-            gemm_part<4, 1, FOLD ? 1108 : 1304>(acc, dh, dl, st, wave, lane16);
+            gemm_part<4, 1, FOLD ? FOLD_POS_RGB : 1304>(acc, dh, dl, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll
@@ -1003,6 +1015,7 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
                     }
             }
         }
+        if constexpr (FOLD && !RGB_DEPTH) mirror_head();
     }
 
     if (GRAD) {
@@ -1110,12 +1123,18 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
         __syncthreads();
         if (wave == 0) {
             const long long ray = tile;
-            const CompLdsSrc src{fz, A.f_surf_normal != nullptr, A.f_mirror_mask != nullptr};
-            const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, A.f_rgb_map, A.f_depth, A.f_mirror_mask,
-                               A.f_surf_normal, nullptr, nullptr, A.f_x_surface, A.rays, A.white_back};
             int cl;      // (opaque: a plain lane id is hoisted out of the tile loop and parked in scratch)
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(cl));
-            composite_ray(src, WG_SAMPLES, cl, ray, out);
+            if constexpr (RGB_DEPTH) {      // (the launcher refuses mirror-mask and normal maps for this variant)
+                const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, A.f_rgb_map, A.f_depth, nullptr,
+                                   nullptr, nullptr, nullptr, A.f_x_surface, A.rays, A.white_back};
+                composite_ray(CompLdsSrcRgbDepth{fz, false, false}, WG_SAMPLES, cl, ray, out);
+            } else {
+                const CompLdsSrc src{fz, A.f_surf_normal != nullptr, A.f_mirror_mask != nullptr};
+                const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, A.f_rgb_map, A.f_depth, A.f_mirror_mask,
+                                   A.f_surf_normal, nullptr, nullptr, A.f_x_surface, A.rays, A.white_back};
+                composite_ray(src, WG_SAMPLES, cl, ray, out);
+            }
         }
     }
     if (!queued) break;
@@ -1138,6 +1157,18 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     }
 }
 
+template <bool SIGMA_ONLY, bool GRAD, bool PLANES = false, bool FUSE = false>
+__global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_kernel(FieldArgs A) {
+    field_split_body<SIGMA_ONLY, GRAD, PLANES, FUSE, false>(A);
+}
+// the rgb / depth variant of the ray-fused pass: a kernel of its own name, so that the instantiations above keep theirs
+template <bool ON = true>
+__global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_kernel_rgb_depth(FieldArgs A) {
+    field_split_body<false, false, false, ON, ON>(A);
+}
+
+// (a template only so that the discarded branch below never instantiates the ray-fused kernels in the S = 2 tunings)
+template <bool UNUSED = false>
 inline int launch(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s) {
     const long long blocks64 = (A.B + WG_SAMPLES - 1) / WG_SAMPLES;
     if (blocks64 > 0x7fffffff || A.B > 0x7fffffffLL) return -1;
@@ -1148,7 +1179,9 @@ inline int launch(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s)
         grid = dim3((unsigned)A.resident);
     }
     if (sigma_only && !grad) hipLaunchKernelGGL((field_split_kernel<true, false>), grid, block, LDS_BYTES, s, A);
-    else if (!sigma_only && !grad && S == 3 && A.fuse)
+    else if (!sigma_only && !grad && S == 3 && A.fuse == 2) {
+        if constexpr (S == 3) hipLaunchKernelGGL((field_split_kernel_rgb_depth<>), grid, block, LDS_BYTES_FUSE, s, A);
+    } else if (!sigma_only && !grad && S == 3 && A.fuse)
         hipLaunchKernelGGL((field_split_kernel<false, false, false, S == 3>), grid, block, LDS_BYTES_FUSE, s, A);
     else if (!sigma_only && !grad) hipLaunchKernelGGL((field_split_kernel<false, false>), grid, block, LDS_BYTES, s, A);
 #ifndef MNRF_SPLIT_NO_GRAD

@@ -133,14 +133,22 @@ constexpr int64_t SPLIT_TAIL_FLOATS = 2 * 16 * (PAIR_BYTES / 4);
 //      xyz_encoding_final only feeds dir_encoding, whose first 256 columns Wd times it are one 128 x 256 map Wd.Wf on h8 (bias
 //      Wd.bf + bd).  The products are formed in fp64 by mnrf_fold_weights_n and split from the fp64 value.  The stream is the
 //      split forward stream with those heads folded: trunk 0..959 (a copy), sigma | normal 960 (one 16-row block: sigma in row 0,
-//      the folded normal in rows 1..3), is_mirror_net.0 968, is_mirror_net.2 1032, dir_encoding 1036 (folded h8 columns) 1100
-//      (view), rgb 1108, end 1112 -- 1112 pairs per full sample instead of 1308.  Behind its read-ahead tail lies a copy of the
-//      bias block with the folded biases in place (normal at BIAS_SIG + 1..3, dir_encoding at BIAS_DIR).
+//      the folded normal in rows 1..3), dir_encoding 968 (folded h8 columns) 1032 (view), rgb 1040, is_mirror_net.0 1044,
+//      is_mirror_net.2 1108, end 1112 -- 1112 pairs per full sample instead of 1308.  The mirror head comes LAST so that a pass
+//      whose caller reads only colour and depth (the last reflection level of a frame) is the prefix 0..1043 of the stream: the
+//      rgb / depth variant of the ray-fused kernel (mnrf_field_split.inc RGB_DEPTH) stops there.  Behind its read-ahead tail lies
+//      a copy of the bias block with the folded biases in place (normal at BIAS_SIG + 1..3, dir_encoding at BIAS_DIR).
 //      The region is reserved at FOLD_REGION_PAIRS pairs, more than the stream needs: the image keeps its size and the device-state
 //      words at its end keep their offsets (shrinking it would move them and change the kernels' immediates).
 constexpr int FOLD_REGION_PAIRS = 1328;
-constexpr int SPLIT_FOLD_USED = 960 + 8 + 64 + 4 + 64 + 8 + 4;                                      // 1112
+constexpr int FOLD_POS_DIR = 960 + 8;                                                               // 968
+constexpr int FOLD_POS_VIEW = FOLD_POS_DIR + 64;                                                     // 1032
+constexpr int FOLD_POS_RGB = FOLD_POS_VIEW + 8;                                                      // 1040
+constexpr int FOLD_POS_MIR1 = FOLD_POS_RGB + 4;                                                      // 1044: end of the rgb / depth prefix
+constexpr int FOLD_POS_MIR2 = FOLD_POS_MIR1 + 64;                                                    // 1108
+constexpr int SPLIT_FOLD_USED = FOLD_POS_MIR2 + 4;                                                   // 1112
 constexpr int SPLIT_FOLD_PAIRS = padded_pairs(SPLIT_FOLD_USED);                                      // 1120
+static_assert(SPLIT_FOLD_USED == 960 + 8 + 64 + 4 + 64 + 8 + 4, "the folded stream holds every folded part once");
 constexpr int64_t OFF_FOLD_FWD = OFF_SPLIT_HBWD + (int64_t)SPLIT_HBWD_PAIRS * (PAIR_BYTES / 4);
 constexpr int64_t OFF_FOLD_BIAS = OFF_FOLD_FWD + (int64_t)SPLIT_FOLD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
 constexpr int64_t PACKED_FLOATS = OFF_FOLD_FWD + (int64_t)FOLD_REGION_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;

@@ -565,11 +565,16 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     # "any mirror pixel" flag (eval.py:303-312 branches on it): the GPU then never idles on that read.  Not used with the
     # roughness jitters, whose random draws would change order against the primary passes.
     def stage_a(rays_chunk, level, host_flags=None, slot=0):
+        # The last level of a recursion traces nothing: its caller (stage_b of the level above) reads rgb_* and depth_* of it
+        # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
+        # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
+        rgb_depth = 1 <= level == args.max_recursive_level and not rough
         r = render_rays(models, embeddings, rays_chunk, N_samples, use_disp, 0, 0, N_importance, chunk,
                         white_back, test_time=test_time,
                         compute_normal=trace_flag and (not args.predict_normal),
                         only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
-                        current_epoch=fine_epoch + 1, _guard=False, _maps_only=maps_only)
+                        current_epoch=fine_epoch + 1, _guard=False, _maps_only=maps_only or rgb_depth,
+                        _rgb_depth_only=rgb_depth)
         r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
         r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
         mask = None
@@ -621,7 +626,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                 r2 = render_rays(system_sub.models, system_sub.embeddings, sec.contiguous(), N_samples, use_disp, 0, 0,
                                  N_importance, chunk, white_back, test_time=test_time, compute_normal=False,
                                  only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
-                                 current_epoch=fine_epoch + 1, _guard=False, _maps_only=True)
+                                 current_epoch=fine_epoch + 1, _guard=False, _maps_only=True, _rgb_depth_only=True)
             else:
                 r2 = recurse(sec.contiguous(), level + 1)
             if rough:                                                     # eval.py:622-674

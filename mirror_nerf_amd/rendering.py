@@ -20,7 +20,10 @@ Differences from the reference that do not change values:
     the count alone; the result tensors have the capacity's shape, their rows past the count are undefined;
   * `_maps_only=True` (set by batched_inference for to_cpu="maps" / maps_only=True): in eval the final pass runs ray-fused --
     field evaluation + compositing in one kernel -- and the per-sample keys nobody downstream of eval.py:735-736 reads
-    (weights_*, pred_normal_*) are not produced; the per-ray maps are identical bit for bit.
+    (weights_*, pred_normal_*) are not produced; the per-ray maps are identical bit for bit.  With `_rgb_depth_only=True` as well
+    (set by batched_inference for a render of which only rgb_* / depth_* are read: the last reflection level, the substitution
+    render) that pass produces only opacity_*, rgb_*, depth_* and z_vals_*: the kernel skips the mirror head
+    (mnrf_field_composite_fused MNRF_FUSED_RGB_DEPTH); those maps are again identical bit for bit.
 Outputs live on rays.device.  When autograd is enabled and a model parameter (or `rays`) requires
 grad, the field evaluation and the compositing run through `autograd.FieldFn` / `CompositeFn`,
 whose backward passes are HIP kernels too (including the second-order term that reaches the
@@ -206,21 +209,26 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         from .weights import folded_of
         if _mn.precision_of(model) != "split" or z.shape[1] != L.mnrf_fused_samples_per_ray():
             return False
-        has_m, has_n = getattr(model, "predict_mirror_mask", True), getattr(model, "predict_normal", True)
-        opacity, rgb_map, depth, xs = f(N), f(N, 3), f(N), f(N, 3)
+        rgb_depth = bool(kwargs.get("_rgb_depth_only"))
+        has_m = not rgb_depth and getattr(model, "predict_mirror_mask", True)
+        has_n = not rgb_depth and getattr(model, "predict_normal", True)
+        opacity, rgb_map, depth = f(N), f(N, 3), f(N)
+        xs = None if rgb_depth else f(N, 3)
         mask = f(N) if has_m else None
         sn = f(N, 3) if has_n else None
+        flags = (_lib.MNRF_FUSED_WHITE_BACK if white_back else 0) | (_lib.MNRF_FUSED_RGB_DEPTH if rgb_depth else 0)
         if _mn.LAUNCH_LOG is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        rc = L.mnrf_field_composite_fused(p(folded_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], int(bool(white_back)),
+        rc = L.mnrf_field_composite_fused(p(folded_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], flags,
                                           None, p(opacity), p(rgb_map), p(depth), p(mask), p(sn), p(xs), _lib.stream())
         if rc == -3:          # MNRF_ERR_UNSUPPORTED: the 48-samples-per-wave tuning is switched off
             return False
         _lib.check(rc, "mnrf_field_composite_fused")
         if _mn.LAUNCH_LOG is not None:
             e1.record()
-            _mn.LAUNCH_LOG.append((_lib.MNRF_SPLIT_F16 | 0x2000, N * z.shape[1], e0, e1))     # 0x2000: ray-fused launch
+            # 0x2000: ray-fused launch, 0x4000: its rgb / depth variant
+            _mn.LAUNCH_LOG.append((_lib.MNRF_SPLIT_F16 | 0x2000 | (0x4000 if rgb_depth else 0), N * z.shape[1], e0, e1))
         results[f"opacity_{typ}"] = opacity
         results[f"z_vals_{typ}"] = z
         results[f"rgb_{typ}"] = rgb_map
@@ -229,7 +237,8 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
             results[f"mirror_mask_{typ}"] = mask
         if has_n:
             results[f"surface_normal_{typ}"] = sn
-        results[f"_x_surface_{typ}"] = xs
+        if xs is not None:
+            results[f"_x_surface_{typ}"] = xs
         return True
 
     def inference(model, typ, z, noise_key):
@@ -397,7 +406,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
     results.pop("_z_fine_fused", None)
     for typ in ("coarse", "fine"):                                        # rendering.py:362-367
         xs = results.pop(f"_x_surface_{typ}", None)
-        if f"depth_{typ}" in results:
+        if xs is not None and f"depth_{typ}" in results:
             results[f"x_surface_{typ}"] = xs
     # range guard of the split arithmetic (mirror_nerf.check_guard): a stand-alone call checks its own launches (one
     # 8-byte device->host read); the recursion drivers pass _guard=False and check once per frame / training forward

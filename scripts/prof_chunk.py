@@ -50,8 +50,11 @@ for _ in range(a.reps + 1):
             M.render_rays(models, emb, rays, 64, False, 0, 0, 128, test_time=True, compute_normal=False)
             if a.fused:         # the same chunk, final pass ray-fused (field + compositing in one kernel, no per-sample output)
                 M.render_rays(models, emb, rays, 64, False, 0, 0, 128, test_time=True, compute_normal=False, _maps_only=True)
+                # ... and its rgb / depth variant (the last reflection level of a frame: no mirror head)
+                M.render_rays(models, emb, rays, 64, False, 0, 0, 128, test_time=True, compute_normal=False, _maps_only=True,
+                              _rgb_depth_only=True)
 torch.cuda.synchronize()
-for flags, B, e0, e1 in MN.LAUNCH_LOG[(4 if a.fused else 2):]:
+for flags, B, e0, e1 in MN.LAUNCH_LOG[(6 if a.fused else 2):]:
     ms = e0.elapsed_time(e1)
     flop = B * (MN.FLOP_SIGMA if flags & 1 else MN.FLOP_FULL) + (B * MN.FLOP_GRAD if flags & 2 else 0)
     print(f"flags={flags} B={B} {ms:.3f} ms  {flop / ms / 1e9:.1f} TFLOP/s (algorithmic)")
