@@ -664,6 +664,65 @@ int mnrf_mse_blocks(void);
 int mnrf_mse_psnr(const float* pred, const float* gt, const unsigned char* mask, int64_t n, int per_mask,
                   float* partials, float* out, void* stream);
 
+/* ---- mesh extraction (extract_color_mesh.py): density grid, marching cubes, connected components, vertex colours.
+ * csrc/mnrf_mesh.hip.  As everywhere: caller-owned buffers, no device state, arguments validated before the GPU is touched. */
+
+/* The query points of the density volume, rows [start, start + count) of the reference's (N^3, 3) float32 tensor
+ * (extract_color_mesh.py:146-152): numpy.linspace(lo, hi, N) per axis in float64 (i * ((hi - lo) / (N - 1)) + lo, the
+ * last sample equal to hi), numpy.meshgrid(x, y, z) in its default "xy" order -- the flat index runs y, x, z from slow
+ * to fast -- then the cast to float32.  Bit-identical to that construction.  out: (count, 3). */
+int mnrf_grid_points(double x0, double x1, double y0, double y1, double z0, double z1, int n, int64_t start,
+                     int64_t count, float* out, void* stream);
+/* x = max(x, 0) in place (extract_color_mesh.py:185); a NaN stays a NaN. */
+int mnrf_clamp_zero(float* x, int64_t n, void* stream);
+
+/* Marching cubes over a C-ordered (nx, ny, nz) volume with welded vertices (one per crossed grid edge), in two phases so
+ * that the caller can allocate exact sizes:
+ *   blocks = mnrf_mc_blocks(nx, ny, nz);  mnrf_mc_count -> block_counts (blocks, 2) int32: per block of grid points in
+ *   flat order, the crossed edges its points own (+x, +y, +z of each point) and the triangles of the cells it owns (a cell
+ *   belongs to its lowest corner);  block_offsets = the EXCLUSIVE scan of block_counts along the blocks (the caller's; the
+ *   totals are the mesh's vertex and triangle counts);  mnrf_mc_emit -> vertices (n_vertices, 3) in index coordinates of
+ *   the volume and triangles (n_triangles, 3) int32.
+ * Conventions: a corner is inside <=> value >= threshold; an edge is crossed <=> its ends differ; the vertex lies at
+ * p0 + (threshold - s0) / (s1 - s0) from the edge's lower-index end p0; triangles are wound so that the geometric normal
+ * points towards lower values.  No atomics: the output order is the flat order of the volume, two runs are bit-identical.
+ * vertex_base: workspace of nx * ny * nz int32.  At most 2^30 grid points and 2^29 vertices.  Offsets that do not belong
+ * to this volume never make the launch write outside [0, n_vertices) / [0, n_triangles). */
+int64_t mnrf_mc_blocks(int nx, int ny, int nz);
+int mnrf_mc_count(const float* volume, int nx, int ny, int nz, float threshold, int32_t* block_counts, void* stream);
+int mnrf_mc_emit(const float* volume, int nx, int ny, int nz, float threshold, const int32_t* block_offsets,
+                 int32_t* vertex_base, int64_t n_vertices, int64_t n_triangles, float* vertices, int32_t* triangles,
+                 void* stream);
+/* One row of the 256-case triangle table (HOST call, no GPU): up to five triangles as edge numbers, -1 terminated.
+ * Corner c sits at offset (c & 1, (c >> 1) & 1, (c >> 2) & 1) and bit c of the case index is its inside flag; edge e
+ * runs along axis e / 4 from the corner at offsets (k & 1, k >> 1), k = e % 4, along the two other axes in increasing
+ * order.  The table is derived by scripts/gen_mc_table.py; ambiguous faces never join two inside corners. */
+int mnrf_mc_table(int case_index, int8_t* out16);
+
+/* Connected components of a triangle mesh by union-find over its vertices (hooking with an atomic min + pointer
+ * jumping): mnrf_cc_init sets labels[v] = v; each mnrf_cc_step hooks along every triangle, flattens, and stores 1 into
+ * *changed (device int32, zeroed by the caller) if it joined anything -- repeat until it stays 0; labels[v] is then the
+ * smallest vertex of v's component.  mnrf_cc_count adds, per triangle, 1 to counts[label of its first vertex]
+ * (counts: n_vertices int32, zeroed by the caller).  Triangles that index outside [0, n_vertices) are skipped. */
+int mnrf_cc_init(int32_t* labels, int64_t n_vertices, void* stream);
+int mnrf_cc_step(const int32_t* triangles, int64_t n_triangles, int32_t* labels, int64_t n_vertices, int32_t* changed,
+                 void* stream);
+int mnrf_cc_count(const int32_t* triangles, int64_t n_triangles, const int32_t* labels, int64_t n_vertices,
+                  int32_t* counts, void* stream);
+
+/* One view of the vertex colouring (extract_color_mesh.py:269-355).  mnrf_project_colors: project world-space vertices
+ * with the HOST matrices w2c (3x4 float64, row-major: the inverse of the camera-to-world pose) and K = [[focal, 0, W/2],
+ * [0, focal, H/2], [0, 0, 1]] in float64 (flip y/z, depth = z + 1e-5, pixel = float32(uv / depth) clipped to the image),
+ * sample image (H, W, 3) uint8 bilinearly in float -> colors (n, 3), depth (n) float64, and the occlusion rays (n, 8) =
+ * [origin, normalize(vertex - origin), near, far = depth].  mnrf_accumulate_colors: w = 0.1 / depth + (opacity <
+ * occ_threshold), color_sum += colors * w, weight_sum += w (float64; a NaN opacity counts as 0, as numpy.nan_to_num does
+ * the way the reference calls it). */
+int mnrf_project_colors(const float* vertices, int64_t n_vertices, const uint8_t* image, int H, int W,
+                        const double* w2c_host12, const float* origin_host3, float focal, float near, float* colors,
+                        double* depth, float* rays, void* stream);
+int mnrf_accumulate_colors(const float* colors, const double* depth, const float* opacity, float occ_threshold,
+                           int64_t n_vertices, double* color_sum, double* weight_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,19 @@ SIGNATURES = {
     "mnrf_adam_prep": (_int, [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_f, _c_f, ctypes.POINTER(ctypes.c_void_p), _int, _c_f, _str]),
     "mnrf_adam_step_dev": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _c_f, _c_i, _str]),
     "mnrf_adam_step_dev_n": (_int, [_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), _c_f, ctypes.POINTER(ctypes.c_void_p), _str]),
+    # ---- mesh extraction (csrc/mnrf_mesh.hip)
+    "mnrf_grid_points": (_int, [ctypes.c_double] * 6 + [_int, _i64, _i64, _c_f, _str]),
+    "mnrf_clamp_zero": (_int, [_c_f, _i64, _str]),
+    "mnrf_mc_blocks": (_i64, [_int, _int, _int]),
+    "mnrf_mc_count": (_int, [_c_f, _int, _int, _int, _flt, _c_i, _str]),
+    "mnrf_mc_emit": (_int, [_c_f, _int, _int, _int, _flt, _c_i, _c_i, _i64, _i64, _c_f, _c_i, _str]),
+    "mnrf_mc_table": (_int, [_int, ctypes.c_void_p]),
+    "mnrf_cc_init": (_int, [_c_i, _i64, _str]),
+    "mnrf_cc_step": (_int, [_c_i, _i64, _c_i, _i64, _c_i, _str]),
+    "mnrf_cc_count": (_int, [_c_i, _i64, _c_i, _i64, _c_i, _str]),
+    "mnrf_project_colors": (_int, [_c_f, _i64, ctypes.c_void_p, _int, _int, ctypes.POINTER(ctypes.c_double),
+                                   ctypes.POINTER(ctypes.c_float), _flt, _flt, _c_f, ctypes.c_void_p, _c_f, _str]),
+    "mnrf_accumulate_colors": (_int, [_c_f, ctypes.c_void_p, _c_f, _flt, _i64, ctypes.c_void_p, ctypes.c_void_p, _str]),
 }
 
 _lib = None
