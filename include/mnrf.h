@@ -723,6 +723,24 @@ int mnrf_project_colors(const float* vertices, int64_t n_vertices, const uint8_t
 int mnrf_accumulate_colors(const float* colors, const double* depth, const float* opacity, float occ_threshold,
                            int64_t n_vertices, double* color_sum, double* weight_sum, void* stream);
 
+/* Colouring along the vertex normals (extract_color_mesh.py --use_vertex_normal, lines 247-267 and 358-362).
+ * mnrf_vertex_normals: normals (n_vertices, 3) float32 = for every vertex the sum, over the triangles (a, b, c) that hold
+ * it, of the unnormalised (v_b - v_a) x (v_c - v_a) (float64 from the float32 vertices; so: area-weighted, direction by the
+ * winding as given), normalised in float64 and cast.  A vertex whose sum is zero (no triangle, only degenerate ones) or that
+ * shares a triangle with a non-finite vertex gets (0, 0, 1).  Deterministic and independent of the order of the triangles:
+ * the components are accumulated as 64-bit integers (vector-memory integer atomics) in steps of 2^-k, k chosen on the device
+ * from the largest cross-product component M of the mesh and the triangle count so that no sum can overflow; a step is at
+ * most M * 2^(b - 61), 3 * n_triangles < 2^b.  scratch: mnrf_vertex_normals_scratch_bytes(n_vertices) bytes, 8-byte aligned
+ * (zeroed by the call).  Triangles that index outside [0, n_vertices) are skipped.
+ * mnrf_normal_rays: rays (n, 8) = [v - (n * near) * near_t, n, near, far] in float32, each operation rounded on its own.
+ * mnrf_rgb_to_uint8: out[i] = the float32 product rgb[i] * 255 truncated towards zero (saturated to [0, 255], NaN -> 0). */
+int64_t mnrf_vertex_normals_scratch_bytes(int64_t n_vertices);
+int mnrf_vertex_normals(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                        void* scratch, float* normals, void* stream);
+int mnrf_normal_rays(const float* vertices, const float* normals, int64_t n_vertices, float near, float far, float near_t,
+                     float* rays, void* stream);
+int mnrf_rgb_to_uint8(const float* rgb, int64_t n, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ SIGNATURES = {
     "mnrf_project_colors": (_int, [_c_f, _i64, ctypes.c_void_p, _int, _int, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_float), _flt, _flt, _c_f, ctypes.c_void_p, _c_f, _str]),
     "mnrf_accumulate_colors": (_int, [_c_f, ctypes.c_void_p, _c_f, _flt, _i64, ctypes.c_void_p, ctypes.c_void_p, _str]),
+    "mnrf_vertex_normals_scratch_bytes": (_i64, [_i64]),
+    "mnrf_vertex_normals": (_int, [_c_f, _i64, _c_i, _i64, ctypes.c_void_p, _c_f, _str]),
+    "mnrf_normal_rays": (_int, [_c_f, _c_f, _i64, _flt, _flt, _flt, _c_f, _str]),
+    "mnrf_rgb_to_uint8": (_int, [_c_f, _i64, ctypes.c_void_p, _str]),
 }
 
 _lib = None

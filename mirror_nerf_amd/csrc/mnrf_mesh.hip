@@ -1,5 +1,6 @@
 // mnrf_mesh.hip -- mesh extraction on the device (extract_color_mesh.py): the grid-point generator of the density volume,
-// marching cubes with welded vertices, connected components of the mesh and the per-view colour projection.
+// marching cubes with welded vertices, connected components of the mesh, the per-view colour projection, and the colouring
+// along the vertex normals (area-weighted vertex normals, one ray per vertex, the uint8 cast).
 //
 // Marching cubes is memory-bound (one float of density per grid point, a few hundred thousand vertices out), so the kernels
 // keep no per-point intermediate but one: a point OWNS its +x, +y and +z edges, a cell is owned by its lowest corner, and
@@ -17,6 +18,7 @@
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
+#include "mnrf_fill.h"
 
 namespace {
 
@@ -367,6 +369,131 @@ __global__ __launch_bounds__(256) void accumulate_colors_kernel(const float* col
     weight_sum[i] = weight_sum[i] + w;
 }
 
+// ------------------------------------------------------------------------------------------------ vertex normals
+// normal(v) = normalise(sum over the triangles (a, b, c) that hold v of (v_b - v_a) x (v_c - v_a)), float64 from the float32
+// vertices.  The sum is order-free because it is an integer sum: every cross-product component is rounded to a multiple of
+// 2^-k and added as a 64-bit integer with a vector-memory atomic.  k comes from the mesh itself: M = the largest finite
+// |component| of any cross product (a first pass, an integer atomic max over the bits of the non-negative doubles), M < 2^e,
+// 3 T < 2^b contributions at most per accumulator, k = 62 - e - b, so |sum| < 2^62 and the rounding (half a step per
+// contribution) keeps it below 2^63.  One step is at most M * 2^(b - 61): with T = 2 M triangles 2^-38 of the largest cross
+// product.  A triangle with a non-finite corner marks its three vertices instead (finite float32 corners cannot overflow a
+// float64 cross product); those, and vertices whose sum is zero, get (0, 0, 1).
+struct NormalArgs {
+    const float* vertices;
+    long long n_vert;
+    const int32_t* tri;
+    long long n_tri;
+    long long* sums;                 // (n_vert, 3), zeroed
+    unsigned long long* max_bits;    // the bits of M, zeroed
+    uint32_t* marked;                // (n_vert), zeroed
+    int count_bits;                  // b
+};
+
+// false: the triangle indexes outside [0, n_vert) and is skipped
+__device__ inline bool vn_cross(const NormalArgs& A, long long t, int idx[3], double c[3]) {
+    idx[0] = A.tri[t * 3 + 0];
+    idx[1] = A.tri[t * 3 + 1];
+    idx[2] = A.tri[t * 3 + 2];
+    for (int q = 0; q < 3; ++q)
+        if (idx[q] < 0 || idx[q] >= A.n_vert) return false;
+    double p[3][3];
+    for (int q = 0; q < 3; ++q)
+        for (int a = 0; a < 3; ++a) p[q][a] = (double)A.vertices[(long long)idx[q] * 3 + a];
+    const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
+    const double wx = p[2][0] - p[0][0], wy = p[2][1] - p[0][1], wz = p[2][2] - p[0][2];
+    c[0] = uy * wz - uz * wy;
+    c[1] = uz * wx - ux * wz;
+    c[2] = ux * wy - uy * wx;
+    return true;
+}
+
+__device__ inline bool vn_finite(const double c[3]) { return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]); }
+
+// M: grid-stride over the triangles, one atomic per block
+__global__ __launch_bounds__(256) void vn_max_kernel(NormalArgs A) {
+    __shared__ double wave_max[4];
+    double m = 0.0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < A.n_tri; t += (long long)gridDim.x * blockDim.x) {
+        int idx[3];
+        double c[3];
+        if (!vn_cross(A, t, idx, c) || !vn_finite(c)) continue;
+        m = fmax(m, fmax(fabs(c[0]), fmax(fabs(c[1]), fabs(c[2]))));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmax(m, __shfl_xor(m, d));
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmax(fmax(wave_max[0], wave_max[1]), fmax(wave_max[2], wave_max[3]));
+        if (m > 0.0) atomicMax(A.max_bits, (unsigned long long)__double_as_longlong(m));
+    }
+}
+
+__global__ __launch_bounds__(256) void vn_accumulate_kernel(NormalArgs A) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= A.n_tri) return;
+    int idx[3];
+    double c[3];
+    if (!vn_cross(A, t, idx, c)) return;
+    if (!vn_finite(c)) {
+        for (int q = 0; q < 3; ++q) atomicOr(&A.marked[idx[q]], 1u);
+        return;
+    }
+    const double M = __longlong_as_double((long long)*A.max_bits);
+    if (!(M > 0.0)) return;      // every triangle is degenerate
+    int e;
+    frexp(M, &e);                // M = m * 2^e, 0.5 <= m < 1
+    const int k = 62 - e - A.count_bits;
+    for (int a = 0; a < 3; ++a) {
+        const long long q = __double2ll_rn(ldexp(c[a], k));
+        if (q == 0) continue;
+        for (int v = 0; v < 3; ++v)
+            atomicAdd((unsigned long long*)&A.sums[(long long)idx[v] * 3 + a], (unsigned long long)q);
+    }
+}
+
+__global__ __launch_bounds__(256) void vn_finish_kernel(NormalArgs A, float* normals) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n_vert) return;
+    const double sx = (double)A.sums[i * 3 + 0], sy = (double)A.sums[i * 3 + 1], sz = (double)A.sums[i * 3 + 2];
+    const double len = sqrt(sx * sx + sy * sy + sz * sz);      // (|s| < 2^62: the squares cannot overflow)
+    float n[3] = {0.f, 0.f, 1.f};
+    if (!A.marked[i] && len > 0.0) {
+        n[0] = (float)(sx / len);
+        n[1] = (float)(sy / len);
+        n[2] = (float)(sz / len);
+    }
+    normals[i * 3 + 0] = n[0];
+    normals[i * 3 + 1] = n[1];
+    normals[i * 3 + 2] = n[2];
+}
+
+// extract_color_mesh.py:250-253, 262 as torch evaluates it in float32: d = n, o = v - (d * near) * near_t, [o, d, near, far]
+__global__ __launch_bounds__(256) void normal_rays_kernel(const float* vertices, const float* normals, long long n, float near,
+                                                          float far, float near_t, float* rays) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float* r = rays + i * 8;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float d = normals[i * 3 + a];
+        const float step = d * near;
+        r[a] = vertices[i * 3 + a] - step * near_t;
+        r[3 + a] = d;
+    }
+    r[6] = near;
+    r[7] = far;
+}
+
+// extract_color_mesh.py:359-362: (rgb * 255.0).astype(uint8) -- the float32 product truncated towards zero.  Outside
+// [0, 256) numpy's cast is undefined; here the value saturates and a NaN becomes 0.
+__global__ __launch_bounds__(256) void rgb_to_uint8_kernel(const float* rgb, long long n, uint8_t* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = rgb[i] * 255.0f;
+    out[i] = v >= 255.f ? (uint8_t)255 : (v > 0.f ? (uint8_t)(int)v : (uint8_t)0);
+}
+
 int mc_check(const char* who, const float* volume, int nx, int ny, int nz, float threshold, long long* npts) {
     static thread_local char msg[160];
     if (nx < 2 || ny < 2 || nz < 2) {
@@ -533,4 +660,57 @@ extern "C" int mnrf_accumulate_colors(const float* colors, const double* depth, 
     hipLaunchKernelGGL(accumulate_colors_kernel, dim3(blocks_for(n_vertices, 256)), dim3(256), 0, (hipStream_t)stream, colors, depth,
                        opacity, occ_threshold, (long long)n_vertices, color_sum, weight_sum);
     return mnrf_check_launch("mnrf_accumulate_colors");
+}
+
+extern "C" int64_t mnrf_vertex_normals_scratch_bytes(int64_t n_vertices) {
+    if (n_vertices < 0 || n_vertices > MC_MAX_VERTICES)
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_vertex_normals_scratch_bytes: bad size (at most 2^29 vertices)");
+    return ((24 * n_vertices + 8 + 4 * n_vertices + 7) / 8) * 8;
+}
+
+extern "C" int mnrf_vertex_normals(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                                   void* scratch, float* normals, void* stream) {
+    if (n_vertices < 0 || n_vertices > MC_MAX_VERTICES || n_triangles < 0 || n_triangles > (1ll << 31) / 3)
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_vertex_normals: bad size (at most 2^29 vertices, 2^31 / 3 triangles)");
+    if (n_vertices == 0) return MNRF_OK;
+    if (!vertices || !scratch || !normals || (n_triangles > 0 && !triangles))
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_vertex_normals: null pointer");
+    if (((uintptr_t)scratch & 7u) != 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_vertex_normals: scratch must be 8-byte aligned");
+    NormalArgs A;
+    A.vertices = vertices;
+    A.n_vert = n_vertices;
+    A.tri = triangles;
+    A.n_tri = n_triangles;
+    A.sums = (long long*)scratch;
+    A.max_bits = (unsigned long long*)scratch + 3 * n_vertices;
+    A.marked = (uint32_t*)((unsigned long long*)scratch + 3 * n_vertices + 1);
+    A.count_bits = 0;
+    for (long long c = 3 * (long long)n_triangles; c > 0; c >>= 1) ++A.count_bits;      // 3 T < 2^count_bits
+    hipStream_t s = (hipStream_t)stream;
+    mnrf::zero_fill(s, scratch, (size_t)(24 * n_vertices + 8 + 4 * n_vertices));
+    if (n_triangles > 0) {
+        unsigned blocks = blocks_for(n_triangles, 256);
+        hipLaunchKernelGGL(vn_max_kernel, dim3(blocks > 1024u ? 1024u : blocks), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(vn_accumulate_kernel, dim3(blocks), dim3(256), 0, s, A);
+    }
+    hipLaunchKernelGGL(vn_finish_kernel, dim3(blocks_for(n_vertices, 256)), dim3(256), 0, s, A, normals);
+    return mnrf_check_launch("mnrf_vertex_normals");
+}
+
+extern "C" int mnrf_normal_rays(const float* vertices, const float* normals, int64_t n_vertices, float near, float far,
+                                float near_t, float* rays, void* stream) {
+    if (n_vertices < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_normal_rays: bad size");
+    if (n_vertices == 0) return MNRF_OK;
+    if (!vertices || !normals || !rays) return mnrf_fail(MNRF_ERR_ARG, "mnrf_normal_rays: null pointer");
+    hipLaunchKernelGGL(normal_rays_kernel, dim3(blocks_for(n_vertices, 256)), dim3(256), 0, (hipStream_t)stream, vertices, normals,
+                       (long long)n_vertices, near, far, near_t, rays);
+    return mnrf_check_launch("mnrf_normal_rays");
+}
+
+extern "C" int mnrf_rgb_to_uint8(const float* rgb, int64_t n, uint8_t* out, void* stream) {
+    if (n < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rgb_to_uint8: bad size");
+    if (n == 0) return MNRF_OK;
+    if (!rgb || !out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rgb_to_uint8: null pointer");
+    hipLaunchKernelGGL(rgb_to_uint8_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, rgb, (long long)n, out);
+    return mnrf_check_launch("mnrf_rgb_to_uint8");
 }

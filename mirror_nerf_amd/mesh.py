@@ -4,12 +4,14 @@
     vertices, triangles = marching_cubes(volume, threshold)                       # :189 (mcubes.marching_cubes)
     vertices, triangles = largest_component(vertices, triangles)                  # :220-224 (open3d clustering)
     colors = fuse_vertex_colors(world_vertices, model, embeddings, images, poses, focal, near, ...)      # :269-355
-    write_ply(path, world_vertices, triangles, colors)                            # :367-369 (plyfile)
+    colors = normal_vertex_colors(world_vertices, triangles, models, embeddings, near, far)              # :247-267, 358-359
+    normals = vertex_normals(world_vertices, triangles)                           # :249 (open3d compute_vertex_normals)
+    write_ply(path, world_vertices, triangles, colors, normals)                   # :367-369 (plyfile)
 
 `extract_mesh` chains the first three and maps the vertices to world coordinates.  The arithmetic runs in
 csrc/mnrf_mesh.hip and the field kernels (include/mnrf.h); this module allocates, scans the per-block counts
-(torch.cumsum), compacts (boolean indexing) and writes files.  Datasets are out of scope: images and poses come from the
-caller.  The `--use_vertex_normal` colouring is not provided (it depends on the winding of `mcubes`).
+(torch.cumsum), compacts (boolean indexing) and writes files.  Datasets are out of scope: the images and poses of `fuse_vertex_colors` come
+from the caller; `normal_vertex_colors` (the reference's `--use_vertex_normal`) needs the two models only.
 """
 import ctypes
 
@@ -319,20 +321,131 @@ def occlusion_opacity(model, embeddings, rays, N_samples=64, white_back=False, c
     return torch.cat(out, 0).float().contiguous() if out else torch.empty(0, device=rays.device)
 
 
+# ----------------------------------------------------------------------------------------------- colours along the normals
+def _check_mesh(vertices, triangles):
+    if not vertices.is_cuda or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError("vertices must be a (V, 3) float32 tensor on the GPU")
+    if not triangles.is_cuda or triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise RuntimeError("triangles must be a (T, 3) int32 tensor on the GPU")
+
+
+def vertex_normals(vertices, triangles):
+    """Unit vertex normals (V, 3) float32 on the device: for every triangle (a, b, c) the unnormalised cross product
+    (v_b - v_a) x (v_c - v_a) in float64, summed per vertex (so: weighted by area), normalised in float64, cast.  What
+    open3d's compute_vertex_normals is believed to do (extract_color_mesh.py:249; open3d is not available to compare with).
+    A vertex without a triangle, or with degenerate ones only, gets (0, 0, 1).  The direction follows the winding as
+    given: for the meshes of `extract_mesh` it points towards HIGHER density, in both spacing modes.  Deterministic, and
+    independent of the order of the triangle array (64-bit fixed-point sums, include/mnrf.h)."""
+    _check_mesh(vertices, triangles)
+    vertices, triangles = vertices.contiguous(), triangles.contiguous()
+    V, T, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    L, p = _lib.lib(), _lib.ptr
+    with torch.cuda.device(dev):
+        nbytes = L.mnrf_vertex_normals_scratch_bytes(V)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "mnrf_vertex_normals_scratch_bytes")
+        scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        _lib.check(L.mnrf_vertex_normals(p(vertices), V, p(triangles) if T else None, T, p(scratch) if V else None, p(normals),
+                                         _lib.stream()), "mnrf_vertex_normals")
+    return normals
+
+
+def normal_rays(vertices, normals, near, far, near_t=1.0):
+    """One ray per vertex along its normal, (V, 8) float32 [o, d, near, far] with d = n and o = v - (d * near) * near_t:
+    extract_color_mesh.py:250-253, 262 as torch evaluates it in float32 (bit-equal to that expression on the CPU)."""
+    if not vertices.is_cuda or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError("vertices must be a (V, 3) float32 tensor on the GPU")
+    if not normals.is_cuda or normals.dtype != torch.float32 or normals.shape != vertices.shape:
+        raise RuntimeError("normals must be a float32 tensor of the vertices' shape on the GPU")
+    vertices, normals = vertices.contiguous(), normals.contiguous()
+    V, dev = int(vertices.shape[0]), vertices.device
+    with torch.cuda.device(dev):
+        rays = torch.empty(V, 8, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().mnrf_normal_rays(_lib.ptr(vertices), _lib.ptr(normals), V, float(near), float(far), float(near_t),
+                                               _lib.ptr(rays), _lib.stream()), "mnrf_normal_rays")
+    return rays
+
+
+def rgb_to_uint8(rgb):
+    """`(rgb * 255.0).astype(np.uint8)` of extract_color_mesh.py:359-362 on the device: the float32 product truncated
+    towards zero.  Where numpy's cast is undefined the value saturates to [0, 255] and a NaN becomes 0."""
+    if not rgb.is_cuda or rgb.dtype != torch.float32:
+        raise RuntimeError("rgb must be a float32 tensor on the GPU")
+    rgb = rgb.contiguous()
+    with torch.cuda.device(rgb.device):
+        out = torch.empty(rgb.shape, dtype=torch.uint8, device=rgb.device)
+        _lib.check(_lib.lib().mnrf_rgb_to_uint8(_lib.ptr(rgb), rgb.numel(), _lib.ptr(out), _lib.stream()), "mnrf_rgb_to_uint8")
+    return out
+
+
+def normal_vertex_colors(vertices, triangles, models, embeddings, near, far, near_t=1.0, N_samples=64, N_importance=128,
+                         white_back=False, chunk=32 * 1024, normals=None, return_rgb=False):
+    """Vertex colours (V, 3) uint8 by the reference's `--use_vertex_normal` method (extract_color_mesh.py:247-267, 358-362):
+    one ray per vertex that starts `near * near_t` in front of it and travels along the vertex normal, rendered by
+    `render_rays(models, ..., N_samples, False, 0, 0, N_importance, chunk, white_back, test_time=True)` in chunks;
+    `rgb_fine * 255`, truncated, is the colour.  Needs nothing but the two models.
+
+    models: {"coarse": ..., "fine": ...}; near, far: the bounds of the rays (the reference's dataset.bounds).  The ray must
+    run from the outside into the surface, so the normals must point towards higher density: the winding of `extract_mesh`.
+    normals: None computes them with `vertex_normals`; a (V, 3) float32 tensor is used as it is.
+    Of the render only `rgb_fine` is read, so MirrorNeRF models go through the ray-fused colour / depth pass of render_rays
+    (nothing per sample reaches memory; the same map bit for bit as the two-kernel route); that pass, like every forward-only
+    one, does not evaluate the density-gradient normals the reference's call computes and discards, whose kernel rounds
+    rgb differently by ~1e-6.  The fused pass exists for N_samples + N_importance = 192 samples per ray
+    (mnrf_fused_samples_per_ray) in the split arithmetic; any other sample count, and the fp32 arithmetic, take the
+    two-kernel route of render_rays with the same values.  The range guard of the split arithmetic is checked once over all
+    chunks.  MirrorNeRFTcnn models take render_rays as it is.  The Whitted recursion is not traced: a mirror's
+    vertices get the mirror's direct colour, as in the reference.  return_rgb: also return the float32 `rgb_fine` (V, 3)."""
+    from .rendering import render_rays
+    if "coarse" not in models or "fine" not in models:
+        raise ValueError('models must hold "coarse" and "fine"')
+    if int(N_importance) < 1:
+        raise ValueError("N_importance must be positive: the colour is rgb_fine")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    _check_mesh(vertices, triangles)
+    if normals is None:
+        normals = vertex_normals(vertices, triangles)
+    rays = normal_rays(vertices, normals, near, far, near_t)
+    V, dev = int(rays.shape[0]), rays.device
+    hashgrid = isinstance(models["coarse"], MirrorNeRFTcnn)
+    extra = {} if hashgrid else dict(compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
+    with torch.cuda.device(dev), torch.no_grad():
+        while True:
+            out = [render_rays(models, embeddings, rays[i:i + chunk], N_samples, False, 0, 0, N_importance, chunk, white_back,
+                               test_time=True, **extra)["rgb_fine"] for i in range(0, V, chunk)]
+            # range guard of the split arithmetic: a trip switches the models to the exact kernels; render again
+            if hashgrid or not V or not _mn.check_guard(list(models.values())):
+                break
+        if not hashgrid and V:
+            _mn.release_transient(list(models.values()))
+        rgb = torch.cat(out, 0).float().contiguous() if out else torch.empty(0, 3, dtype=torch.float32, device=dev)
+        colors = rgb_to_uint8(rgb)
+    return (colors, rgb) if return_rgb else colors
+
+
 # ----------------------------------------------------------------------------------------------- PLY
 def _host(a, dtype):
     a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     return np.ascontiguousarray(a.astype(dtype, copy=False))
 
 
-def write_ply(path, vertices, triangles, colors=None):
-    """Binary little-endian PLY: vertex x y z (float) [red green blue (uchar)], face vertex_indices (uchar count + 3 int).
-    The layout plyfile / open3d write for the reference's meshes; plain numpy."""
+def write_ply(path, vertices, triangles, colors=None, normals=None):
+    """Binary little-endian PLY: vertex x y z (float) [nx ny nz (float)] [red green blue (uchar)], face vertex_indices
+    (uchar count + 3 int).  The layout plyfile / open3d write for the reference's meshes; plain numpy."""
     v = _host(vertices, "<f4").reshape(-1, 3)
     t = _host(triangles, "<i4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}",
               "property float x", "property float y", "property float z"]
+    if normals is not None:
+        n = _host(normals, "<f4").reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"{len(v)} vertices but {len(n)} normals")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = _host(colors, "u1").reshape(-1, 3)
         if len(c) != len(v):
@@ -342,6 +455,8 @@ def write_ply(path, vertices, triangles, colors=None):
     header += [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
     vert = np.empty(len(v), dtype=fields)
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(len(t), dtype=[("n", "u1"), ("vertex_indices", "<i4", (3,))])
@@ -353,9 +468,10 @@ def write_ply(path, vertices, triangles, colors=None):
         f.write(face.tobytes())
 
 
-def read_ply(path):
-    """Reads what write_ply wrote (binary little-endian, float xyz, optional uchar rgb, triangles as `uchar int` lists):
-    (vertices (V, 3) float32, triangles (T, 3) int32, colors (V, 3) uint8 or None)."""
+def read_ply(path, return_normals=False):
+    """Reads what write_ply wrote (binary little-endian, float xyz, optional float normals, optional uchar rgb, triangles as
+    `uchar int` lists): (vertices (V, 3) float32, triangles (T, 3) int32, colors (V, 3) uint8 or None), and with
+    return_normals=True the normals (V, 3) float32 or None as a fourth value."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -371,11 +487,15 @@ def read_ply(path):
         elif w[:1] == ["property"]:
             props[cur].append(tuple(w[1:]))
     want = [("float", "x"), ("float", "y"), ("float", "z")]
+    nrm = [("float", "nx"), ("float", "ny"), ("float", "nz")]
     rgb = [("uchar", "red"), ("uchar", "green"), ("uchar", "blue")]
-    has_color = props.get("vertex") == want + rgb
-    if props.get("vertex") not in (want, want + rgb) or props.get("face") != [("list", "uchar", "int", "vertex_indices")]:
+    layouts = [(want + (nrm if n else []) + (rgb if c else []), n, c) for n in (False, True) for c in (False, True)]
+    found = [(n, c) for layout, n, c in layouts if props.get("vertex") == layout]
+    if not found or props.get("face") != [("list", "uchar", "int", "vertex_indices")]:
         raise ValueError(f"{path}: unsupported PLY layout")
-    vdt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if has_color else []))
+    has_normal, has_color = found[0]
+    vdt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if has_normal else [])
+                   + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if has_color else []))
     fdt = np.dtype([("n", "u1"), ("vertex_indices", "<i4", (3,))])
     nv, nf = counts["vertex"], counts["face"]
     if len(data) != end + nv * vdt.itemsize + nf * fdt.itemsize:
@@ -386,4 +506,7 @@ def read_ply(path):
         raise ValueError(f"{path}: only triangles are supported")
     vertices = np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float32)
     colors = np.stack([vert["red"], vert["green"], vert["blue"]], 1).astype(np.uint8) if has_color else None
-    return vertices, face["vertex_indices"].astype(np.int32).reshape(-1, 3), colors
+    out = (vertices, face["vertex_indices"].astype(np.int32).reshape(-1, 3), colors)
+    if return_normals:
+        out += (np.stack([vert["nx"], vert["ny"], vert["nz"]], 1).astype(np.float32) if has_normal else None,)
+    return out

@@ -6,7 +6,9 @@
 Milliseconds from torch.cuda.Event pairs on the launching stream, the median of `repeats` runs after `warmup` untimed
 ones: the density grid (grid points + sigma-only field + clamp), marching cubes split into count, scan (torch.cumsum of
 the per-block counts, with the host read of the totals) and emit, the connected components (labels, counts, compaction)
-and one view of the colour fusion (projection, the occlusion render and the accumulation).  `mc_bytes_per_s`: the bytes
+one view of the colour fusion (projection, the occlusion render and the accumulation), the vertex normals of the largest
+component, and its colouring along those normals (rays, the 64 + 128-sample render with the coarse and the fine model, the
+uint8 cast; `normal_colors_rays_per_s`: vertices over that time).  `mc_bytes_per_s`: the bytes
 count + emit must move -- the volume once for each of the three launches, the vertex-base array written once, the
 vertices and triangles written once -- over their time.  `mc_over_sigma`: (count + scan + emit) / grid sigma.
 """
@@ -39,6 +41,9 @@ def main():
     model = M.MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=True, predict_mirror_mask=True)
     model.load_state_dict({k[len("fine__"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("fine__")})
     model = model.to(dev)
+    coarse = M.MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=True, predict_mirror_mask=True)
+    coarse.load_state_dict({k[len("coarse__"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("coarse__")})
+    coarse = coarse.to(dev)
     emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
     N, box = args.N, ((-1.5, 1.5), (-1.5, 1.5), (-0.3, 1.7))
     H = W = 400
@@ -65,11 +70,16 @@ def main():
         e4 = ev()
         mesh.fuse_vertex_colors(world, model, emb, image, pose, focal, 0.05)
         e5 = ev()
+        normals = mesh.vertex_normals(world, lt)
+        e6 = ev()
+        mesh.normal_vertex_colors(world, lt, {"coarse": coarse, "fine": model}, emb, 0.05, 8.0, normals=normals)
+        e7 = ev()
         torch.cuda.synchronize()
         marks = dict(tm["events"])
         row = dict(grid_sigma_ms=e0.elapsed_time(e1), count_ms=marks["start"].elapsed_time(marks["count"]),
                    scan_ms=marks["count"].elapsed_time(marks["scan"]), emit_ms=marks["scan"].elapsed_time(marks["emit"]),
-                   components_ms=e2.elapsed_time(e3), color_view_ms=e4.elapsed_time(e5))
+                   components_ms=e2.elapsed_time(e3), color_view_ms=e4.elapsed_time(e5),
+                   vertex_normals_ms=e5.elapsed_time(e6), normal_colors_ms=e6.elapsed_time(e7))
         sizes = dict(vertices=int(v.shape[0]), triangles=int(t.shape[0]), largest_vertices=int(lv.shape[0]),
                      largest_triangles=int(lt.shape[0]))
         if it >= args.warmup:
@@ -81,7 +91,8 @@ def main():
                 warmup=args.warmup, **{k: round(x, 4) for k, x in med.items()}, **spread, **sizes, mc_bytes=mc_bytes,
                 mc_bytes_per_s=mc_bytes / ((med["count_ms"] + med["emit_ms"]) * 1e-3),
                 mc_over_sigma=(med["count_ms"] + med["scan_ms"] + med["emit_ms"]) / med["grid_sigma_ms"],
-                sigma_evals_per_s=N ** 3 / (med["grid_sigma_ms"] * 1e-3), color_view_image=[H, W])
+                sigma_evals_per_s=N ** 3 / (med["grid_sigma_ms"] * 1e-3), color_view_image=[H, W],
+                normal_colors_rays_per_s=sizes["largest_vertices"] / (med["normal_colors_ms"] * 1e-3), normal_colors_samples=[64, 128])
     text = json.dumps(line)
     print(text)
     if args.out:
