@@ -664,6 +664,24 @@ int mnrf_mse_blocks(void);
 int mnrf_mse_psnr(const float* pred, const float* gt, const unsigned char* mask, int64_t n, int per_mask,
                   float* partials, float* out, void* stream);
 
+/* Structural similarity on the device (csrc/mnrf_metrics.hip): out[f] = the mean over channels, rows and columns of
+ *   S = ((2 ux uy + c1)(2 sxy + c2)) / ((ux^2 + uy^2 + c1)(sx + sy + c2)),   s.. = cov_norm * (E[..] - u. u.),
+ * where ux, uy, E[x^2], E[y^2], E[xy] are the means of frame f of pred and gt under the separable window
+ * taps (x) taps (HOST array of 2 * radius + 1 doubles, radius 0..5).  reflect == 0: the border is cropped, S exists
+ * where the window fits (H - 2 radius rows, W - 2 radius columns: scikit-image's structural_similarity, whose crop equals
+ * the window radius); reflect != 0: the images are padded as torch's "reflect" does (index -1 -> 1) and S exists at every
+ * pixel (kornia's ssim).  Both images are read in place: element (x, y, channel, frame) of pred lies at
+ * pred[x * s[0] + y * s[1] + channel * s[2] + frame * s[3]] with s = pred_strides4 (HOST array, in elements), likewise gt.
+ * Moments and S are evaluated in float64 from the float32 inputs.  map: null, or (frames, channels, rows, columns) float32
+ * receiving S.  partials: mnrf_ssim_blocks(H, W, frames, channels) doubles of workspace -- one per 32 x 16 tile of the H x W
+ * image, channel and frame, an upper bound on what a launch writes for any radius and border rule (the output of a cropped
+ * border is smaller and may take fewer tiles); 0 for a non-positive argument.  No atomics: deterministic, and
+ * out[f] does not depend on the other frames.  H and W must hold a window, frames and channels must be positive. */
+int64_t mnrf_ssim_blocks(int H, int W, int frames, int channels);
+int mnrf_ssim(const float* pred, const int64_t* pred_strides4, const float* gt, const int64_t* gt_strides4, int H, int W,
+              int channels, int frames, const double* taps, int radius, int reflect, double cov_norm, double c1, double c2,
+              double* partials, float* out, float* map, void* stream);
+
 /* ---- mesh extraction (extract_color_mesh.py): density grid, marching cubes, connected components, vertex colours.
  * csrc/mnrf_mesh.hip.  As everywhere: caller-owned buffers, no device state, arguments validated before the GPU is touched. */
 

@@ -120,6 +120,10 @@ SIGNATURES = {
     "mnrf_loss_count": (_int, [ctypes.c_void_p, _c_f, _str]),
     "mnrf_mse_blocks": (_int, []),
     "mnrf_mse_psnr": (_int, [_c_f, _c_f, ctypes.c_void_p, _i64, _int, _c_f, _c_f, _str]),
+    "mnrf_ssim_blocks": (_i64, [_int, _int, _int, _int]),
+    "mnrf_ssim": (_int, [_c_f, ctypes.POINTER(ctypes.c_int64), _c_f, ctypes.POINTER(ctypes.c_int64), _int, _int, _int, _int,
+                         ctypes.POINTER(ctypes.c_double), _int, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                         ctypes.c_void_p, _c_f, _c_f, _str]),
     # ---- live row counts on the device (round 5): the namesake's arguments + n_live (device int32) in front of the stream
     "mnrf_embed_n": (_int, [_c_f, _i64, _int, _int, _c_f, _c_i, _str]),
     "mnrf_embed_backward_n": (_int, [_c_f, _c_f, _i64, _int, _int, _c_f, _c_i, _str]),
