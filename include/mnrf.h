@@ -759,6 +759,37 @@ int mnrf_normal_rays(const float* vertices, const float* normals, int64_t n_vert
                      float* rays, void* stream);
 int mnrf_rgb_to_uint8(const float* rgb, int64_t n, uint8_t* out, void* stream);
 
+/* ---- the ray bank (csrc/mnrf_bank.hip): training batches from frames that stay on the device as decoded bytes
+ * (datasets/blender.py:51-108, 159-168, 191-204 without the 48 B per ray of host float arrays and without the DataLoader).
+ * All arrays are DEVICE memory of the caller; the struct itself is host memory, read during the call.  N = slots * H * W;
+ * a global index g addresses slot g / (H*W) and pixel g % (H*W), a slot being frame `slot`, or frames[slot] when a frame
+ * list is given (the reference's *_wmask subset: slots counts its entries; without a list slots == n_frames). */
+typedef struct {
+    const float* poses;       /* (n_frames, 3, 4) camera-to-world */
+    const uint8_t* images;    /* (n_frames, H, W, channels) */
+    const int8_t* masks;      /* (n_frames, H, W): -1 = no ground-truth mask for the frame, 0, 1 */
+    const int32_t* frames;    /* (slots) frame numbers, or null */
+    int n_frames, H, W, channels, slots;
+    float focal, near, far;
+} MnrfBank;
+/* Row k of the outputs for pixel indices[k] (device int64), or for start + k when indices is null (start .. start + n must
+ * lie inside the bank: how a whole frame is read).  rays (n, 8): bit-identical to the same pixel of mnrf_generate_rays;
+ * rgbs (n, 3): float(v) / 255.0f, with four channels rgb * a + (1 - a) as separate fp32 operations; mirror_mask (n): the
+ * int8 as a float; valid_mask (n) bytes: last channel > 0.  Any output may be null.  An index outside [0, N), or a frame
+ * number outside [0, n_frames), reads nothing: its row is NaN (valid 0).  n == 0 is a no-op. */
+int mnrf_bank_gather(const MnrfBank* bank, const int64_t* indices, int64_t start, int64_t n, float* rays, float* rgbs,
+                     float* mirror_mask, uint8_t* valid_mask, void* stream);
+/* The same outputs for the `batch` pixels of one step of a shuffled stream that visits every pixel once per epoch.  Lane l of
+ * `rank` in `world` at step s = step + (step_dev ? *step_dev : 0) (step_dev: device int64, so that a captured graph can
+ * replay the draw and advance the word) takes stream position p = (s * world + rank) * batch + l, epoch = p / N, i = p % N
+ * and pixel g = perm(seed, epoch)(i); indices_out (batch) int64 receives g when not null.  perm is a six-round balanced
+ * Feistel network over 2 * ceil(max(2, bit_length(N - 1)) / 2) bits with cycle walking; the mixer and the key schedule are
+ * stated in the header comment of csrc/mnrf_bank.hip and are part of the contract: a (seed, step, rank, world, batch)
+ * names the same pixels on every build.  N >= 2^32 is refused (before any pointer is looked at).  batch == 0 is a no-op. */
+int mnrf_bank_draw(const MnrfBank* bank, uint64_t seed, int64_t step, const int64_t* step_dev, int rank, int world,
+                   int64_t batch, float* rays, float* rgbs, float* mirror_mask, uint8_t* valid_mask, int64_t* indices_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ rendering hot path behind the reference's own Python interfaces.
     from mirror_nerf_amd import render_rays, MirrorNeRF, Embedding      # models/rendering.py, models/mirror_nerf.py
     from mirror_nerf_amd import NeRFSystem, batched_inference          # train.py:102-348, eval.py:114-740
     from mirror_nerf_amd import get_loss                                # losses.py:258 (TotalLoss, fused value + gradient)
+    from mirror_nerf_amd import RayBank, read_blender                   # datasets/blender.py: training batches drawn on the device
 
 All arithmetic runs in libmnrf_hip.so (include/mnrf.h).  There is no CPU fallback.
 """
@@ -12,7 +13,8 @@ from .mirror_nerf_tcnn import MirrorNeRFTcnn  # noqa: F401
 from .rendering import render_rays, sample_pdf  # noqa: F401
 from .recursion import NeRFSystem, batched_inference, render_rays_chunk_recursively  # noqa: F401
 from .losses import TotalLoss, get_loss  # noqa: F401
+from .data import RayBank, read_blender  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["Embedding", "MirrorNeRF", "render_rays", "sample_pdf", "NeRFSystem", "batched_inference",
-           "render_rays_chunk_recursively", "TotalLoss", "get_loss"]
+           "render_rays_chunk_recursively", "TotalLoss", "get_loss", "RayBank", "read_blender"]

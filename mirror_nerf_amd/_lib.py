@@ -174,6 +174,10 @@ SIGNATURES = {
     "mnrf_vertex_normals": (_int, [_c_f, _i64, _c_i, _i64, ctypes.c_void_p, _c_f, _str]),
     "mnrf_normal_rays": (_int, [_c_f, _c_f, _i64, _flt, _flt, _flt, _c_f, _str]),
     "mnrf_rgb_to_uint8": (_int, [_c_f, _i64, ctypes.c_void_p, _str]),
+    # ---- the ray bank (csrc/mnrf_bank.hip); the first argument is a const MnrfBank* (data._Bank)
+    "mnrf_bank_gather": (_int, [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _c_f, _c_f, _c_f, ctypes.c_void_p, _str]),
+    "mnrf_bank_draw": (_int, [ctypes.c_void_p, ctypes.c_uint64, _i64, ctypes.c_void_p, _int, _int, _i64, _c_f, _c_f, _c_f,
+                              ctypes.c_void_p, ctypes.c_void_p, _str]),
 }
 
 _lib = None

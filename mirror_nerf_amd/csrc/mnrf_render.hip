@@ -13,6 +13,7 @@
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
 #include "mnrf_fill.h"
+#include "mnrf_rays.h"
 
 // ------------------------------------------------------------------ error plumbing
 static thread_local char g_err[512] = "";
@@ -609,18 +610,7 @@ struct Pose { float m[12]; };
 __global__ void generate_rays_kernel(int H, int W, float focal, Pose c2w, float near, float far, float* __restrict__ rays) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (long long)H * W) return;
-    const int i = (int)(p % W), j = (int)(p / W);
-    const float dx = ((float)i - (float)W / 2.f) / focal;   // no +0.5 (ray_utils.py:19-24)
-    const float dy = -((float)j - (float)H / 2.f) / focal;
-    const float dz = -1.f;
-    float d[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] = dx * c2w.m[r * 4] + dy * c2w.m[r * 4 + 1] + dz * c2w.m[r * 4 + 2];
-    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    float* o = rays + p * 8;
-    o[0] = c2w.m[3]; o[1] = c2w.m[7]; o[2] = c2w.m[11];
-    o[3] = d[0] / nrm; o[4] = d[1] / nrm; o[5] = d[2] / nrm;
-    o[6] = near; o[7] = far;
+    mnrf_pinhole_ray((int)(p % W), (int)(p / W), H, W, focal, c2w.m, near, far, rays + p * 8);   // mnrf_rays.h: the ray bank's too
 }
 
 // ------------------------------------------------------------------ backward of the per-ray glue (training)
