@@ -790,6 +790,54 @@ int mnrf_bank_draw(const MnrfBank* bank, uint64_t seed, int64_t step, const int6
                    int64_t batch, float* rays, float* rgbs, float* mirror_mask, uint8_t* valid_mask, int64_t* indices_out,
                    void* stream);
 
+/* ---- the output stage of eval.py (csrc/mnrf_frames.hip; eval.py:743-978, utils/visualization.py:10-23, 208-221): the
+ * 8-bit images of a rendered frame from its float32 maps, which stay where batched_inference left them.  Two launches per
+ * frame (extrema, finish), no host read between or after them.  The expressions, the cast and the reduction are stated in
+ * the header comment of csrc/mnrf_frames.hip; every byte is what numpy gives for the reference's expression.
+ * A null map or a null image skips that image.  Every image is (n, 3) bytes, the reference's (H, W, 3). */
+typedef struct {
+    const float* rgb;                  /* (n, 3) */
+    const float* mirror_mask;          /* (n) */
+    const float* depth;                /* (n) */
+    const float* depth_reflect;        /* (n); its image also needs mirror_mask */
+    const float* surface_normal;       /* (n, 3) */
+    const float* surface_normal_grad;  /* (n, 3) */
+    const float* x_surface;            /* (n, 3) */
+} MnrfFrameMaps;
+typedef struct {
+    uint8_t* rgb;
+    uint8_t* mirror_mask;
+    uint8_t* depth;
+    uint8_t* depth_reflect;
+    uint8_t* surface_normal;
+    uint8_t* surface_normal_grad;
+    uint8_t* x_surface;
+} MnrfFrameImages;
+/* Sizes, in floats, of a frame's stats block and of the split-wide running block.
+ * The stats block: [0], [1] min and max of nan_to_num(depth); [2], [3] of nan_to_num(depth_reflect); [4], [5] of x_surface
+ * over its three channels (a NaN makes both NaN, as torch.min does); the rest is the reduction's own state, which must be
+ * ZERO before the first launch on a block and is left zero by every launch.  A null map leaves NaN in its entries.
+ * The running block: min and max of the raw depth, then of the raw reflected depth, over every frame folded into it: a
+ * frame's np.min / np.max replaces the entry when it is smaller / larger (eval.py:776-785); a frame that holds a NaN has NaN
+ * extremes and changes nothing, an infinity counts.  The caller resets the block to (+inf, -inf, +inf, -inf). */
+int mnrf_frame_stats_floats(void);
+int mnrf_split_extrema_floats(void);
+/* The extremes of one frame into `stats`, and its raw depth extremes folded into `running` (null: not folded).  Any map may
+ * be null.  Deterministic: integer atomics on an order-preserving image of the floats.  n == 0 is a no-op. */
+int mnrf_frame_extrema(const float* depth, const float* depth_reflect, const float* x_surface, int64_t n, float* stats,
+                       float* running, void* stream);
+/* Every image whose map and output are both given, in one launch; `stats` as the extrema launch left it on the same stream;
+ * table: (256, 3) bytes on the device, the colour of depth index k in the channel order it is to be stored in (required
+ * when a depth image is asked for).  The maps are only read. */
+int mnrf_frame_finish(const MnrfFrameMaps* maps, const MnrfFrameImages* images, int64_t n, const float* stats,
+                      const uint8_t* table, void* stream);
+/* The depth colour map of a stack of resident maps, depth (frames, n) -> out (frames, n, 3), in one launch.  extrema: two
+ * device floats (vmin, vmax) for every frame -- a pair of the running block for save_depth_unified_normalization -- or null
+ * for each frame's own extremes, which one more launch then reduces into `stats` (frames stats blocks, zero before first
+ * use).  mask (frames, n) or null: the reflected variant, the colour multiplied by clip(mask, 0, 1). */
+int mnrf_depth_colormap(const float* depth, const float* mask, int64_t frames, int64_t n, const float* extrema, float* stats,
+                        const uint8_t* table, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ rendering hot path behind the reference's own Python interfaces.
     from mirror_nerf_amd import NeRFSystem, batched_inference          # train.py:102-348, eval.py:114-740
     from mirror_nerf_amd import get_loss                                # losses.py:258 (TotalLoss, fused value + gradient)
     from mirror_nerf_amd import RayBank, read_blender                   # datasets/blender.py: training batches drawn on the device
+    from mirror_nerf_amd import finish_frame, SplitExtrema, colormap_depth   # eval.py:743-978: the 8-bit images of a frame
 
 All arithmetic runs in libmnrf_hip.so (include/mnrf.h).  There is no CPU fallback.
 """
@@ -14,7 +15,10 @@ from .rendering import render_rays, sample_pdf  # noqa: F401
 from .recursion import NeRFSystem, batched_inference, render_rays_chunk_recursively  # noqa: F401
 from .losses import TotalLoss, get_loss  # noqa: F401
 from .data import RayBank, read_blender  # noqa: F401
+from . import frames  # noqa: F401
+from .frames import SplitExtrema, colormap_depth, finish_frame, jet_table  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["Embedding", "MirrorNeRF", "render_rays", "sample_pdf", "NeRFSystem", "batched_inference",
-           "render_rays_chunk_recursively", "TotalLoss", "get_loss", "RayBank", "read_blender"]
+           "render_rays_chunk_recursively", "TotalLoss", "get_loss", "RayBank", "read_blender", "frames", "finish_frame", "SplitExtrema",
+           "colormap_depth", "jet_table"]

@@ -178,6 +178,12 @@ SIGNATURES = {
     "mnrf_bank_gather": (_int, [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _c_f, _c_f, _c_f, ctypes.c_void_p, _str]),
     "mnrf_bank_draw": (_int, [ctypes.c_void_p, ctypes.c_uint64, _i64, ctypes.c_void_p, _int, _int, _i64, _c_f, _c_f, _c_f,
                               ctypes.c_void_p, ctypes.c_void_p, _str]),
+    # ---- the output stage of eval.py (csrc/mnrf_frames.hip); maps / images are const MnrfFrameMaps* / MnrfFrameImages*
+    "mnrf_frame_stats_floats": (_int, []),
+    "mnrf_split_extrema_floats": (_int, []),
+    "mnrf_frame_extrema": (_int, [_c_f, _c_f, _c_f, _i64, _c_f, _c_f, _str]),
+    "mnrf_frame_finish": (_int, [ctypes.c_void_p, ctypes.c_void_p, _i64, _c_f, ctypes.c_void_p, _str]),
+    "mnrf_depth_colormap": (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f, ctypes.c_void_p, ctypes.c_void_p, _str]),
 }
 
 _lib = None

@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""The counterpart of the reference's `python eval.py` for the Blender layout: renders every frame of a split from a
+checkpoint and leaves the reference's output directory behind.
+
+    python scripts/eval_scene.py --root_dir data/scene --split test --img_wh 800 800 --ckpt_path ckpts/exp/last.ckpt \\
+        --N_samples 64 --N_importance 128 --trace_secondary_rays --out_dir results/blender/exp
+
+Per frame: RayBank.frame (rays made on the device), batched_inference(to_cpu=False, maps_only=True), frames.finish_frame (the
+8-bit images, on the device), metrics.psnr against the ground truth (on the device), ONE device-to-host copy of the uint8
+images into pinned staging, and PNGs written with PIL from a small thread pool.  The float depth maps stay resident; after the
+last frame frames.colormap_depth re-colours them with the split-wide extremes (save_depth_unified_normalization) and the mean
+PSNR line is printed.  Directory and file names are eval.py's (eval.py:1095-1116, 743-978):
+
+    rgb_{typ}_{i:03d}.png                       depth/depth_{typ}_{i:03d}.png [.pfm] [raw bytes]
+    mirror_mask/mirror_mask_{typ}_{i:03d}.png   depth_reflect/depth_reflect_{typ}_{i:03d}.png
+    normal/surface_normal[_grad]_{typ}_{i:03d}.png      x_surface/x_surface_{typ}_{i:03d}.png
+    depth_unified_normalization/depth_{typ}_{i:03d}.png
+    depth_reflect_unified_normalization/depth_reflect_{typ}_{i:03d}.png
+
+`pfm` and `bytes` in --depth_format copy the float depth map as well.  Out of scope: the GIFs of
+save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the other datasets and the scene-editing
+applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
+frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
+"""
+import argparse
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def get_opts(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--root_dir", type=str, required=True, help="root directory of the dataset (transforms_{split}.json)")
+    ap.add_argument("--split", type=str, default="test", help="test or test_train")
+    ap.add_argument("--img_wh", nargs=2, type=int, default=[800, 800], help="resolution (img_w, img_h) of the image")
+    ap.add_argument("--ckpt_path", type=str, required=True, help="checkpoint holding nerf_coarse.* / nerf_fine.*")
+    ap.add_argument("--trusted", action="store_true", help="unpickle the checkpoint fully (only for files you wrote)")
+    ap.add_argument("--N_samples", type=int, default=64, help="number of coarse samples")
+    ap.add_argument("--N_importance", type=int, default=128, help="number of additional fine samples")
+    ap.add_argument("--chunk", type=int, default=32 * 1024, help="rays per pass")
+    ap.add_argument("--depth_format", type=str, default="png", help="which of png, pfm, bytes to write (any substring)")
+    ap.add_argument("--not_save_depth", action="store_true", help="write no depth maps")
+    ap.add_argument("--out_dir", type=str, required=True, help="the reference's results/{dataset_name}/{exp_name}")
+    # the model and the recursion, named as in the reference's opt.py; NeRFSystem builds whichever model_type asks for
+    ap.add_argument("--model_type", type=str, default="nerf", choices=("nerf", "nerf_tcnn"))
+    ap.add_argument("--bound", type=float, default=1.0, help="scene bound of the hash grid (nerf_tcnn)")
+    ap.add_argument("--N_emb_xyz", type=int, default=10)
+    ap.add_argument("--N_emb_dir", type=int, default=4)
+    ap.add_argument("--no_predict_normal", dest="predict_normal", action="store_false")
+    ap.add_argument("--no_predict_mirror_mask", dest="predict_mirror_mask", action="store_false")
+    ap.add_argument("--only_one_field", action="store_true")
+    ap.add_argument("--only_one_field_fine_epoch", type=int, default=2)
+    ap.add_argument("--use_disp", action="store_true")
+    ap.add_argument("--white_back", action="store_true")
+    ap.add_argument("--trace_secondary_rays", action="store_true")
+    ap.add_argument("--max_recursive_level", type=int, default=1)
+    ap.add_argument("--near", type=float, default=2.0)
+    ap.add_argument("--far", type=float, default=6.0)
+    ap.add_argument("--workers", type=int, default=8, help="PNG-writing threads (at most 16)")
+    return ap.parse_args(argv)
+
+
+def load_system(args, device):
+    """NeRFSystem for args.model_type with every model loaded from args.ckpt_path (eval.py:995-1001)."""
+    import mirror_nerf_amd as M
+    from mirror_nerf_amd import checkpoint
+    system = M.NeRFSystem(args)
+    for key, model in system.models.items():
+        checkpoint.load_ckpt(model, args.ckpt_path, model_name="nerf_" + key if key in ("coarse", "fine") else key,
+                             trusted=args.trusted)
+        model.to(device).eval()
+    return system
+
+
+def render(system, rays, args):
+    """The per-ray maps of one frame, on the device."""
+    import mirror_nerf_amd as M
+    return M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
+                               args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
+                               white_back=args.white_back, to_cpu=False, maps_only=True)
+
+
+def save_pfm(path, image):
+    """utils.save_pfm: a little-endian single-channel PFM, rows bottom to top."""
+    import numpy as np
+    image = np.flipud(np.asarray(image, dtype="<f4"))
+    with open(path, "wb") as f:
+        f.write(b"Pf\n")
+        f.write(f"{image.shape[1]} {image.shape[0]}\n".encode())
+        f.write(b"-1.000000\n")
+        image.tofile(f)
+
+
+class Staging:
+    """The images of a frame reach the host in ONE device-to-host copy: they are concatenated on the device and land in a
+    pinned buffer that is re-used from frame to frame; the arrays handed out are copies the PNG threads own."""
+
+    def __init__(self):
+        self.buf = None
+
+    def fetch(self, images):
+        import torch
+        names = list(images)
+        flat = torch.cat([images[k].reshape(-1) for k in names])
+        if self.buf is None or self.buf.numel() < flat.numel():
+            self.buf = torch.empty(flat.numel(), dtype=torch.uint8).pin_memory()
+        self.buf[:flat.numel()].copy_(flat, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out, o = {}, 0
+        for k in names:
+            n = images[k].numel()
+            out[k] = self.buf[o:o + n].numpy().reshape(tuple(images[k].shape)).copy()
+            o += n
+        return out
+
+
+def main(argv=None):
+    args = get_opts(argv)
+    import torch
+    from PIL import Image
+    from mirror_nerf_amd import frames, metrics
+    from mirror_nerf_amd.data import RayBank
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_scene.py needs a GPU: there is no CPU path")
+    dev = torch.device("cuda", 0)
+    w, h = args.img_wh
+    bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
+    system = load_system(args, dev)
+
+    out = args.out_dir
+    dirs = {"rgb": out, "mirror_mask": os.path.join(out, "mirror_mask"), "depth": os.path.join(out, "depth"),
+            "depth_reflect": os.path.join(out, "depth_reflect"), "surface_normal": os.path.join(out, "normal"),
+            "surface_normal_grad": os.path.join(out, "normal"), "x_surface": os.path.join(out, "x_surface"),
+            "depth_unified": os.path.join(out, "depth_unified_normalization"),
+            "depth_reflect_unified": os.path.join(out, "depth_reflect_unified_normalization")}
+    save_depth = not args.not_save_depth
+    for k, d in dirs.items():
+        if save_depth or k not in ("depth", "depth_unified"):
+            os.makedirs(d, exist_ok=True)
+    print(f"[info] Results saved to dir {out}.")
+    depth_png = save_depth and "png" in args.depth_format
+
+    def write_png(path, a):
+        Image.fromarray(a.reshape(h, w, 3)).save(path)
+
+    extrema = frames.SplitExtrema(dev)
+    staging = Staging()
+    depth_maps, reflect_maps, mask_maps, psnrs = [], [], [], []
+    typ = "fine"
+    pending = []
+    with ThreadPoolExecutor(max_workers=max(1, min(16, args.workers))) as pool:
+        for i in range(bank.n_frames):
+            sample = bank.frame(i)
+            results = render(system, sample["rays"], args)
+            typ = "fine" if "rgb_fine" in results else "coarse"
+            want = [s for s in frames.STEMS if s != "depth" or depth_png]
+            images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
+            # eval.py:801-804: against the clipped prediction; the value stays on the device until the end
+            psnrs.append(metrics.psnr(results[f"rgb_{typ}"].clamp(0, 1), sample["rgbs"]))
+            if save_depth:
+                depth_maps.append(results[f"depth_{typ}"])
+            if f"mirror_mask_{typ}" in results and f"depth_{typ}_reflect" in results:
+                reflect_maps.append(results[f"depth_{typ}_reflect"])
+                mask_maps.append(results[f"mirror_mask_{typ}"])
+            for fut in pending:         # at most one frame of PNGs in flight; a failed write surfaces here
+                fut.result()
+            pending = []
+            host = staging.fetch(images)
+            for name, a in host.items():
+                stem = name[:-len(typ) - 1]
+                pending.append(pool.submit(write_png, os.path.join(dirs[stem], f"{name}_{i:03d}.png"), a))
+            if save_depth and ("pfm" in args.depth_format or "bytes" in args.depth_format):
+                depth = results[f"depth_{typ}"].cpu().numpy().reshape(h, w)
+                if "pfm" in args.depth_format:
+                    save_pfm(os.path.join(dirs["depth"], f"depth_{typ}_{i:03d}.pfm"), depth)
+                if "bytes" in args.depth_format:
+                    with open(os.path.join(dirs["depth"], f"depth_{typ}_{i:03d}"), "wb") as f:
+                        f.write(depth.tobytes())
+        for fut in pending:
+            fut.result()
+
+        # save_depth_unified_normalization (eval.py:931-978): every map again, with the extremes of the whole split
+        jobs = []
+        if depth_png and depth_maps:
+            jobs.append(("depth_unified", f"depth_{typ}", frames.colormap_depth(torch.stack(depth_maps), extrema.depth)))
+        if reflect_maps:
+            jobs.append(("depth_reflect_unified", f"depth_reflect_{typ}",
+                         frames.colormap_depth(torch.stack(reflect_maps), extrema.depth_reflect, torch.stack(mask_maps))))
+        for key, stem, stack in jobs:
+            stack = stack.cpu().numpy()
+            pending += [pool.submit(write_png, os.path.join(dirs[key], f"{stem}_{i:03d}.png"), stack[i])
+                        for i in range(stack.shape[0])]
+        for fut in pending:
+            fut.result()
+
+    if psnrs:
+        mean_psnr = float(torch.stack(psnrs).double().mean())
+        print(f"Mean PSNR ({typ}): {mean_psnr:.2f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
