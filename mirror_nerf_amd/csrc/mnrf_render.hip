@@ -141,9 +141,9 @@ __global__ __launch_bounds__(256) void composite_kernel(CompArgs A) {
 
 
 // ------------------------------------------------------------------ compositing backward
-// w_i = alpha_i T_i, T_i = prod_{j<i} t_j, t_j = 1 - alpha_j + 1e-10.  With G_i = dL/dw_i (direct +
+// w_i = alpha_i T_i, T_i = prod_{j<i} t_j, t_j = exp(-delta_j sigma_j) + 1e-10 (= 1 - alpha_j + 1e-10).  With G_i = dL/dw_i (direct +
 // through every composited output):  dL/dalpha_i = G_i T_i - (sum_{k>i} G_k w_k) / t_i, and
-// dalpha/dsigma = delta (1 - alpha) [sigma + noise > 0].  One wavefront per ray: T by the forward
+// dalpha/dsigma = delta exp(-delta sigma) [sigma + noise > 0].  One wavefront per ray: T by the forward
 // prefix product of the forward kernel, the suffix sum by a reverse scan over the lanes; both are
 // carried across 64-sample blocks (S <= 256).
 struct CompBwdArgs {
@@ -201,14 +201,15 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(CompBwdArgs A) 
         const int s = blk * 64 + lane;
         const bool in = s < S;
         const long long i1 = ray * S + s, i3 = i1 * 3;
-        float alpha = 0.f, G = 0.f, delta = 0.f, sv = 0.f;
+        float alpha = 0.f, G = 0.f, delta = 0.f, sv = 0.f, ex = 1.f;
         float pn[3] = {0.f, 0.f, 0.f}, gn[3] = {0.f, 0.f, 0.f};
         if (in) {
             const float zv = A.z[i1];
             delta = s + 1 < S ? A.z[i1 + 1] - zv : 1e10f;
             sv = A.sigma[i1];
             if (A.noise) sv = sv + A.noise[i1];
-            alpha = 1.f - expf(-delta * fmaxf(sv, 0.f));
+            ex = expf(-delta * fmaxf(sv, 0.f));
+            alpha = 1.f - ex;
             G = (A.g_w ? A.g_w[i1] : 0.f) + gop + gd * zv;
             if (A.rgb) G += gc[0] * A.rgb[i3] + gc[1] * A.rgb[i3 + 1] + gc[2] * A.rgb[i3 + 2];
             if (A.is_mirror) G += gm_w * A.is_mirror[i1];
@@ -219,7 +220,10 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(CompBwdArgs A) 
                 G += gnd_w * (d0 * d0 + d1 * d1 + d2 * d2);
             }
         }
-        const float t = in ? (1.f - alpha) + 1e-10f : 1.f;
+        // 1 - alpha + 1e-10 with 1 - alpha taken as the exponential itself: re-formed from the rounded alpha (as the forward does,
+        // which keeps the reference's float32 expression) it is 0 once alpha is within an ulp of 1, and a transmittance of 3e-9
+        // becomes 1e-10 -- harmless in the forward's maps (3e-9 of the ray's largest weight), 9 % of a gradient row behind it
+        const float t = in ? ex + 1e-10f : 1.f;
         float incl = t;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -232,7 +236,9 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(CompBwdArgs A) 
         carry = carry * __shfl(incl, 63);
         const float w = alpha * T;
         Tn[blk] = T; Gv[blk] = G; Gw[blk] = in ? G * w : 0.f; tv[blk] = t;
-        dads[blk] = (in && sv > 0.f) ? delta * (1.f - alpha) : 0.f;   // relu'(0) = 0 as in torch
+        // dalpha/dsigma = delta exp(-delta sigma): the exponential itself, not 1 - alpha, which is 0 (or a few ulp of 1) once alpha
+        // is within 1e-5 of 1 and then loses the gradient of a nearly opaque sample; relu'(0) = 0 as in torch
+        dads[blk] = (in && sv > 0.f) ? delta * ex : 0.f;
         if (in) {   // gradients of the per-sample inputs that enter linearly
             if (A.d_rgb) { for (int k = 0; k < 3; ++k) A.d_rgb[i3 + k] = w * gc[k]; }
             if (A.d_mirror) A.d_mirror[i1] = w * gm;

@@ -1,5 +1,5 @@
-"""Plain-torch restatements of the two floating-point kernels that have a backward pass
-(field MLP, compositing), in the dtype of their inputs (fp32, or float64 with the kernel's own
+"""Plain-torch restatements of the floating-point kernels that have a backward pass (field MLP, compositing) and of
+the per-ray kernels around them (resampling, reflection, blend, ray gradients), in the dtype of their inputs (fp32, or float64 with the kernel's own
 activation masks: `field(..., masks=)`).  TEST INFRASTRUCTURE ONLY: the GPU tests differentiate these with
 torch.autograd to check the hand-written HIP backward kernels; the product never imports this."""
 import torch
@@ -127,6 +127,51 @@ def blend(base, sec, mask, compact):
         part = sec
     m = mask[:, None]
     return m * part + (1 - m) * base
+
+
+def sample_pdf(bins, weights, n_importance, u, eps=1e-5):
+    """models/rendering.py:7-51 in the dtype of its inputs.  bins (N, S-1): the mid-points; weights (N, S-2): weights[:, 1:-1];
+    u (n_importance,) shared by the rays or (N, n_importance)."""
+    return sample_pdf_info(bins, weights, n_importance, u, eps)[0]
+
+
+def sample_pdf_info(bins, weights, n_importance, u, eps=1e-5):
+    """sample_pdf and what it decided on the way: (samples, cdf (N, S-1), u (N, n_importance), c1 - c0 before the `< eps`
+    replacement, b1 - b0 of the selected bin)."""
+    n_rays, n_s = weights.shape
+    weights = weights + eps
+    pdf = weights / weights.sum(-1, keepdim=True)
+    cdf = torch.cumsum(pdf, -1)
+    cdf = torch.cat([torch.zeros_like(cdf[:, :1]), cdf], -1)
+    u = u.to(cdf.dtype).expand(n_rays, n_importance).contiguous()
+    inds = torch.searchsorted(cdf, u, right=True)
+    below = torch.clamp_min(inds - 1, 0)
+    above = torch.clamp_max(inds, n_s)
+    c0, c1 = torch.gather(cdf, 1, below), torch.gather(cdf, 1, above)
+    b0, b1 = torch.gather(bins, 1, below), torch.gather(bins, 1, above)
+    raw = c1 - c0
+    denom = torch.where(raw < eps, torch.ones_like(raw), raw)
+    return b0 + (u - c0) / denom * (b1 - b0), cdf, u, raw, b1 - b0
+
+
+def mids(z):
+    """models/rendering.py:313-315: the interval mid-points of the depths."""
+    return 0.5 * (z[:, :-1] + z[:, 1:])
+
+
+def merge_sorted(z, fine):
+    """models/rendering.py:324: coarse and fine depths in one sorted row."""
+    return torch.sort(torch.cat([z, fine], -1), -1)[0]
+
+
+def ray_grads(d_xyz, z, d_dir, spr):
+    """include/mnrf.h mnrf_ray_grads: g_rays (N, 8) = [sum_s dL/dx_s | sum_s z_s dL/dx_s | 0 0] and g_de (N, 27) = the sum of the
+    first 27 columns of d_dir (N * spr, 32) over each ray's samples.  d_xyz (N * spr, 3), z (N, spr)."""
+    n = z.shape[0]
+    g = d_xyz.reshape(n, spr, 3)
+    g_rays = torch.cat([g.sum(1), (z[..., None] * g).sum(1), torch.zeros_like(g[:, 0, :2])], -1)
+    g_de = d_dir.reshape(n, spr, -1)[:, :, :27].sum(1)
+    return g_rays, g_de
 
 
 def hashgrid_encode(x01, table, cfg):
