@@ -838,6 +838,27 @@ int mnrf_frame_finish(const MnrfFrameMaps* maps, const MnrfFrameImages* images, 
 int mnrf_depth_colormap(const float* depth, const float* mask, int64_t frames, int64_t n, const float* extrema, float* stats,
                         const uint8_t* table, uint8_t* out, void* stream);
 
+/* ---- the ingest step of the ray bank (csrc/mnrf_resample.hip; datasets/real_arkit.py:236-237, 251-264): decoded frames are
+ * resized on the device.  The arithmetic is Pillow's 8-bit resampler, stated in the header comment of csrc/mnrf_resample.hip:
+ * a pass along x into `tmp`, rounded to 8 bits, then a pass along y; a pass whose sizes agree is not run.  src (frames, src_h,
+ * src_w, channels), dst (frames, dst_h, dst_w, channels), channels 3 or 4; four channels are RGBA, premultiplied at the first
+ * pass's loads and divided out at the last pass's stores.  Per resized axis the caller hands in the tables data.lanczos_taps
+ * makes on the host: bounds (out, 2) int32 (first source sample, count) and taps (ksize, out) int32 (22 fraction bits, tap k
+ * of output i at [k * out + i]); the tables of a pass that is not run may be null.  Every window is clamped to the source extent
+ * and to ksize before use.  tmp: (frames, src_h, dst_w, channels) bytes of the caller's, needed when both passes run (the size
+ * below; 0 when at most one pass runs, -1 for sizes the call would refuse).  Refused: sizes < 1, channels other than 3 or 4,
+ * null pointers, and src and dst sizes that agree on both axes (nothing to resample: the caller copies). */
+int64_t mnrf_resample_tmp_bytes(int64_t frames, int src_h, int src_w, int dst_h, int dst_w, int channels);
+int mnrf_resample_u8(const uint8_t* src, int64_t frames, int src_h, int src_w, int channels, uint8_t* dst, int dst_h, int dst_w,
+                     const int32_t* taps_x, const int32_t* bounds_x, int ksize_x, const int32_t* taps_y,
+                     const int32_t* bounds_y, int ksize_y, uint8_t* tmp, void* stream);
+/* A mirror mask at its native depth to the bank's int8: src (frames, src_h, src_w) samples of 1 or 2 bytes (native byte
+ * order), dst (frames, dst_h, dst_w).  Output (y, x) picks source (min(floor(y * (src_h / dst_h)), src_h - 1), the same in x),
+ * the quotient and the product in double (cv2's INTER_NEAREST rule as data._resize_nearest states it); an 8-bit sample >= 128
+ * gives 1, a 16-bit sample > 0 gives 1, anything else 0. */
+int mnrf_mask_nearest(const void* src, int sample_bytes, int64_t frames, int src_h, int src_w, int8_t* dst, int dst_h, int dst_w,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,11 @@ SIGNATURES = {
     "mnrf_frame_extrema": (_int, [_c_f, _c_f, _c_f, _i64, _c_f, _c_f, _str]),
     "mnrf_frame_finish": (_int, [ctypes.c_void_p, ctypes.c_void_p, _i64, _c_f, ctypes.c_void_p, _str]),
     "mnrf_depth_colormap": (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f, ctypes.c_void_p, ctypes.c_void_p, _str]),
+    # ---- the bank's ingest step (csrc/mnrf_resample.hip): Pillow's 8-bit LANCZOS resize and the masks' nearest pick
+    "mnrf_resample_tmp_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
+    "mnrf_resample_u8": (_int, [ctypes.c_void_p, _i64, _int, _int, _int, ctypes.c_void_p, _int, _int, _c_i, _c_i, _int, _c_i, _c_i, _int,
+                                ctypes.c_void_p, _str]),
+    "mnrf_mask_nearest": (_int, [ctypes.c_void_p, _int, _i64, _int, _int, ctypes.c_void_p, _int, _int, _str]),
 }
 
 _lib = None

@@ -124,6 +124,20 @@ def device_rays(H, W, dev, pose=None, near=NEAR, far=FAR, camera_angle_x=CAMERA_
     return rays
 
 
+def generate_rays(H, W, focal, pose, near, far, dev):
+    """(H*W, 8) rays [o, d, near, far] of a pin-hole camera with the given focal length and camera-to-world `pose` ((3, 4), or
+    the upper rows of a (4, 4); rounded to float32 as the reference rounds it), generated on the GPU by mnrf_generate_rays
+    (datasets/ray_utils.py:6-53).  What a dataset's pose-only splits need: there is no image to draw from."""
+    import ctypes
+    from . import _lib
+    rays = torch.empty(H * W, 8, device=dev)
+    c2w = (ctypes.c_float * 12)(*np.asarray(pose, np.float32)[:3, :4].reshape(-1).tolist())
+    with torch.cuda.device(rays.device):
+        _lib.check(_lib.lib().mnrf_generate_rays(H, W, float(focal), c2w, float(near), float(far), _lib.ptr(rays),
+                                                 _lib.stream()), "mnrf_generate_rays")
+    return rays
+
+
 def build_models(dev, tweaks=None, seed=0, names=("coarse", "fine")):
     """The seeded random-init MirrorNeRF pair of the benchmark / smoke test on `dev` (+ its numpy state dicts)."""
     from .mirror_nerf import MirrorNeRF

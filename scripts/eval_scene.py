@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The counterpart of the reference's `python eval.py` for the Blender layout: renders every frame of a split from a
-checkpoint and leaves the reference's output directory behind.
+"""The counterpart of the reference's `python eval.py` for the Blender layout and for real captures (--dataset_name
+real_arkit: datasets/real_arkit.py's layout, data.read_arkit): renders every frame of a split from a checkpoint and leaves the
+reference's output directory behind.
 
     python scripts/eval_scene.py --root_dir data/scene --split test --img_wh 800 800 --ckpt_path ckpts/exp/last.ckpt \\
         --N_samples 64 --N_importance 128 --trace_secondary_rays --out_dir results/blender/exp
@@ -17,9 +18,16 @@ PSNR line is printed.  Directory and file names are eval.py's (eval.py:1095-1116
     depth_unified_normalization/depth_{typ}_{i:03d}.png
     depth_reflect_unified_normalization/depth_reflect_{typ}_{i:03d}.png
 
-`pfm` and `bytes` in --depth_format copy the float depth map as well.  Out of scope: the GIFs of
-save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the other datasets and the scene-editing
-applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
+`pfm` and `bytes` in --depth_format copy the float depth map as well.
+
+The fly-through splits of a real capture (--split test_rotate | test_interpolation) carry poses only: the rays of a frame come
+from synthetic.generate_rays, there is no ground truth and so no PSNR line, the files keep the same names, and the frames'
+GIF `{exp}_rgb_{typ}.gif` (eval.py:897-903; exp = --exp_name, by default the last component of --out_dir; 15 frames per
+second) is written with PIL.  That GIF is NOT pinned against imageio's: the frames are the PNGs' bytes, the palette and the
+container are PIL's.
+
+Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
+and the scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
 frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -34,7 +42,12 @@ sys.path.insert(0, ROOT)
 def get_opts(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root_dir", type=str, required=True, help="root directory of the dataset (transforms_{split}.json)")
-    ap.add_argument("--split", type=str, default="test", help="test or test_train")
+    ap.add_argument("--dataset_name", type=str, default="blender", choices=("blender", "real_arkit"))
+    ap.add_argument("--split", type=str, default="test",
+                    help="test or test_train; with real_arkit also val, test_rotate and test_interpolation (poses only)")
+    ap.add_argument("--scale_factor", type=float, default=1.0, help="real_arkit: translations, near and far are divided by it")
+    ap.add_argument("--val_idx", type=int, default=0, help="real_arkit: the frame of val and the one test_rotate moves around")
+    ap.add_argument("--exp_name", type=str, default=None, help="prefix of the GIF (default: the last component of --out_dir)")
     ap.add_argument("--img_wh", nargs=2, type=int, default=[800, 800], help="resolution (img_w, img_h) of the image")
     ap.add_argument("--ckpt_path", type=str, required=True, help="checkpoint holding nerf_coarse.* / nerf_fine.*")
     ap.add_argument("--trusted", action="store_true", help="unpickle the checkpoint fully (only for files you wrote)")
@@ -122,12 +135,26 @@ def main(argv=None):
     import torch
     from PIL import Image
     from mirror_nerf_amd import frames, metrics
-    from mirror_nerf_amd.data import RayBank
+    from mirror_nerf_amd.data import PATH_SPLITS, RayBank, read_arkit
     if not torch.cuda.is_available():
         raise SystemExit("eval_scene.py needs a GPU: there is no CPU path")
     dev = torch.device("cuda", 0)
     w, h = args.img_wh
-    bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
+    path_split = args.dataset_name == "real_arkit" and args.split in PATH_SPLITS
+    if path_split:
+        from mirror_nerf_amd import synthetic
+        fly = read_arkit(args.root_dir, args.split, (w, h), args.near, args.far, args.scale_factor, args.val_idx)
+        n_frames = len(fly["poses"])
+
+        def frame_of(i):
+            return {"rays": synthetic.generate_rays(h, w, fly["focal"], fly["poses"][i], fly["near"], fly["far"], dev)}
+    else:
+        if args.dataset_name == "real_arkit":
+            bank = RayBank.from_arkit(args.root_dir, args.split, (w, h), args.near, args.far, args.scale_factor, args.val_idx,
+                                      device=dev, workers=args.workers)
+        else:
+            bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
+        n_frames, frame_of = bank.n_frames, bank.frame
     system = load_system(args, dev)
 
     out = args.out_dir
@@ -148,18 +175,19 @@ def main(argv=None):
 
     extrema = frames.SplitExtrema(dev)
     staging = Staging()
-    depth_maps, reflect_maps, mask_maps, psnrs = [], [], [], []
+    depth_maps, reflect_maps, mask_maps, psnrs, gif_frames = [], [], [], [], []
     typ = "fine"
     pending = []
     with ThreadPoolExecutor(max_workers=max(1, min(16, args.workers))) as pool:
-        for i in range(bank.n_frames):
-            sample = bank.frame(i)
+        for i in range(n_frames):
+            sample = frame_of(i)
             results = render(system, sample["rays"], args)
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
             # eval.py:801-804: against the clipped prediction; the value stays on the device until the end
-            psnrs.append(metrics.psnr(results[f"rgb_{typ}"].clamp(0, 1), sample["rgbs"]))
+            if "rgbs" in sample:
+                psnrs.append(metrics.psnr(results[f"rgb_{typ}"].clamp(0, 1), sample["rgbs"]))
             if save_depth:
                 depth_maps.append(results[f"depth_{typ}"])
             if f"mirror_mask_{typ}" in results and f"depth_{typ}_reflect" in results:
@@ -169,6 +197,8 @@ def main(argv=None):
                 fut.result()
             pending = []
             host = staging.fetch(images)
+            if path_split:
+                gif_frames.append(Image.fromarray(host[f"rgb_{typ}"].reshape(h, w, 3)))
             for name, a in host.items():
                 stem = name[:-len(typ) - 1]
                 pending.append(pool.submit(write_png, os.path.join(dirs[stem], f"{name}_{i:03d}.png"), a))
@@ -196,6 +226,10 @@ def main(argv=None):
         for fut in pending:
             fut.result()
 
+    if gif_frames:      # save_gif_and_print_mean_psnr's first GIF (eval.py:897-903), FPS = 15
+        exp = args.exp_name or os.path.basename(os.path.normpath(out))
+        gif_frames[0].save(os.path.join(out, f"{exp}_rgb_{typ}.gif"), save_all=True, append_images=gif_frames[1:],
+                           duration=round(1000 / 15), loop=0)
     if psnrs:
         mean_psnr = float(torch.stack(psnrs).double().mean())
         print(f"Mean PSNR ({typ}): {mean_psnr:.2f}")

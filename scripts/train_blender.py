@@ -5,6 +5,10 @@ PNGs, masks/MirrorMask_*.png) ON THE GPU: the frames are read once (data.read_bl
 ray arrays, no DataLoader, no per-step host-to-device copy.  On the graph route the draw writes straight into the captured
 step's static buffers.  The weights are written as scripts/train_scene.py writes them (coarse__* / fine__* arrays).
 
+With --dataset_name real_arkit the directory is a real capture (datasets/real_arkit.py's layout): the poses are centred with the
+average pose of transforms.json and divided by --scale_factor, and the frames are resized on the device as they enter the bank
+(RayBank.from_arkit).
+
     python scripts/train_blender.py --root_dir data/scene --img_wh 400 400 --near 2 --far 6 --steps 20000 --route graph --out weights.npz
 """
 import argparse
@@ -32,6 +36,9 @@ def main():
     ap.add_argument("--near", type=float, default=2.0)
     ap.add_argument("--far", type=float, default=6.0)
     ap.add_argument("--train_skip_step", type=int, default=1)
+    ap.add_argument("--dataset_name", choices=("blender", "real_arkit"), default="blender")
+    ap.add_argument("--scale_factor", type=float, default=1.0, help="real_arkit: translations, near and far are divided by it")
+    ap.add_argument("--val_idx", type=int, default=0, help="real_arkit: accepted as the reference's option; the train split does not use it")
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--lr", type=float, default=5e-4)
@@ -50,7 +57,11 @@ def main():
     torch.manual_seed(a.seed)
     hp = training.default_hparams(N_importance=64, train_geometry_stage_end_epoch=a.geometry_epochs)
     system = M.NeRFSystem(hp).to(dev)
-    full = RayBank.from_blender(a.root_dir, "train", tuple(a.img_wh), a.near, a.far, a.train_skip_step, device=dev)
+    if a.dataset_name == "real_arkit":
+        full = RayBank.from_arkit(a.root_dir, "train", tuple(a.img_wh), a.near, a.far, a.scale_factor, a.val_idx, a.train_skip_step,
+                                  device=dev)
+    else:
+        full = RayBank.from_blender(a.root_dir, "train", tuple(a.img_wh), a.near, a.far, a.train_skip_step, device=dev)
     print(f"{full.n_frames} frames of {full.W}x{full.H}x{full.channels}, {len(full.frames_with_mask)} with a mirror mask; "
           f"{full.bytes_resident() / 1e6:.2f} MB resident ({full.n_rays * 48 / 1e6:.2f} MB as float rays)", flush=True)
     if a.geometry_epochs > 0 and not full.frames_with_mask:
