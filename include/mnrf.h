@@ -210,6 +210,25 @@ int mnrf_place_mirror(const float* rays, int64_t n_rays, int axis, float positio
 int mnrf_transform_rays(float* rays, int64_t n_rays, const float* rotation, float scale, float tx, float ty, float tz,
                         void* stream);
 
+/* Reflect a newly placed object (eval.py:173-291, app_reflect_newly_placed_objects; the object is a plain NeRF field that
+ * the caller renders between these two calls).
+ *
+ * Move one level's rays (n_rays,8) into the object's frame, OUT OF PLACE (the level's own rays are still needed): with pose
+ * (a HOST array of 12 floats, the row-major 3x4 [A | p] of the reference's pose_align; null = none) o = A o + p and
+ * d = l2_normalize(A d) (utils/func.py:5-7); then o = o * scale, then o = o + (tx, ty, tz) -- two roundings, as the reference
+ * writes them.  Columns 6..7 (near, far) are copied.  out (n_rays,8) must not be rays. */
+int mnrf_object_rays(const float* rays, int64_t n_rays, const float* pose, float scale, float tx, float ty, float tz,
+                     float* out, void* stream);
+
+/* Merge the object's maps into the level's, ordered by depth (eval.py:261-291).  Per ray: d = obj_depth / scale / pose_scale0
+ * (two divisions, in that order; pose_scale0 = the norm of the first column of A, 1 without a pose); the object counts where
+ * `d > 0 && obj_opacity > 0.8f`, and is hidden by the scene where `d > depth && depth > near` (near = the global
+ * hyper-parameter).  Where it counts and is not hidden: rgb (n_rays,3) = obj_rgb, depth (n_rays) = d, mask (n_rays) = 0, in
+ * place; every other ray is left as it was.  Comparisons with NaN are false.  mask: null = skip (a level rendered without a
+ * mirror head); *n_used (int32, device, caller zeroes it, null = skip) receives the number of rays that took the object. */
+int mnrf_object_merge(const float* obj_rgb, const float* obj_depth, const float* obj_opacity, int64_t n_rays, float scale,
+                      float pose_scale0, float near, float* rgb, float* depth, float* mask, int32_t* n_used, void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

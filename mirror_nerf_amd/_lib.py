@@ -114,6 +114,8 @@ SIGNATURES = {
     "mnrf_blend_scatter": (_int, [_c_f, _c_f, _c_i, _i64, _c_f, _i64, _int, _c_f, _c_f, _str]),
     "mnrf_place_mirror": (_int, [_c_f, _i64, _int] + [_flt] * 9 + [_c_f, _c_f, _c_f, _c_f, ctypes.c_void_p, _c_i, _str]),
     "mnrf_transform_rays": (_int, [_c_f, _i64, ctypes.POINTER(ctypes.c_float), _flt, _flt, _flt, _flt, _str]),
+    "mnrf_object_rays": (_int, [_c_f, _i64, ctypes.POINTER(ctypes.c_float), _flt, _flt, _flt, _flt, _c_f, _str]),
+    "mnrf_object_merge": (_int, [_c_f, _c_f, _c_f, _i64, _flt, _flt, _flt, _c_f, _c_f, _c_f, _c_i, _str]),
     "mnrf_generate_rays": (_int, [_int, _int, _flt, ctypes.POINTER(ctypes.c_float), _flt, _flt, _c_f, _str]),
     "mnrf_loss_workspace_floats": (_i64, [_i64, _int, _int, _i64]),
     "mnrf_total_loss": (_int, [ctypes.c_void_p, _c_f, _str]),     # const MnrfLossArgs* (losses._Args)

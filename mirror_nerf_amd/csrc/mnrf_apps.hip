@@ -1,7 +1,9 @@
-// mnrf_apps.hip -- the per-ray kernels of the two scene-editing applications of eval.batched_inference that need only
-// MirrorNeRF fields: placing a new planar mirror (eval.py:311-320, 364-504) and the ray transform in front of a reflection
-// substitution (eval.py:550-613).  Both are memory-bound (one thread per ray, ~70 B read and written per ray); they exist
-// so that the application modes run no chain of framework ops per level.
+// mnrf_apps.hip -- the per-ray kernels of the scene-editing applications of eval.batched_inference that need only
+// MirrorNeRF fields: placing a new planar mirror (eval.py:311-320, 364-504), the ray transform in front of a reflection
+// substitution (eval.py:550-613), and the two steps around the object field of a newly placed object (eval.py:173-291): the
+// move of a level's rays into the object's frame and the depth-ordered merge of the object's maps into the level's.  All are
+// memory-bound (one thread per ray, ~70 B read and written per ray); they exist so that the application modes run no chain
+// of framework ops per level.
 // Compiled with -ffp-contract=off and IEEE division: the expressions below are the reference's, in its order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +101,74 @@ __global__ __launch_bounds__(256) void transform_rays_kernel(XformArgs A) {
     for (int k = 0; k < 3; ++k) r[k] = o[k] * A.scale + A.t[k];
 }
 
+struct ObjectRaysArgs {
+    const float* rays; long long n; int posed; float A[9]; float p[3]; float scale; float t[3]; float* out;
+};
+
+// eval.py:175-217, out of place: with a pose o = A o + p (two steps: the product, then the sum), d = l2_normalize(A d)
+// (utils/func.py:5-7); then o = o * scale, then o = o + t (two roundings); near / far are copied
+__global__ __launch_bounds__(256) void object_rays_kernel(ObjectRaysArgs A) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const float* r = A.rays + i * 8;
+    float* q = A.out + i * 8;
+    float o[3] = {r[0], r[1], r[2]};
+    float d[3] = {r[3], r[4], r[5]};
+    if (A.posed) {
+        float ro[3], rd[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ro[k] = A.A[k * 3 + 0] * o[0] + A.A[k * 3 + 1] * o[1] + A.A[k * 3 + 2] * o[2];
+            rd[k] = A.A[k * 3 + 0] * d[0] + A.A[k * 3 + 1] * d[1] + A.A[k * 3 + 2] * d[2];
+        }
+        const float len = sqrtf(fmaxf(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2], EPS32));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            o[k] = ro[k] + A.p[k];
+            d[k] = rd[k] / len;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float scaled = o[k] * A.scale;
+        q[k] = scaled + A.t[k];
+        q[3 + k] = d[k];
+    }
+    q[6] = r[6];
+    q[7] = r[7];
+}
+
+struct ObjectMergeArgs {
+    const float* obj_rgb; const float* obj_depth; const float* obj_opacity; long long n; float scale; float pose_scale0; float near;
+    float* rgb; float* depth; float* mask; int* n_used;
+};
+
+// eval.py:261-291 on one ray: the object's depth back in the scene's units (two divisions, in the reference's order), the
+// object where it is opaque (`> 0.8` of the accumulated weight, depth > 0: "remove white bg") and not behind the scene's
+// foreground (the scene's depth of this level, valid when beyond the global near).  Comparisons with NaN are false.
+__global__ __launch_bounds__(256) void object_merge_kernel(ObjectMergeArgs A) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool use = false;
+    if (i < A.n) {
+        const float d = A.obj_depth[i] / A.scale / A.pose_scale0;                                  // eval.py:261-265
+        const float depth = A.depth[i];
+        const bool obj = d > 0.f && A.obj_opacity[i] > 0.8f;                                       // eval.py:268-272
+        const bool blocked = d > depth && depth > A.near;                                          // eval.py:275-281, 169-171
+        use = obj && !blocked;                                                                     // eval.py:282-284
+        if (use) {                                                                                 // eval.py:285-291
+            A.rgb[i * 3 + 0] = A.obj_rgb[i * 3 + 0];
+            A.rgb[i * 3 + 1] = A.obj_rgb[i * 3 + 1];
+            A.rgb[i * 3 + 2] = A.obj_rgb[i * 3 + 2];
+            A.depth[i] = d;
+            if (A.mask) A.mask[i] = 0.f;
+        }
+    }
+    if (A.n_used) {
+        const unsigned long long b = __ballot(use);
+        if (b != 0ull && (threadIdx.x & 63) == 0) atomicAdd(A.n_used, __popcll(b));
+    }
+}
+
 inline unsigned blocks_for(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 }  // namespace
@@ -127,4 +197,32 @@ extern "C" int mnrf_transform_rays(float* rays, int64_t n_rays, const float* rot
         for (int k = 0; k < 9; ++k) A.R[k] = rotation[k];
     hipLaunchKernelGGL(transform_rays_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, A);
     return mnrf_check_launch("mnrf_transform_rays");
+}
+
+extern "C" int mnrf_object_rays(const float* rays, int64_t n_rays, const float* pose, float scale, float tx, float ty, float tz,
+                                float* out, void* stream) {
+    if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_rays: bad size");
+    if (n_rays == 0) return MNRF_OK;
+    if (!rays || !out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_rays: null pointer");
+    if (rays == out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_rays: works out of place (out must not be rays)");
+    ObjectRaysArgs A{rays, (long long)n_rays, pose != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}, scale,
+                     {tx, ty, tz}, out};
+    if (pose)
+        for (int k = 0; k < 3; ++k) {
+            for (int j = 0; j < 3; ++j) A.A[k * 3 + j] = pose[k * 4 + j];
+            A.p[k] = pose[k * 4 + 3];
+        }
+    hipLaunchKernelGGL(object_rays_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_object_rays");
+}
+
+extern "C" int mnrf_object_merge(const float* obj_rgb, const float* obj_depth, const float* obj_opacity, int64_t n_rays, float scale,
+                                 float pose_scale0, float near, float* rgb, float* depth, float* mask, int32_t* n_used,
+                                 void* stream) {
+    if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_merge: bad size");
+    if (n_rays == 0) return MNRF_OK;
+    if (!obj_rgb || !obj_depth || !obj_opacity || !rgb || !depth) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_merge: null pointer");
+    ObjectMergeArgs A{obj_rgb, obj_depth, obj_opacity, (long long)n_rays, scale, pose_scale0, near, rgb, depth, mask, n_used};
+    hipLaunchKernelGGL(object_merge_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_object_merge");
 }

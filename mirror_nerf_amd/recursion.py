@@ -2,17 +2,18 @@
 
   * `NeRFSystem.forward` / `render_rays_chunk_recursively`  -- TRAIN semantics, train.py:102-348
   * `batched_inference`                                      -- EVAL semantics, eval.py:114-172,
-    293-740: the core path, roughness (app_control_mirror_roughness) and the two scene-editing
+    293-740: the core path, roughness (app_control_mirror_roughness) and the three scene-editing
     applications that need only MirrorNeRF fields -- a new planar mirror (app_place_new_mirror,
-    eval.py:311-320, 364-504; run.sh MODE 3) and reflection substitution (app_reflection_substitution,
-    eval.py:550-613: the reflections are rendered by a second system).  The new-object branch
-    (app_reflect_newly_placed_objects, eval.py:173-291) is refused: it needs D-NeRF / nerf_pl object
-    models, and cannot run in the reference itself (see _refuse_apps).
+    eval.py:311-320, 364-504; run.sh MODE 3), reflection substitution (app_reflection_substitution,
+    eval.py:550-613: the reflections are rendered by a second system) and a newly placed object
+    (app_reflect_newly_placed_objects, eval.py:173-291; run.sh MODE 4) whose field is a nerf_pl model:
+    the plain NeRF this package already runs (MirrorNeRF without the optional heads).  The other object
+    type of the reference, D-NeRF (a time-conditioned deformation network), is refused (see _refuse_apps).
 
 Python here is the recursion driver only: mask thresholding, reflected-ray construction,
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
-mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror and
-mnrf_transform_rays.  One 4-byte device->host read per level decides
+mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
+mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge.  One 4-byte device->host read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
@@ -57,6 +58,14 @@ SUBSTITUTION_PRESETS = (
                     translation=(0.0, 0.0, 0.0))),                                                          # eval.py:555-583
     (None, dict(rotation=None, scale=1.0, translation=(0.0, 0.0, 0.0))),                                    # eval.py:584-586
 )
+# app_reflect_newly_placed_objects presets (eval.py:177-190): how a level's rays are moved into the object's frame.  pose_align
+# is None in every branch of the reference (eval.py:177); `new_object=` of batched_inference may give one.
+OBJECT_PRESETS = (
+    ("livingroom", dict(pose_align=None, scale=2.0, translation=(0.0, 0.0, 0.0))),                          # eval.py:180-184
+    ("washroom", dict(pose_align=None, scale=2.0, translation=(-0.5, -0.5, 0.0))),                          # eval.py:185-187
+    ("office", dict(pose_align=None, scale=2.0, translation=(0.0, 3.0, 0.5))),                              # eval.py:188-190
+    (None, dict(pose_align=None, scale=1.0, translation=(0.0, 0.0, 0.0))),                                  # eval.py:178-179
+)
 
 
 def _preset(table, root_dir):
@@ -92,15 +101,88 @@ def resolve_substitution(args):
     return _preset(SUBSTITUTION_PRESETS, getattr(args, "root_dir", ""))
 
 
+def resolve_new_object(args, new_object=None):
+    """The ray move of app_reflect_newly_placed_objects: dict(pose (12 floats, the row-major 3x4 [A | p], or None), scale,
+    translation (3,), pose_scale0).  `new_object=dict(pose_align=None | 3x4 | 4x4, scale=, translation=)` overrides the preset
+    that args.root_dir selects (eval.py:177-190).  pose_scale0 is the fp32 norm of the first column of A (eval.py:194-196) and
+    1 without a pose: the reference leaves `pose_scale` unbound there (eval.py:264), and no alignment is a scale of 1."""
+    if new_object is not None:
+        cfg = dict(new_object)
+        missing = {"pose_align", "scale", "translation"} - set(cfg)
+        if missing:
+            raise ValueError(f"new_object needs the keys pose_align, scale, translation (missing: {sorted(missing)})")
+    else:
+        cfg = _preset(OBJECT_PRESETS, getattr(args, "root_dir", ""))
+    if len(cfg["translation"]) != 3:
+        raise ValueError("new_object translation has 3 entries")
+    scale = float(cfg["scale"])
+    if not scale > 0.0:
+        raise ValueError(f"new_object scale must be positive, not {cfg['scale']!r}")
+    pose, pose_scale0 = None, 1.0
+    if cfg["pose_align"] is not None:
+        m = torch.as_tensor(cfg["pose_align"], dtype=torch.float32)            # eval.py:193 (FloatTensor)
+        if tuple(m.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"new_object pose_align must be None, 3x4 or 4x4, not {tuple(m.shape)}")
+        pose = tuple(float(v) for v in m[:3, :4].reshape(-1))
+        pose_scale0 = float(torch.norm(m[:3, 0]))                              # eval.py:194-196, the only entry that is read
+        if not pose_scale0 > 0.0:
+            raise ValueError("new_object pose_align: the first column of its 3x3 is zero")
+    return dict(pose=pose, scale=scale, translation=tuple(float(v) for v in cfg["translation"]), pose_scale0=pose_scale0)
+
+
+def _object_system(system_obj):
+    """(models, embeddings) of system_obj as the dicts render_rays takes: nerf_pl keeps lists, [coarse, fine] and [xyz, dir]
+    (models/nerf_pl/rendering_nerfpl.py:138-140, 197)."""
+    models, embeddings = system_obj.models, system_obj.embeddings
+    if not isinstance(models, dict):
+        models = dict(zip(("coarse", "fine"), models))
+    if not isinstance(embeddings, dict):
+        embeddings = dict(zip(("xyz", "dir"), embeddings))
+    return models, embeddings
+
+
+def load_object_system(ckpt_path, device, N_importance=64, trusted=False):
+    """The object of app_reflect_newly_placed_objects from a nerf_pl checkpoint (eval.py:1041-1061): the pair of plain NeRF
+    fields -- MirrorNeRF without the optional heads, whose parameter names are nerf_pl's (models/nerf_pl/nerf_nerfpl.py:42-109)
+    -- filled from `nerf_coarse.*` and, with N_importance > 0, `nerf_fine.*`; .models / .embeddings are dicts."""
+    from . import checkpoint
+    models = {}
+    for key in ("coarse", "fine") if N_importance > 0 else ("coarse",):
+        m = MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=False, predict_mirror_mask=False)
+        checkpoint.load_ckpt(m, ckpt_path, model_name="nerf_" + key, trusted=trusted)
+        models[key] = m.to(device).eval()
+    return SimpleNamespace(models=models, embeddings={"xyz": Embedding(10), "dir": Embedding(4)})
+
+
 def _refuse_apps(args, models, kwargs):
     """The application flags batched_inference cannot honour, refused up front with the reason."""
-    if getattr(args, "app_reflect_newly_placed_objects", False):
-        raise NotImplementedError(
-            "app_reflect_newly_placed_objects is not supported: it needs D-NeRF / nerf_pl object models, and the reference "
-            "cannot run it either (pose_align is always None there, so pose_scale at eval.py:264 is never bound: "
-            "UnboundLocalError)")
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
+    if getattr(args, "app_reflect_newly_placed_objects", False):
+        obj_type = getattr(args, "obj_model_type", "d_nerf")                   # eval.py:108: the reference's default
+        if obj_type == "d_nerf":
+            raise NotImplementedError(
+                "app_reflect_newly_placed_objects with obj_model_type='d_nerf' is not supported: D-NeRF (a time-conditioned "
+                "deformation network) is a model this package does not have, and the reference cannot run the branch either "
+                "(pose_align is always None there, so pose_scale at eval.py:264 is never bound: UnboundLocalError).  nerf_pl "
+                "objects are supported: pass obj_model_type='nerf_pl' with system_obj= (load_object_system)")
+        if obj_type != "nerf_pl":
+            raise ValueError(f"args.obj_model_type must be 'nerf_pl' or 'd_nerf', not {obj_type!r}")
+        if kwargs.get("system_obj") is None:
+            raise ValueError("app_reflect_newly_placed_objects needs system_obj= (an object with .models and .embeddings, the "
+                             "radiance field of the object; load_object_system)")
+        for other in ("app_place_new_mirror", "app_reflection_substitution", "app_control_mirror_roughness"):
+            if getattr(args, other, False):
+                raise ValueError(f"app_reflect_newly_placed_objects cannot be combined with {other} (one application at a time)")
+        if not ("fine" in models and kwargs.get("_N_importance", 1) > 0 and not getattr(args, "only_one_field", False)
+                and getattr(models["fine"], "predict_mirror_mask", False)):
+            raise ValueError("app_reflect_newly_placed_objects needs a fine mirror mask (N_importance > 0, not only_one_field, "
+                             "predict_mirror_mask=True): the reference clears mirror_mask_fine where the object is seen "
+                             "(eval.py:291)")
+        if getattr(args, "near", None) is None:
+            raise ValueError("app_reflect_newly_placed_objects needs args.near: the occlusion test compares the depth with it "
+                             "(eval.py:169-171, 275-281)")
+        return
     if not (place or subst):
         return
     which = "app_place_new_mirror" if place else "app_reflection_substitution"
@@ -150,6 +232,30 @@ def _transform_rays(sec, xform):
     tx, ty, tz = xform["translation"]
     _lib.check(_lib.lib().mnrf_transform_rays(_lib.ptr(sec), sec.shape[0], rot, float(xform["scale"]), tx, ty, tz, _lib.stream()),
                "mnrf_transform_rays")
+
+
+def _merge_object(r, rays_chunk, xform, near, n_used, render):
+    """eval.py:173-291 on one level's maps, in place: the level's rays moved into the object's frame (mnrf_object_rays), the
+    object field rendered for colour, depth and opacity (`render`: rays -> dict), and its maps merged where the object is
+    opaque and not hidden by the scene (mnrf_object_merge).  The mirror flag is cleared there BEFORE the caller's hard clip,
+    as in the reference; x_surface and the normals are not edited (the reference does not edit them either)."""
+    N = rays_chunk.shape[0]
+    if N == 0:
+        return
+    p = _lib.ptr
+    obj_rays = torch.empty_like(rays_chunk)
+    pose = (ctypes.c_float * 12)(*xform["pose"]) if xform["pose"] is not None else None
+    tx, ty, tz = xform["translation"]
+    _lib.check(_lib.lib().mnrf_object_rays(p(rays_chunk), N, pose, xform["scale"], tx, ty, tz, p(obj_rays), _lib.stream()),
+               "mnrf_object_rays")
+    o = render(obj_rays)
+    for k in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
+        if k in r and not r[k].is_contiguous():
+            r[k] = r[k].contiguous()
+    _lib.check(_lib.lib().mnrf_object_merge(
+        p(o["rgb_fine"].contiguous()), p(o["depth_fine"].contiguous()), p(o["opacity_fine"].contiguous()), N, xform["scale"],
+        xform["pose_scale0"], float(near), p(r["rgb_fine"]), p(r["depth_fine"]), p(r.get("mirror_mask_fine")), p(n_used),
+        _lib.stream()), "mnrf_object_merge")
 
 
 def _f(dev, *s):
@@ -524,11 +630,26 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     the mirror mask right behind the threshold (mnrf_place_mirror), `new_mirror=dict(axis=, position=, normal=, rect=)`
     overrides the preset; args.app_reflection_substitution with system_substitution= (.models, .embeddings): the level-0
     reflections are moved by the args.root_dir preset (SUBSTITUTION_PRESETS, mnrf_transform_rays) and rendered once by
-    that system.  Both may be combined, as in the reference."""
+    that system.  Both may be combined, as in the reference.
+
+    args.app_reflect_newly_placed_objects with args.obj_model_type="nerf_pl" (the reference's default "d_nerf" is refused),
+    system_obj= (.models: the nerf_pl list [coarse, fine] or a dict; .embeddings: [xyz, dir] or a dict; load_object_system) and
+    args.near: at EVERY recursion level, the last one included, the level's rays are moved into the object's frame by the
+    args.root_dir preset (OBJECT_PRESETS; `new_object=dict(pose_align=None | 3x4 | 4x4, scale=, translation=)` overrides it),
+    the object field is rendered for colour, depth and opacity, and where the object is opaque and not hidden by the scene it
+    gives the level's colour and depth and clears the mirror flag (mnrf_object_rays, mnrf_object_merge) -- so the object is
+    seen in the mirrors too.  Not combined with another application.  object_used= (a device int32 tensor of one element,
+    zeroed here): receives the number of rays, over all levels, that took the object."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
-    _refuse_apps(args, models, kwargs)
+    _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
+    objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
+    obj_xform = resolve_new_object(args, kwargs.get("new_object")) if objects else None
+    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if objects else (None, None)
+    obj_used = kwargs.get("object_used") if objects else None
+    if obj_used is not None:
+        obj_used.zero_()
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
     plane = resolve_new_mirror(args, kwargs.get("new_mirror")) if place else None
@@ -577,6 +698,8 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                         _rgb_depth_only=rgb_depth)
         r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
         r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
+        if objects:                                                       # eval.py:173-291, ahead of the hard clip
+            _merge_object(r, rays_chunk, obj_xform, args.near, obj_used, render_object)
         mask = None
         for key in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse"):
             if key in r:
@@ -596,6 +719,11 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
             else:
                 any_mirror = _threshold_(mask, want_any=not last, edit=edit)
         return r, rays_chunk, level, mask, any_mirror, pending
+
+    def render_object(obj_rays):
+        # eval.py:221-232: only colour, depth and opacity of this render are read -- the maps-only path
+        return render_rays(obj_models, obj_embeddings, obj_rays, N_samples, use_disp, 0, 0, N_importance, chunk, white_back,
+                           test_time=True, compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
 
     def recurse(rays_chunk, level):
         return stage_b(stage_a(rays_chunk, level))
@@ -723,7 +851,8 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         torch.cuda.current_stream().synchronize()
     # range guard of the split arithmetic, once per call (= per frame): a tripped model is on the fp32 kernels now
     from .mirror_nerf import check_guard, release_transient
-    guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else [])
+    guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else []) + \
+        (list(obj_models.values()) if objects else [])
     if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard(guarded):
         try:
             return batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk,

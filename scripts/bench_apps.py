@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""Cost of app_place_new_mirror (run.sh MODE 3) on the bench.py workload (BASELINE config 2: the synthetic 800x800 frame, 64 coarse
+"""Cost of app_place_new_mirror (run.sh MODE 3) and app_reflect_newly_placed_objects (run.sh MODE 4) on the bench.py workload (BASELINE config 2: the synthetic 800x800 frame, 64 coarse
 + 192 fine samples per ray, chunk 32768, the all-mirror random-init pair) through mirror_nerf_amd.batched_inference.
 
 Prints ONE JSON line: ms per frame with the application off (max_recursive_level 1, the bench.py call) and with the new mirror
 (default plane_x preset, args.near = 0.05) at max_recursive_level 2 and 50; per run the rays rendered per recursion level (the
 rows of every render_rays call of one frame, summed per level) and the rays whose level-0 depth the new mirror replaced (= hits
-of the new mirror on the primary rays).  One warm-up frame, then the median of --reps frames; result maps stay on the GPU
+of the new mirror on the primary rays).  The object leg (--no_object skips it) renders the same frame at max_recursive_level 1
+with and without a nerf_pl object -- the seeded random-init plain pair with the density tweaks of fixture g26_object_office_l2,
+moved by the office preset -- and reports both times, the rows of the render_rays calls (scene and object renders alternate, so
+two entries per level) and the rays, over all levels, that took the object.  By construction the object costs about one more field pass per level; nothing is asserted on the time.  One warm-up frame, then the median of --reps frames; result maps stay on the GPU
 (to_cpu=False, as bench.py).
 
-    python scripts/bench_apps.py [--reps 3] [--levels 2 50]
+    python scripts/bench_apps.py [--reps 3] [--levels 2 50] [--no_object]
 """
 import argparse
 import json
@@ -32,6 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--levels", type=int, nargs="+", default=[2, 50])
+    ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
     a = ap.parse_args()
     dev = "cuda:0"
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
@@ -46,9 +50,11 @@ def main():
         calls.append(int(r.shape[0]))
         return orig(models_, embeddings, r, *args_, **kw)
 
+    extra = {}
+
     def frame(args):
         return M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=args, trace_secondary_rays=True,
-                                   to_cpu=False)
+                                   to_cpu=False, **extra)
 
     n_chunks = (rays.shape[0] + CHUNK - 1) // CHUNK
 
@@ -94,6 +100,25 @@ def main():
         res[f"place_mirror_l{lv}"] = {"ms_per_frame": round(ms, 2), "ms_reps": [round(x, 2) for x in t], "new_mirror_hits_level0": hits,
                                       "merged_mirror_rays_level0": int(out["mirror_mask_fine"].sum().item()),
                                       "rays_per_level": traced, "vs_app_off": round(ms / ms_off, 2)}
+    if not a.no_object:
+        # the object of fixture g26_object_office_l2: seed 7, density head x 1000 with the fixture's biases
+        from types import SimpleNamespace
+        obj_models = {}
+        for name, sd, bias in zip(("coarse", "fine"), SY.make_state_dict(7, 2, predict_normal=False, predict_mirror_mask=False),
+                                  (6.18, 44.94)):
+            SY.apply_tweaks(sd, [["sigma.weight", "mul", 1000.0], ["sigma.bias", "set", bias]])
+            m = M.MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=False, predict_mirror_mask=False)
+            m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+            obj_models[name] = m.to(dev).eval()
+        used = torch.zeros(1, dtype=torch.int32, device=dev)
+        extra.update(system_obj=SimpleNamespace(models=obj_models, embeddings=emb), object_used=used)
+        args = dict(base_args, app_reflect_newly_placed_objects=True, obj_model_type="nerf_pl", root_dir="office", near=0.05)
+        out, ms, t, traced = run(args)
+        extra.clear()
+        res["object_l1"] = {"ms_per_frame": round(ms, 2), "ms_reps": [round(x, 2) for x in t], "rays_per_render_call": traced,
+                            "rays_that_took_the_object": int(used.item()),
+                            "changed_rays": int((out["rgb_fine"] != off["rgb_fine"]).any(-1).sum().item()),
+                            "vs_app_off": round(ms / ms_off, 2)}
     print(json.dumps(res))
 
 

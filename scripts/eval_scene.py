@@ -26,8 +26,13 @@ GIF `{exp}_rgb_{typ}.gif` (eval.py:897-903; exp = --exp_name, by default the las
 second) is written with PIL.  That GIF is NOT pinned against imageio's: the frames are the PNGs' bytes, the palette and the
 container are PIL's.
 
+A newly placed object (run.sh MODE 4): --app_reflect_newly_placed_objects --obj_ckpt_path PATH --obj_model_type nerf_pl loads
+the object's nerf_pl checkpoint (recursion.load_object_system) and hands it to batched_inference, which shows the object in
+the scene and in its mirrors; the preset of the ray move follows --root_dir as in the reference.  --obj_model_type defaults to
+the reference's d_nerf, which batched_inference refuses.
+
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
-and the scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
+and the other scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
 frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -73,6 +78,11 @@ def get_opts(argv=None):
     ap.add_argument("--near", type=float, default=2.0)
     ap.add_argument("--far", type=float, default=6.0)
     ap.add_argument("--workers", type=int, default=8, help="PNG-writing threads (at most 16)")
+    # the new-object application, named as in the reference's eval.py
+    ap.add_argument("--app_reflect_newly_placed_objects", action="store_true",
+                    help="show a newly placed object in the scene and in its mirrors")
+    ap.add_argument("--obj_ckpt_path", type=str, default=None, help="radiance field of the object (a nerf_pl checkpoint)")
+    ap.add_argument("--obj_model_type", type=str, default="d_nerf", choices=("nerf_pl", "d_nerf"))
     return ap.parse_args(argv)
 
 
@@ -88,12 +98,26 @@ def load_system(args, device):
     return system
 
 
-def render(system, rays, args):
+def load_object(args, device):
+    """The object system of --app_reflect_newly_placed_objects (eval.py:1035-1061), None without the flag."""
+    if not args.app_reflect_newly_placed_objects:
+        return None
+    if args.obj_ckpt_path is None:
+        raise SystemExit("[Error] obj_ckpt_path should be appointed in app_reflect_newly_placed_objects.")
+    if args.obj_model_type != "nerf_pl":
+        return None          # batched_inference refuses d_nerf with the reason
+    from mirror_nerf_amd.recursion import load_object_system
+    print("[info] Load object radiance field from ckpt:", args.obj_ckpt_path)
+    return load_object_system(args.obj_ckpt_path, device, args.N_importance, trusted=args.trusted)
+
+
+def render(system, rays, args, system_obj=None):
     """The per-ray maps of one frame, on the device."""
     import mirror_nerf_amd as M
+    extra = {"system_obj": system_obj} if system_obj is not None else {}
     return M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
                                args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
-                               white_back=args.white_back, to_cpu=False, maps_only=True)
+                               white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
 
 
 def save_pfm(path, image):
@@ -156,6 +180,7 @@ def main(argv=None):
             bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
         n_frames, frame_of = bank.n_frames, bank.frame
     system = load_system(args, dev)
+    system_obj = load_object(args, dev)
 
     out = args.out_dir
     dirs = {"rgb": out, "mirror_mask": os.path.join(out, "mirror_mask"), "depth": os.path.join(out, "depth"),
@@ -181,7 +206,7 @@ def main(argv=None):
     with ThreadPoolExecutor(max_workers=max(1, min(16, args.workers))) as pool:
         for i in range(n_frames):
             sample = frame_of(i)
-            results = render(system, sample["rays"], args)
+            results = render(system, sample["rays"], args, system_obj)
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
