@@ -216,7 +216,8 @@ __global__ void sample_kernel(MnrfLossArgs A, int typ, const float* counts, floa
     const bool in = j < A.n_rays * S;
     const long long ray = in ? j / S : 0;
     const bool valid = in && (A.valid_mask ? A.valid_mask[ray] != 0 : true);
-    const float inv = 1.f / (counts[C_VALID] * (float)S);
+    // no valid ray: the term is mean([]) = nan (below) and its gradients are zero like autograd's, not 0 * inf
+    const float inv = counts[C_VALID] > 0.f ? 1.f / (counts[C_VALID] * (float)S) : 0.f;
     const float d[3] = {A.rays[ray * 8 + 3], A.rays[ray * 8 + 4], A.rays[ray * 8 + 5]};
     const float w = in ? A.weights[typ][j] : 0.f;
     float total = 0.f, gw = 0.f;
