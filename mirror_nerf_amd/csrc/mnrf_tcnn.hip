@@ -906,8 +906,12 @@ struct TcnnBwdArgs {
     // a scale under which NO entry can overflow: tcnn_bwd_kernel writes dL/d encoding as planes [NL][B] float2 and, per level,
     // S = sum over the samples of max(|e0|, |e1|) -- the interpolation weights of a sample add up to 1, so no entry of the level can
     // collect more than S in either feature, however the samples collide (all rays of a batch leave one camera: 6 400 adds to one
-    // entry of level 4 in a 1024-ray batch) -- and tcnn_scatter_fx_kernel scatters with the power of two that puts S at 2^30.
-    // The fixed-point step is S * 2^-30: with B = 196 608 samples typically 2^-16 of the level's largest contribution.
+    // entry of level 4 in a 1024-ray batch) -- and tcnn_scatter_fx_kernel scatters with the power of two that puts S into
+    // [0.98 * 2^30, 2^31) (fx_scale below: the 32-bit halves are signed, |sum| < 2^31 suffices).  The fixed-point step is then at
+    // most S * 2^-30 and the rounding of one add at most half of it.  Measured against float64 (bound 6, uniform
+    // samples): at B = 196 608 the step is 2e-6 .. 4e-6 (2^-19 .. 2^-18) of a level's LARGEST ENTRY and the worst entry of a level is
+    // off by 2.1e-5 of it (fp32 atomics: 6e-6); both grow with B (6.4e-5 at 524 365 samples), which is why the Python shim leaves
+    // fixed point above FIXED_MAX_SAMPLES.
     float2* genc;                                // planes (caller's workspace) or null
     double* ssum;                                // [NL] S per level (zeroed by the launcher)
     unsigned long long* fx;                      // (entries) packed fixed-point sums (zeroed by the launcher)
@@ -1600,12 +1604,19 @@ __global__ __launch_bounds__(BT) void tcnn_bwd2_kernel(TcnnBwdArgs P) {
 #undef GR
 
 // d_table[level entries] += sum of the level's private copies
-// power of two k with k * S <= 2^30, S = the level's bound on any entry's sum (TcnnBwdArgs::ssum)
-__device__ __forceinline__ float fx_scale(double S) {
+// power of two k with k * S < 2^31 - 2^25, S = the level's bound on any entry's sum (TcnnBwdArgs::ssum).  A half of the packed word
+// holds |sum| < 2^31.  An entry's integer sum is at most k S plus half a unit per add, and an entry takes at most 8 adds per sample:
+// with B <= 2^22 samples that is 2^24.  The fp32 roundings between S and the integers -- of the interpolation weights (their sum
+// may exceed 1 by a few 2^-24), of the wave reduction of max(|e0|, |e1|) that S is summed from, and of the run aggregation -- are
+// each a few 2^-24 relative, together below k S 2^-20 <= 2^11.  The 2^25 kept free covers all of it.  So k = 2^(31-e) while the mantissa m of S = m 2^e leaves that room
+// (m <= 1 - 2^-6), else 2^(30-e), as for any larger B: k S lies in [0.98 * 2^30, 2^31), where it was [2^29, 2^30) -- one more bit
+// for every level at the cost of nothing.  (k stays a power of two: the last bits of S depend on the order of its atomic adds,
+// the exponent does not, so the sums stay reproducible bit for bit.)
+__device__ __forceinline__ float fx_scale(double S, long long B) {
     if (!(S > 0.0)) return 0.f;                                           // nothing to add on this level
     int e;
-    (void)frexp(S, &e);                                                   // S = m 2^e, m in [0.5, 1): S < 2^e
-    const int p = 30 - e;
+    const double mant = frexp(S, &e);                                     // S = m 2^e, m in [0.5, 1): S < 2^e
+    const int p = (mant <= 1.0 - 0.015625 && B <= (1ll << 22) ? 31 : 30) - e;
     if (p < -120 || p > 120) return 0.f;                                  // (gradients outside any sane range: leave the level out)
     return __uint_as_float((unsigned)(127 + p) << 23);
 }
@@ -1667,13 +1678,13 @@ __global__ __launch_bounds__(256) void tcnn_scatter_fx_kernel(TcnnBwdArgs P) {
                 continue;
             }
             const bool head = aggregate_runs(P, lv, pg, v0, v1, active, lane);
-            const float k = fx_scale(P.ssum[lv]);
+            const float k = fx_scale(P.ssum[lv], A.Bs);
             if (!(active && head) || k == 0.f) continue;
             unsigned long long* fx = P.fx + A.off[lv];
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const unsigned idx = grid_index(pg[0] + (c & 1), pg[1] + ((c >> 1) & 1), pg[2] + ((c >> 2) & 1), hsize, res, A.mode[lv]);
-                const long long q0 = (long long)__float2int_rn(v0[c] * k), q1 = (long long)__float2int_rn(v1[c] * k);      // (|v k| <= 2^30)
+                const long long q0 = (long long)__float2int_rn(v0[c] * k), q1 = (long long)__float2int_rn(v1[c] * k);      // (|v k| < 2^31)
                 if (q0 | q1) atomicAdd(fx + idx, (unsigned long long)((q1 << 32) + q0));
             }
         }
@@ -1685,7 +1696,7 @@ __global__ void tcnn_fold_fx_kernel(TcnnBwdArgs P) {
     const TcnnArgs& A = P.f;
     const int lv = blockIdx.y;
     if (P.cp_n[lv]) return;
-    const float k = fx_scale(P.ssum[lv]);
+    const float k = fx_scale(P.ssum[lv], A.Bs);
     if (k == 0.f) return;
     const float inv = 1.f / k;
     const unsigned n = A.off[lv + 1] - A.off[lv];

@@ -54,6 +54,10 @@ GRAD_F16 = os.environ.get("MNRF_TCNN_GRAD_F16", "0") == "1"
 # (one MFMA per product, fp32 accumulation; ~1e-3 relative) instead of hi/lo pairs at fp32 accuracy -- "fp16 MLP on CDNA4 MFMA"
 # as BASELINE config 5 words it; the sigma-only launches then run on the matrix pipe too.  The backward recomputes in fp32.
 GRAD_FIXED = os.environ.get("MNRF_TCNN_GRAD_FIXED", "1") != "0"
+# The fixed-point step of a level is its S 2^-30 at most, S = the level's sum of gradient magnitudes over ALL samples of the call: it
+# grows linearly with the sample count while a level's largest entry does not.  Measured against float64: within 4e-5 of
+# each level's largest entry up to 262 144 samples per backward call; above that the scatter goes back to fp32 atomics.
+FIXED_MAX_SAMPLES = 262144
 MLP_F16 = os.environ.get("MNRF_TCNN_F16", "0") == "1"
 # module.table_f16 (env MNRF_TCNN_TABLE_F16=1 sets the default): the kernels gather from a half2 copy of the table (4 B per entry,
 # tinycudann's storage) instead of the fp32 master; see MirrorNeRFTcnn._table
@@ -139,8 +143,8 @@ class TcnnFieldFn(torch.autograd.Function):
         flags = ctx.cut | (_lib.MNRF_TCNN_GRAD_F16 if getattr(m, "table_grad_f16", GRAD_F16) else 0)
         # table_grad_fixed (module attribute, default on; MNRF_TCNN_GRAD_FIXED=0 turns it off): one 64-bit integer atomic per table
         # entry -- two 32-bit fixed-point halves under the step's own per-level scale -- instead of two fp32 atomics: exact integer
-        # sums (bitwise reproducible), 17 bits below the largest contribution of a level, 4.1 -> 3.0 ms per 1024-ray step
-        if not (flags & _lib.MNRF_TCNN_GRAD_F16) and getattr(m, "table_grad_fixed", GRAD_FIXED):
+        # sums (bitwise reproducible), 4.1 -> 3.0 ms per 1024-ray step; up to FIXED_MAX_SAMPLES samples per call (see there)
+        if not (flags & _lib.MNRF_TCNN_GRAD_F16) and getattr(m, "table_grad_fixed", GRAD_FIXED) and B <= FIXED_MAX_SAMPLES:
             flags |= _lib.MNRF_TCNN_GRAD_FIXED
             n_copies = _lib.lib().mnrf_tcnn_backward_workspace_floats(offs)
             ws = torch.empty(max(1, _lib.lib().mnrf_tcnn_backward_workspace_floats3(offs, flags, B)), dtype=torch.float32, device=dev)

@@ -151,7 +151,7 @@ def test_tcnn_backward_matches_torch_autograd(bound, B, which):
             rel = ((gv - wv).abs().max(-1).values / (wv.abs().max(-1).values + 1e-3 * scale))
             assert float(rel.median()) <= 1e-4 and float((rel < 1e-2).float().mean()) > 0.97, (k, float(rel.median()))
         else:
-            # table: the default scatter is fixed point, 2^-17 of a level's largest contribution per add (MNRF_TCNN_GRAD_FIXED)
+            # table: the default scatter is fixed point, a step of at most S 2^-30 per add, S = the level's sum of gradient magnitudes
             assert err <= (6e-5 if k == "encoder.embeddings" else 2e-5) * scale + 1e-7, (k, err, scale)
     # untouched table entries stay exactly zero
     assert int((got["encoder.embeddings"] != 0).sum()) <= B * 16 * 8 * 2
