@@ -878,6 +878,30 @@ int mnrf_resample_u8(const uint8_t* src, int64_t frames, int src_h, int src_w, i
 int mnrf_mask_nearest(const void* src, int sample_bytes, int64_t frames, int src_h, int src_w, int8_t* dst, int dst_h, int dst_w,
                       void* stream);
 
+/* ---- the D-NeRF object field (csrc/mnrf_dnerf.hip; models/d_nerf/run_dnerf_helpers.py:70-253, DirectTemporalNeRF with D = 8,
+ * W = 256, skips = [4], multires 10 / 4, use_viewdirs): a deformation net (_time.0..7, _time_out) that moves a point by dx at
+ * time t, and a canonical NeRF (_occ) evaluated on the encoding of x + dx.  fp32 matrix instructions only.
+ *
+ * The packed image: `params` is a HOST array of MNRF_DNERF_N_PARAMS device pointers in state_dict order -- _occ.pts_linears.0..7,
+ * _occ.views_linears.0, _occ.feature_linear, _occ.alpha_linear, _occ.rgb_linear, _time.0..7, _time_out, weight then bias each
+ * (nn.Linear layout (out,in) row-major).  The image holds no device state: launches only read it. */
+#define MNRF_DNERF_N_PARAMS 42
+#define MNRF_DNERF_SIGMA_ONLY 1u   /* stop in front of the colour branch (the coarse pass): rgb is not written */
+#define MNRF_DNERF_RAW_RGB 2u      /* rgb without the sigmoid (the module's forward; raw2outputs applies it) */
+#define MNRF_DNERF_CANONICAL 4u    /* t == 0 with zero_canonical (run_dnerf_helpers.py:147-148): the deformation net is not
+                                    * evaluated, dx is written as zeros */
+int64_t mnrf_dnerf_packed_floats(void);
+int mnrf_dnerf_pack_weights(const float* const* params, float* packed, void* stream);
+/* DirectTemporalNeRF.forward on B samples at ONE time t.  Positions, view encoding and null outputs as in mnrf_field_forward:
+ * `xyz` rows or o + d*z from `rays` (n_rays, 8) and `z_vals` (n_rays, spr) (separate multiply and add), `dir_emb` rows of 27
+ * floats with row index sample / spr (not read with MNRF_DNERF_SIGMA_ONLY).  The 21 channels of the time encoding are the same
+ * for every sample: their product with _time.0's last 21 columns is added to that layer's bias once per workgroup.
+ * Outputs (null = skip): sigma (B) raw, rgb (B,3) after the sigmoid (raw with MNRF_DNERF_RAW_RGB), dx (B,3).  The canonical
+ * trunk sees the encoding of x + dx (one fp32 add).  Rows past B are not written. */
+int mnrf_dnerf_forward(const float* packed, unsigned flags, int64_t B, const float* xyz, int64_t xyz_stride, const float* rays,
+                       const float* z_vals, int spr, const float* dir_emb, int64_t dir_stride, float t, float* sigma, float* rgb,
+                       float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,10 @@ MNRF_TCNN_GRAD_F16 = 16
 MNRF_DETACH_W_MASK = 1
 MNRF_DETACH_W_NORMAL = 2
 N_PARAMS = 32
+MNRF_DNERF_SIGMA_ONLY = 1      # flags of mnrf_dnerf_forward
+MNRF_DNERF_RAW_RGB = 2
+MNRF_DNERF_CANONICAL = 4
+DNERF_N_PARAMS = 42
 
 # name -> (restype, argtypes): exactly the prototypes of include/mnrf.h
 SIGNATURES = {
@@ -191,6 +195,10 @@ SIGNATURES = {
     "mnrf_resample_u8": (_int, [ctypes.c_void_p, _i64, _int, _int, _int, ctypes.c_void_p, _int, _int, _c_i, _c_i, _int, _c_i, _c_i, _int,
                                 ctypes.c_void_p, _str]),
     "mnrf_mask_nearest": (_int, [ctypes.c_void_p, _int, _i64, _int, _int, ctypes.c_void_p, _int, _int, _str]),
+    # ---- the D-NeRF object field (csrc/mnrf_dnerf.hip)
+    "mnrf_dnerf_packed_floats": (_i64, []),
+    "mnrf_dnerf_pack_weights": (_int, [ctypes.POINTER(ctypes.c_void_p), _c_f, _str]),
+    "mnrf_dnerf_forward": (_int, [_c_f, _u32, _i64, _c_f, _i64, _c_f, _c_f, _int, _c_f, _i64, _flt, _c_f, _c_f, _c_f, _str]),
 }
 
 _lib = None

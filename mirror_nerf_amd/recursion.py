@@ -6,9 +6,9 @@
     applications that need only MirrorNeRF fields -- a new planar mirror (app_place_new_mirror,
     eval.py:311-320, 364-504; run.sh MODE 3), reflection substitution (app_reflection_substitution,
     eval.py:550-613: the reflections are rendered by a second system) and a newly placed object
-    (app_reflect_newly_placed_objects, eval.py:173-291; run.sh MODE 4) whose field is a nerf_pl model:
-    the plain NeRF this package already runs (MirrorNeRF without the optional heads).  The other object
-    type of the reference, D-NeRF (a time-conditioned deformation network), is refused (see _refuse_apps).
+    (app_reflect_newly_placed_objects, eval.py:173-291; run.sh MODE 4) whose field is a nerf_pl model
+    (the plain NeRF this package already runs: MirrorNeRF without the optional heads) or a D-NeRF
+    model (a time-conditioned deformation network in front of a canonical NeRF: dnerf.py).
 
 Python here is the recursion driver only: mask thresholding, reflected-ray construction,
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
@@ -27,6 +27,7 @@ from torch import nn
 
 from . import _lib
 from .mirror_nerf import Embedding, MirrorNeRF
+from .dnerf import render_rays_dnerf
 from .rendering import render_rays
 
 RAY_FORWARD_OFFSET = 0.1   # train.py:232, eval.py:529 (absolute near of a reflected ray)
@@ -161,14 +162,19 @@ def _refuse_apps(args, models, kwargs):
     if getattr(args, "app_reflect_newly_placed_objects", False):
         obj_type = getattr(args, "obj_model_type", "d_nerf")                   # eval.py:108: the reference's default
         if obj_type == "d_nerf":
-            raise NotImplementedError(
-                "app_reflect_newly_placed_objects with obj_model_type='d_nerf' is not supported: D-NeRF (a time-conditioned "
-                "deformation network) is a model this package does not have, and the reference cannot run the branch either "
-                "(pose_align is always None there, so pose_scale at eval.py:264 is never bound: UnboundLocalError).  nerf_pl "
-                "objects are supported: pass obj_model_type='nerf_pl' with system_obj= (load_object_system)")
-        if obj_type != "nerf_pl":
+            if kwargs.get("render_kwargs_test_d_nerf") is None:
+                raise NotImplementedError(
+                    "app_reflect_newly_placed_objects with obj_model_type='d_nerf' needs the D-NeRF object itself: pass "
+                    "render_kwargs_test_d_nerf= (dnerf.load_dnerf_object: network_fn / network_fine are DirectTemporalNeRF "
+                    "modules) and frame_time=, the reference's own keyword names.  (The reference cannot run the branch as it "
+                    "stands: pose_align is always None there, so pose_scale at eval.py:264 is never bound: UnboundLocalError.)  "
+                    "A nerf_pl object is passed as obj_model_type='nerf_pl' with system_obj= (load_object_system)")
+            if kwargs.get("frame_time") is None:
+                raise ValueError("app_reflect_newly_placed_objects with a D-NeRF object needs frame_time= (the object's time in "
+                                 "[0, 1], eval.py:1130, 1154)")
+        elif obj_type != "nerf_pl":
             raise ValueError(f"args.obj_model_type must be 'nerf_pl' or 'd_nerf', not {obj_type!r}")
-        if kwargs.get("system_obj") is None:
+        elif kwargs.get("system_obj") is None:
             raise ValueError("app_reflect_newly_placed_objects needs system_obj= (an object with .models and .embeddings, the "
                              "radiance field of the object; load_object_system)")
         for other in ("app_place_new_mirror", "app_reflection_substitution", "app_control_mirror_roughness"):
@@ -632,8 +638,10 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     reflections are moved by the args.root_dir preset (SUBSTITUTION_PRESETS, mnrf_transform_rays) and rendered once by
     that system.  Both may be combined, as in the reference.
 
-    args.app_reflect_newly_placed_objects with args.obj_model_type="nerf_pl" (the reference's default "d_nerf" is refused),
-    system_obj= (.models: the nerf_pl list [coarse, fine] or a dict; .embeddings: [xyz, dir] or a dict; load_object_system) and
+    args.app_reflect_newly_placed_objects with args.obj_model_type="nerf_pl" and system_obj= (.models: the nerf_pl list
+    [coarse, fine] or a dict; .embeddings: [xyz, dir] or a dict; load_object_system), or with args.obj_model_type="d_nerf" (the
+    reference's default) and render_kwargs_test_d_nerf= (dnerf.load_dnerf_object) plus frame_time= (the object's time: it moves
+    from frame to frame, and its reflection with it; args_d_nerf= is accepted and unused), and
     args.near: at EVERY recursion level, the last one included, the level's rays are moved into the object's frame by the
     args.root_dir preset (OBJECT_PRESETS; `new_object=dict(pose_align=None | 3x4 | 4x4, scale=, translation=)` overrides it),
     the object field is rendered for colour, depth and opacity, and where the object is opaque and not hidden by the scene it
@@ -646,7 +654,9 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
     objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
     obj_xform = resolve_new_object(args, kwargs.get("new_object")) if objects else None
-    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if objects else (None, None)
+    obj_dnerf = kwargs.get("render_kwargs_test_d_nerf") if objects and getattr(args, "obj_model_type", "d_nerf") == "d_nerf" else None
+    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if objects and obj_dnerf is None else (None, None)
+    frame_time = float(kwargs["frame_time"]) if obj_dnerf is not None else None
     obj_used = kwargs.get("object_used") if objects else None
     if obj_used is not None:
         obj_used.zero_()
@@ -721,6 +731,13 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         return r, rays_chunk, level, mask, any_mirror, pending
 
     def render_object(obj_rays):
+        if obj_dnerf is not None:
+            # eval.py:233-259: the time in column 8, the normalised directions behind it (a plain division); near and far are
+            # the rays' own columns 6 and 7; samples, background and models come from the OBJECT's configuration
+            d = obj_rays[:, 3:6]
+            batch = torch.cat([obj_rays, torch.full_like(obj_rays[:, :1], frame_time), d / torch.norm(d, dim=-1, keepdim=True)], -1)
+            o = render_rays_dnerf(batch, **dict(obj_dnerf, _frame_time=frame_time))
+            return {"rgb_fine": o["rgb_map"], "depth_fine": o["depth_map"], "opacity_fine": o["acc_map"]}
         # eval.py:221-232: only colour, depth and opacity of this render are read -- the maps-only path
         return render_rays(obj_models, obj_embeddings, obj_rays, N_samples, use_disp, 0, 0, N_importance, chunk, white_back,
                            test_time=True, compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
@@ -852,7 +869,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     # range guard of the split arithmetic, once per call (= per frame): a tripped model is on the fp32 kernels now
     from .mirror_nerf import check_guard, release_transient
     guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else []) + \
-        (list(obj_models.values()) if objects else [])
+        (list(obj_models.values()) if obj_models is not None else [])      # (a D-NeRF object runs fp32 only: no guard)
     if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard(guarded):
         try:
             return batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk,

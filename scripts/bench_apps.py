@@ -8,10 +8,12 @@ rows of every render_rays call of one frame, summed per level) and the rays whos
 of the new mirror on the primary rays).  The object leg (--no_object skips it) renders the same frame at max_recursive_level 1
 with and without a nerf_pl object -- the seeded random-init plain pair with the density tweaks of fixture g26_object_office_l2,
 moved by the office preset -- and reports both times, the rows of the render_rays calls (scene and object renders alternate, so
-two entries per level) and the rays, over all levels, that took the object.  By construction the object costs about one more field pass per level; nothing is asserted on the time.  One warm-up frame, then the median of --reps frames; result maps stay on the GPU
+two entries per level) and the rays, over all levels, that took the object.  The D-NeRF leg (--no_dnerf skips it) does the same with
+the two-model D-NeRF object of fixture g27_dnerf_office_l2 (64 + 64 samples per ray of its own, frame_time 0.37): its render is
+not a render_rays call, so the rows are per level.  By construction the object costs about one more field pass per level; nothing is asserted on the time.  One warm-up frame, then the median of --reps frames; result maps stay on the GPU
 (to_cpu=False, as bench.py).
 
-    python scripts/bench_apps.py [--reps 3] [--levels 2 50] [--no_object]
+    python scripts/bench_apps.py [--reps 3] [--levels 2 50] [--no_object] [--no_dnerf]
 """
 import argparse
 import json
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--levels", type=int, nargs="+", default=[2, 50])
     ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
+    ap.add_argument("--no_dnerf", action="store_true", help="skip the leg with a D-NeRF object")
     a = ap.parse_args()
     dev = "cuda:0"
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
@@ -119,6 +122,29 @@ def main():
                             "rays_that_took_the_object": int(used.item()),
                             "changed_rays": int((out["rgb_fine"] != off["rgb_fine"]).any(-1).sum().item()),
                             "vs_app_off": round(ms / ms_off, 2)}
+    if not a.no_dnerf:
+        # the object of fixture g27_dnerf_office_l2: seed 7, two models, density head x 1000 with the fixture's biases
+        from mirror_nerf_amd.dnerf import DirectTemporalNeRF
+        torch.manual_seed(7)
+        nets = []
+        for bias in (7.06, -5.08):
+            m = DirectTemporalNeRF()
+            with torch.no_grad():
+                m._occ.alpha_linear.weight.mul_(1000.0)
+                m._occ.alpha_linear.bias.fill_(bias)
+            nets.append(m.to(dev).eval())
+        used = torch.zeros(1, dtype=torch.int32, device=dev)
+        kw = dict(network_fn=nets[0], network_fine=nets[1], N_samples=64, N_importance=64, white_bkgd=False, use_two_models_for_fine=True,
+                  lindisp=False, perturb=False, raw_noise_std=0.0)
+        extra.update(render_kwargs_test_d_nerf=kw, frame_time=0.37, object_used=used)
+        args = dict(base_args, app_reflect_newly_placed_objects=True, obj_model_type="d_nerf", root_dir="office", near=0.05)
+        out, ms, t, traced = run(args)
+        extra.clear()
+        res["dnerf_object_l1"] = {"ms_per_frame": round(ms, 2), "ms_reps": [round(x, 2) for x in t], "rays_per_level": traced,
+                                  "object_samples_per_ray": "64 coarse (density only) + 128 fine", "frame_time": 0.37,
+                                  "rays_that_took_the_object": int(used.item()),
+                                  "changed_rays": int((out["rgb_fine"] != off["rgb_fine"]).any(-1).sum().item()),
+                                  "vs_app_off": round(ms / ms_off, 2)}
     print(json.dumps(res))
 
 

@@ -84,6 +84,9 @@ def main():
         (r"field_kernelILb[01]ELb0EE", fwd32), (r"field_kernelILb[01]ELb1EE", dict(fwd32, scratch_inside_max=4)),
         (r"field_bwd2?_kernel", grad32)])
     ok &= o and n >= 9
+    # the D-NeRF object field (mnrf_dnerf.hip): the same hand-placed scheme over two networks in one launch
+    o, n5 = check_object("mnrf_dnerf.o", "v_mfma_f32_16x16x4_f32", [(r"dnerf_kernel", fwd32)])
+    ok &= o and n5 >= 4
     fwd16 = dict(min_counted=100, counted_re=r"s_waitcnt lgkmcnt\([24]\)", scratch_inside_max=0, scratch_total_max=0)
     grad16 = dict(fwd16, scratch_inside_max=400, scratch_total_max=600)
     o, n2 = check_object("mnrf_field_split.o", "v_mfma_f32_16x16x32_f16", [

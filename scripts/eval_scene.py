@@ -28,8 +28,9 @@ container are PIL's.
 
 A newly placed object (run.sh MODE 4): --app_reflect_newly_placed_objects --obj_ckpt_path PATH --obj_model_type nerf_pl loads
 the object's nerf_pl checkpoint (recursion.load_object_system) and hands it to batched_inference, which shows the object in
-the scene and in its mirrors; the preset of the ray move follows --root_dir as in the reference.  --obj_model_type defaults to
-the reference's d_nerf, which batched_inference refuses.
+the scene and in its mirrors; the preset of the ray move follows --root_dir as in the reference.  --obj_model_type d_nerf (the
+reference's default) loads a D-NeRF `.tar` checkpoint with the `config.txt` beside it (dnerf.load_dnerf_object) and renders
+frame i at frame_time = i / n_frames (eval.py:1130, 1154): the object moves from frame to frame, and in the mirrors with it.
 
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
 and the other scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
@@ -81,7 +82,7 @@ def get_opts(argv=None):
     # the new-object application, named as in the reference's eval.py
     ap.add_argument("--app_reflect_newly_placed_objects", action="store_true",
                     help="show a newly placed object in the scene and in its mirrors")
-    ap.add_argument("--obj_ckpt_path", type=str, default=None, help="radiance field of the object (a nerf_pl checkpoint)")
+    ap.add_argument("--obj_ckpt_path", type=str, default=None, help="radiance field of the object (a nerf_pl .ckpt, or a D-NeRF .tar beside its config.txt)")
     ap.add_argument("--obj_model_type", type=str, default="d_nerf", choices=("nerf_pl", "d_nerf"))
     return ap.parse_args(argv)
 
@@ -99,22 +100,26 @@ def load_system(args, device):
 
 
 def load_object(args, device):
-    """The object system of --app_reflect_newly_placed_objects (eval.py:1035-1061), None without the flag."""
+    """The object of --app_reflect_newly_placed_objects (eval.py:1035-1077) as the keyword of batched_inference that carries
+    it: {"system_obj": ...} for a nerf_pl object, {"render_kwargs_test_d_nerf": ...} for a D-NeRF one; {} without the flag."""
     if not args.app_reflect_newly_placed_objects:
-        return None
+        return {}
     if args.obj_ckpt_path is None:
         raise SystemExit("[Error] obj_ckpt_path should be appointed in app_reflect_newly_placed_objects.")
-    if args.obj_model_type != "nerf_pl":
-        return None          # batched_inference refuses d_nerf with the reason
-    from mirror_nerf_amd.recursion import load_object_system
     print("[info] Load object radiance field from ckpt:", args.obj_ckpt_path)
-    return load_object_system(args.obj_ckpt_path, device, args.N_importance, trusted=args.trusted)
+    if args.obj_model_type == "d_nerf":
+        from mirror_nerf_amd.dnerf import load_dnerf_object
+        return {"render_kwargs_test_d_nerf": load_dnerf_object(args.obj_ckpt_path, device, trusted=args.trusted)}
+    from mirror_nerf_amd.recursion import load_object_system
+    return {"system_obj": load_object_system(args.obj_ckpt_path, device, args.N_importance, trusted=args.trusted)}
 
 
-def render(system, rays, args, system_obj=None):
-    """The per-ray maps of one frame, on the device."""
+def render(system, rays, args, obj=None, frame_time=None):
+    """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object."""
     import mirror_nerf_amd as M
-    extra = {"system_obj": system_obj} if system_obj is not None else {}
+    extra = dict(obj or {})
+    if "render_kwargs_test_d_nerf" in extra:
+        extra["frame_time"] = frame_time
     return M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
                                args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
                                white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
@@ -206,7 +211,7 @@ def main(argv=None):
     with ThreadPoolExecutor(max_workers=max(1, min(16, args.workers))) as pool:
         for i in range(n_frames):
             sample = frame_of(i)
-            results = render(system, sample["rays"], args, system_obj)
+            results = render(system, sample["rays"], args, system_obj, frame_time=i / n_frames)      # eval.py:1130
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
