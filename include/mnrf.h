@@ -229,6 +229,42 @@ int mnrf_object_rays(const float* rays, int64_t n_rays, const float* pose, float
 int mnrf_object_merge(const float* obj_rgb, const float* obj_depth, const float* obj_opacity, int64_t n_rays, float scale,
                       float pose_scale0, float near, float* rgb, float* depth, float* mask, int32_t* n_used, void* stream);
 
+/* ---- Object bounds: render a placed object only along the rays that can see it.  csrc/mnrf_object_cull.hip.
+ *
+ * Bounds are a box [box_lo, box_hi] in the OBJECT's frame cut into Rx x Ry x Rz cells; cell (i, j, k) is the closed box
+ * lo + (i..i+1, j..j+1, k..k+1) * (hi - lo) / R.  One bit per cell says whether the object may have density there: 32 cells
+ * per uint32 along x (cell i is bit i % 32 of word i / 32), rows padded to whole words, so bits holds
+ * Rz * Ry * ceil(Rx / 32) words with (k * Ry + j) * ceil(Rx / 32) + i / 32 the word of cell (i, j, k); padding bits are zero. */
+#define MNRF_OBJECT_MAX_RES 1024
+
+/* The bits of a density volume.  volume: (Rz+1, Ry+1, Rx+1) float32 samples at the cells' corners (x fastest).  A cell is
+ * set when one of its 8 corners has `!(sigma < sigma_min)` (a NaN corner sets the cell); with dilate = 1 the set is then grown
+ * by one cell over the 26-neighbourhood (dilate: 0 or 1).  *n_set (int32, device, null = skip) receives the number of set
+ * cells.  Deterministic.  Rx, Ry, Rz in 1..MNRF_OBJECT_MAX_RES. */
+int mnrf_occupancy_bits(const float* volume, int Rx, int Ry, int Rz, float sigma_min, int dilate, uint32_t* bits,
+                        int32_t* n_set, void* stream);
+
+/* Keep the rays of one level (n_rays,8) whose segment can touch a set cell.  pose, scale, tx, ty, tz: as mnrf_object_rays;
+ * per ray the object-frame ray q is computed by the very device function of mnrf_object_rays.  box_lo, box_hi: HOST arrays of
+ * 3 floats, finite, lo < hi.  bits: null = the whole box counts as one set cell (Rx, Ry, Rz are then not read).
+ * The rule, on q as written in fp32, with the segment {o + d z : z in [q[6], q[7]]}:
+ *   kept for certain:   a ray whose segment, in exact arithmetic, intersects a set cell; a ray with a non-finite component;
+ *   culled for certain: a ray whose segment does not intersect the set cells grown by one cell extent per axis
+ * (the implementation decides in float64 against cells grown by 2^-12 of their extent: the band in between is that thin).
+ * An empty segment (far < near) is culled.  Kept rays are written compacted and in source order: out_rays (n_rays,8) row p
+ * = q of ray index[p], index (n_rays) int32 strictly increasing, *count (int32, device) their number; rows from *count on are
+ * not defined (index is also the pass's scratch).  No atomic decides an order.  out_rays must not be rays. */
+int mnrf_object_cull(const float* rays, int64_t n_rays, const float* pose, float scale, float tx, float ty, float tz,
+                     const float* box_lo, const float* box_hi, int Rx, int Ry, int Rz, const uint32_t* bits,
+                     float* out_rays, int32_t* index, int32_t* count, void* stream);
+
+/* mnrf_object_merge's per-ray rule (the same device function) for the kept rays: row i of the object's maps (rendered on
+ * out_rays) against row index[i] of the level's maps, for i < min(*count, capacity); *count is read on the device.  Rows of
+ * the level's maps that index does not list are not touched.  mask, n_used: as mnrf_object_merge. */
+int mnrf_object_merge_indexed(const float* obj_rgb, const float* obj_depth, const float* obj_opacity, const int32_t* index,
+                              const int32_t* count, int64_t capacity, float scale, float pose_scale0, float near, float* rgb,
+                              float* depth, float* mask, int32_t* n_used, void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

@@ -120,6 +120,11 @@ SIGNATURES = {
     "mnrf_transform_rays": (_int, [_c_f, _i64, ctypes.POINTER(ctypes.c_float), _flt, _flt, _flt, _flt, _str]),
     "mnrf_object_rays": (_int, [_c_f, _i64, ctypes.POINTER(ctypes.c_float), _flt, _flt, _flt, _flt, _c_f, _str]),
     "mnrf_object_merge": (_int, [_c_f, _c_f, _c_f, _i64, _flt, _flt, _flt, _c_f, _c_f, _c_f, _c_i, _str]),
+    # ---- object bounds (csrc/mnrf_object_cull.hip)
+    "mnrf_occupancy_bits": (_int, [_c_f, _int, _int, _int, _flt, _int, ctypes.c_void_p, _c_i, _str]),
+    "mnrf_object_cull": (_int, [_c_f, _i64, ctypes.POINTER(ctypes.c_float), _flt, _flt, _flt, _flt, ctypes.POINTER(ctypes.c_float),
+                                ctypes.POINTER(ctypes.c_float), _int, _int, _int, ctypes.c_void_p, _c_f, _c_i, _c_i, _str]),
+    "mnrf_object_merge_indexed": (_int, [_c_f, _c_f, _c_f, _c_i, _c_i, _i64, _flt, _flt, _flt, _c_f, _c_f, _c_f, _c_i, _str]),
     "mnrf_generate_rays": (_int, [_int, _int, _flt, ctypes.POINTER(ctypes.c_float), _flt, _flt, _c_f, _str]),
     "mnrf_loss_workspace_floats": (_i64, [_i64, _int, _int, _i64]),
     "mnrf_total_loss": (_int, [ctypes.c_void_p, _c_f, _str]),     # const MnrfLossArgs* (losses._Args)

@@ -10,6 +10,7 @@
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
+#include "mnrf_object.h"
 
 namespace {
 
@@ -102,67 +103,25 @@ __global__ __launch_bounds__(256) void transform_rays_kernel(XformArgs A) {
 }
 
 struct ObjectRaysArgs {
-    const float* rays; long long n; int posed; float A[9]; float p[3]; float scale; float t[3]; float* out;
+    const float* rays; long long n; mnrf_object::Move move; float* out;
 };
 
-// eval.py:175-217, out of place: with a pose o = A o + p (two steps: the product, then the sum), d = l2_normalize(A d)
-// (utils/func.py:5-7); then o = o * scale, then o = o + t (two roundings); near / far are copied
+// eval.py:175-217, out of place (mnrf_object.h move_ray, shared with the cull of mnrf_object_cull.hip)
 __global__ __launch_bounds__(256) void object_rays_kernel(ObjectRaysArgs A) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    const float* r = A.rays + i * 8;
-    float* q = A.out + i * 8;
-    float o[3] = {r[0], r[1], r[2]};
-    float d[3] = {r[3], r[4], r[5]};
-    if (A.posed) {
-        float ro[3], rd[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            ro[k] = A.A[k * 3 + 0] * o[0] + A.A[k * 3 + 1] * o[1] + A.A[k * 3 + 2] * o[2];
-            rd[k] = A.A[k * 3 + 0] * d[0] + A.A[k * 3 + 1] * d[1] + A.A[k * 3 + 2] * d[2];
-        }
-        const float len = sqrtf(fmaxf(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2], EPS32));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o[k] = ro[k] + A.p[k];
-            d[k] = rd[k] / len;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float scaled = o[k] * A.scale;
-        q[k] = scaled + A.t[k];
-        q[3 + k] = d[k];
-    }
-    q[6] = r[6];
-    q[7] = r[7];
+    mnrf_object::move_ray(A.move, A.rays + i * 8, A.out + i * 8);
 }
 
 struct ObjectMergeArgs {
-    const float* obj_rgb; const float* obj_depth; const float* obj_opacity; long long n; float scale; float pose_scale0; float near;
-    float* rgb; float* depth; float* mask; int* n_used;
+    const float* obj_rgb; const float* obj_depth; const float* obj_opacity; long long n; mnrf_object::Merge merge; int* n_used;
 };
 
-// eval.py:261-291 on one ray: the object's depth back in the scene's units (two divisions, in the reference's order), the
-// object where it is opaque (`> 0.8` of the accumulated weight, depth > 0: "remove white bg") and not behind the scene's
-// foreground (the scene's depth of this level, valid when beyond the global near).  Comparisons with NaN are false.
+// eval.py:261-291, one thread per ray (mnrf_object.h merge_ray, shared with mnrf_object_merge_indexed)
 __global__ __launch_bounds__(256) void object_merge_kernel(ObjectMergeArgs A) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     bool use = false;
-    if (i < A.n) {
-        const float d = A.obj_depth[i] / A.scale / A.pose_scale0;                                  // eval.py:261-265
-        const float depth = A.depth[i];
-        const bool obj = d > 0.f && A.obj_opacity[i] > 0.8f;                                       // eval.py:268-272
-        const bool blocked = d > depth && depth > A.near;                                          // eval.py:275-281, 169-171
-        use = obj && !blocked;                                                                     // eval.py:282-284
-        if (use) {                                                                                 // eval.py:285-291
-            A.rgb[i * 3 + 0] = A.obj_rgb[i * 3 + 0];
-            A.rgb[i * 3 + 1] = A.obj_rgb[i * 3 + 1];
-            A.rgb[i * 3 + 2] = A.obj_rgb[i * 3 + 2];
-            A.depth[i] = d;
-            if (A.mask) A.mask[i] = 0.f;
-        }
-    }
+    if (i < A.n) use = mnrf_object::merge_ray(A.merge, A.obj_rgb, A.obj_depth, A.obj_opacity, i, i);
     if (A.n_used) {
         const unsigned long long b = __ballot(use);
         if (b != 0ull && (threadIdx.x & 63) == 0) atomicAdd(A.n_used, __popcll(b));
@@ -205,13 +164,7 @@ extern "C" int mnrf_object_rays(const float* rays, int64_t n_rays, const float* 
     if (n_rays == 0) return MNRF_OK;
     if (!rays || !out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_rays: null pointer");
     if (rays == out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_rays: works out of place (out must not be rays)");
-    ObjectRaysArgs A{rays, (long long)n_rays, pose != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}, scale,
-                     {tx, ty, tz}, out};
-    if (pose)
-        for (int k = 0; k < 3; ++k) {
-            for (int j = 0; j < 3; ++j) A.A[k * 3 + j] = pose[k * 4 + j];
-            A.p[k] = pose[k * 4 + 3];
-        }
+    ObjectRaysArgs A{rays, (long long)n_rays, mnrf_object::make_move(pose, scale, tx, ty, tz), out};
     hipLaunchKernelGGL(object_rays_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, A);
     return mnrf_check_launch("mnrf_object_rays");
 }
@@ -222,7 +175,7 @@ extern "C" int mnrf_object_merge(const float* obj_rgb, const float* obj_depth, c
     if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_merge: bad size");
     if (n_rays == 0) return MNRF_OK;
     if (!obj_rgb || !obj_depth || !obj_opacity || !rgb || !depth) return mnrf_fail(MNRF_ERR_ARG, "mnrf_object_merge: null pointer");
-    ObjectMergeArgs A{obj_rgb, obj_depth, obj_opacity, (long long)n_rays, scale, pose_scale0, near, rgb, depth, mask, n_used};
+    ObjectMergeArgs A{obj_rgb, obj_depth, obj_opacity, (long long)n_rays, {scale, pose_scale0, near, rgb, depth, mask}, n_used};
     hipLaunchKernelGGL(object_merge_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, A);
     return mnrf_check_launch("mnrf_object_merge");
 }

@@ -13,7 +13,8 @@
 Python here is the recursion driver only: mask thresholding, reflected-ray construction,
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
-mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge.  One 4-byte device->host read per level decides
+mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
+mnrf_object_merge_indexed).  One 4-byte device->host read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
@@ -240,15 +241,34 @@ def _transform_rays(sec, xform):
                "mnrf_transform_rays")
 
 
-def _merge_object(r, rays_chunk, xform, near, n_used, render):
+def _merge_object(r, rays_chunk, xform, near, n_used, render, bounds=None):
     """eval.py:173-291 on one level's maps, in place: the level's rays moved into the object's frame (mnrf_object_rays), the
     object field rendered for colour, depth and opacity (`render`: rays -> dict), and its maps merged where the object is
     opaque and not hidden by the scene (mnrf_object_merge).  The mirror flag is cleared there BEFORE the caller's hard clip,
-    as in the reference; x_surface and the normals are not edited (the reference does not edit them either)."""
+    as in the reference; x_surface and the normals are not edited (the reference does not edit them either).
+
+    bounds (an ObjectBounds): only the rays whose object-frame segment can touch a set cell are rendered -- mnrf_object_cull
+    compacts them in order, ONE 4-byte device->host read says how many there are, `render` runs on those rows (not at all when
+    there are none) and mnrf_object_merge_indexed applies the same per-ray rule through their index.  The other rays stay as
+    the scene rendered them."""
     N = rays_chunk.shape[0]
     if N == 0:
         return
     p = _lib.ptr
+    if bounds is not None:
+        obj_rays, index, count = bounds.cull(rays_chunk, xform)
+        M = int(count.item())
+        if M == 0:
+            return
+        o = render(obj_rays[:M])
+        for k in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
+            if k in r and not r[k].is_contiguous():
+                r[k] = r[k].contiguous()
+        _lib.check(_lib.lib().mnrf_object_merge_indexed(
+            p(o["rgb_fine"].contiguous()), p(o["depth_fine"].contiguous()), p(o["opacity_fine"].contiguous()), p(index), p(count), M,
+            xform["scale"], xform["pose_scale0"], float(near), p(r["rgb_fine"]), p(r["depth_fine"]), p(r.get("mirror_mask_fine")),
+            p(n_used), _lib.stream()), "mnrf_object_merge_indexed")
+        return
     obj_rays = torch.empty_like(rays_chunk)
     pose = (ctypes.c_float * 12)(*xform["pose"]) if xform["pose"] is not None else None
     tx, ty, tz = xform["translation"]
@@ -262,6 +282,42 @@ def _merge_object(r, rays_chunk, xform, near, n_used, render):
         p(o["rgb_fine"].contiguous()), p(o["depth_fine"].contiguous()), p(o["opacity_fine"].contiguous()), N, xform["scale"],
         xform["pose_scale0"], float(near), p(r["rgb_fine"]), p(r["depth_fine"]), p(r.get("mirror_mask_fine")), p(n_used),
         _lib.stream()), "mnrf_object_merge")
+
+
+def resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, device):
+    """The `object_bounds=` keyword of batched_inference -> an ObjectBounds on `device`, or None.  "auto" estimates them from
+    the object's own density inside object_region=(lo, hi) at object_bounds_res (default 64) cells per axis
+    (object_bounds.estimate_object_bounds): once for a nerf_pl object, kept on system_obj; per call, at frame_time, for a
+    D-NeRF object, which moves."""
+    from .object_bounds import ObjectBounds, estimate_object_bounds
+    bounds = kwargs.get("object_bounds")
+    if bounds is None:
+        if kwargs.get("object_region") is not None:
+            raise ValueError("object_region= is the region object_bounds='auto' looks for the object in: pass object_bounds='auto'")
+        return None
+    if not objects:
+        raise ValueError("object_bounds= bounds the object of app_reflect_newly_placed_objects: the application is not on")
+    if isinstance(bounds, ObjectBounds):
+        return bounds.to(device)
+    if not (isinstance(bounds, str) and bounds == "auto"):
+        raise ValueError(f"object_bounds must be None, an ObjectBounds or 'auto', not {bounds!r}")
+    region = kwargs.get("object_region")
+    if region is None or len(region) != 2:
+        raise ValueError("object_bounds='auto' needs object_region=(lo, hi): the box of the object's frame to look for it in")
+    res = kwargs.get("object_bounds_res", 64)
+    lo, hi = (tuple(float(v) for v in c) for c in region)
+    if obj_dnerf is not None:
+        return estimate_object_bounds(obj_dnerf, lo, hi, res=res, frame_time=frame_time).to(device)
+    system_obj = kwargs["system_obj"]
+    key = (lo, hi, res, str(device))
+    cached = getattr(system_obj, "_mnrf_object_bounds", None)
+    if cached is None or cached[0] != key:
+        cached = (key, estimate_object_bounds(system_obj, lo, hi, res=res).to(device))
+        try:
+            system_obj._mnrf_object_bounds = cached
+        except AttributeError:      # (an object without a __dict__: estimated per call)
+            pass
+    return cached[1]
 
 
 def _f(dev, *s):
@@ -647,7 +703,12 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     the object field is rendered for colour, depth and opacity, and where the object is opaque and not hidden by the scene it
     gives the level's colour and depth and clears the mirror flag (mnrf_object_rays, mnrf_object_merge) -- so the object is
     seen in the mirrors too.  Not combined with another application.  object_used= (a device int32 tensor of one element,
-    zeroed here): receives the number of rays, over all levels, that took the object."""
+    zeroed here): receives the number of rays, over all levels, that took the object.
+    object_bounds= (None, the default: every ray of a level renders the object; an object_bounds.ObjectBounds; or "auto" with
+    object_region=(lo, hi) and optionally object_bounds_res=64, see resolve_object_bounds): the object is rendered only along
+    the rays whose segment, in the object's frame, can touch the bounds (mnrf_object_cull, mnrf_object_merge_indexed).  Those
+    rays get bit for bit what they get without bounds; the others stay as the scene rendered them.  Costs one more 4-byte
+    device->host read per chunk and level."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
@@ -658,6 +719,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if objects and obj_dnerf is None else (None, None)
     frame_time = float(kwargs["frame_time"]) if obj_dnerf is not None else None
     obj_used = kwargs.get("object_used") if objects else None
+    obj_bounds = resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, rays.device)
     if obj_used is not None:
         obj_used.zero_()
     place = bool(getattr(args, "app_place_new_mirror", False))
@@ -709,7 +771,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
         r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
         if objects:                                                       # eval.py:173-291, ahead of the hard clip
-            _merge_object(r, rays_chunk, obj_xform, args.near, obj_used, render_object)
+            _merge_object(r, rays_chunk, obj_xform, args.near, obj_used, render_object, obj_bounds)
         mask = None
         for key in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse"):
             if key in r:

@@ -14,6 +14,16 @@ not a render_rays call, so the rows are per level.  By construction the object c
 (to_cpu=False, as bench.py).
 
     python scripts/bench_apps.py [--reps 3] [--levels 2 50] [--no_object] [--no_dnerf]
+
+--obj_bounds runs the object-bounds leg INSTEAD (batched_inference(object_bounds=), on the D-NeRF leg's workload and object): the
+application off; then, alternating frame by frame after one warm-up each, the route without bounds and all-keeping bounds (a
++-1e6 box: every ray is kept, so the difference is the overhead of the cull, the count's read and the indexed merge); then
+boxes of the object's frame that about 50 %, 10 % and 2 % of the PRIMARY rays hit (a cube around the point the central pixel
+looks at, its size bisected with mnrf_object_cull), with the kept rays per level and the time the two parent figures predict,
+app_off + kept_fraction x (unculled - app_off).  The random-init object is opaque everywhere, so a culled frame is NOT the
+unculled frame: outside the box the object is simply absent.  Nothing is asserted on the times.
+
+    python scripts/bench_apps.py --obj_bounds [--reps 3]
 """
 import argparse
 import json
@@ -33,12 +43,148 @@ from mirror_nerf_amd import synthetic as SY  # noqa: E402
 from mirror_nerf_amd.benchlegs import ARGS, CHUNK, H, N_IMPORTANCE, N_SAMPLES, W  # noqa: E402
 
 
+def dnerf_object(dev):
+    """The object of fixture g27_dnerf_office_l2 as render_kwargs_test_d_nerf: seed 7, two models, density head x 1000 with the
+    fixture's biases."""
+    from mirror_nerf_amd.dnerf import DirectTemporalNeRF
+    torch.manual_seed(7)
+    nets = []
+    for bias in (7.06, -5.08):
+        m = DirectTemporalNeRF()
+        with torch.no_grad():
+            m._occ.alpha_linear.weight.mul_(1000.0)
+            m._occ.alpha_linear.bias.fill_(bias)
+        nets.append(m.to(dev).eval())
+    return dict(network_fn=nets[0], network_fine=nets[1], N_samples=64, N_importance=64, white_bkgd=False, use_two_models_for_fine=True,
+                lindisp=False, perturb=False, raw_noise_std=0.0)
+
+
+def bounds_leg(a, models, emb, rays, dev, base_args):
+    """The --obj_bounds leg (module docstring) -> the result dict."""
+    from mirror_nerf_amd import ObjectBounds
+    used = torch.zeros(1, dtype=torch.int32, device=dev)
+    obj = dict(render_kwargs_test_d_nerf=dnerf_object(dev), frame_time=0.37, object_used=used)
+    on_args = dict(base_args, app_reflect_newly_placed_objects=True, obj_model_type="d_nerf", root_dir="office", near=0.05)
+    from types import SimpleNamespace
+    xform = REC.resolve_new_object(SimpleNamespace(root_dir="office"))
+    n_chunks = (rays.shape[0] + CHUNK - 1) // CHUNK
+
+    def frame(args, **kw):
+        out = M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=args, trace_secondary_rays=True,
+                                  to_cpu=False, **kw)
+        torch.cuda.synchronize()
+        return out
+
+    def timed(args, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frame(args, **kw)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rows_per_level(bounds):
+        """(rows of the scene's renders, rows of the object's renders) of one unpipelined frame, by recursion level.  The scene's
+        render of the last level is the one batched_inference asks for colour and depth only; the object's render follows the
+        scene's render of its level (and is absent when no ray of the chunk was kept)."""
+        scene_rows, object_rows, level = [0, 0], [0, 0], [0]
+        scene, dn = REC.render_rays, REC.render_rays_dnerf
+
+        def count_scene(m_, e_, r, *x, **k):
+            level[0] = 1 if k.get("_rgb_depth_only") else 0
+            scene_rows[level[0]] += int(r.shape[0])
+            return scene(m_, e_, r, *x, **k)
+
+        def count_object(b, **k):
+            object_rows[level[0]] += int(b.shape[0])
+            return dn(b, **k)
+        REC.render_rays, REC.render_rays_dnerf = count_scene, count_object
+        os.environ["MNRF_EVAL_PIPELINE"] = "0"
+        try:
+            frame(on_args, object_bounds=bounds, **obj)
+        finally:
+            REC.render_rays, REC.render_rays_dnerf = scene, dn
+            os.environ.pop("MNRF_EVAL_PIPELINE")
+        return scene_rows, object_rows
+
+    res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "
+                       "all-mirror random-init pair (bench.py config 2), max_recursive_level 1; D-NeRF object of the dnerf_object_l1 leg "
+                       "(64 coarse + 128 fine samples per ray of its own, frame_time 0.37), office preset",
+           "protocol": f"one warm-up frame per route, then the median of {a.reps} frames; the two overhead routes alternate frame by frame",
+           "note": "the random-init object is opaque everywhere: a culled frame differs from the unculled one (outside the box the "
+                   "object is absent); kept rays are those of the unculled frame"}
+    frame(base_args)
+    t_off = [timed(base_args) for _ in range(a.reps)]
+    ms_off = statistics.median(t_off)
+    res["app_off"] = {"ms_per_frame": round(ms_off, 2), "ms_reps": [round(t, 2) for t in t_off]}
+    # overhead: no bounds against bounds that keep every ray
+    keep_all = ObjectBounds((-1e6,) * 3, (1e6,) * 3)
+    frame(on_args, **obj)
+    frame(on_args, object_bounds=keep_all, **obj)
+    t_none, t_all = [], []
+    for _ in range(a.reps):
+        t_none.append(timed(on_args, **obj))
+        t_all.append(timed(on_args, object_bounds=keep_all, **obj))
+    ms_none, ms_all = statistics.median(t_none), statistics.median(t_all)
+    took_all = int(used.item())
+    res["overhead"] = {"object_bounds_none": {"ms_per_frame": round(ms_none, 2), "ms_reps": [round(t, 2) for t in t_none]},
+                       "all_keeping_bounds": {"ms_per_frame": round(ms_all, 2), "ms_reps": [round(t, 2) for t in t_all],
+                                              "rays_that_took_the_object": took_all},
+                       "ratio": round(ms_all / ms_none, 4),
+                       "spread_of_reps": round(max(max(t) - min(t) for t in (t_none, t_all)) / ms_none, 4)}
+    scene_none, object_none = rows_per_level(None)
+    scene_all, object_all = rows_per_level(keep_all)
+    res["overhead"]["object_bounds_none"].update(rays_per_level=scene_none, object_rays_per_level=object_none)
+    res["overhead"]["all_keeping_bounds"].update(rays_per_level=scene_all, kept_rays_per_level=object_all)
+    # the two parent figures as costs per row: the scene's from app_off (every primary ray reflects once), the object's from the rest
+    # of the unculled frame
+    us_scene = ms_off * 1e3 / (2.0 * rays.shape[0])
+    us_object = (ms_none * 1e3 - us_scene * sum(scene_none)) / sum(object_none)
+    res["per_row_us"] = {"scene": round(us_scene, 4), "object": round(us_object, 4)}
+    # gain: cubes around the point the central pixel looks at (object frame, middle of its segment), bisected to the share
+    centre_ray = rays[(H // 2) * W + W // 2].double().cpu()
+    o = centre_ray[:3] * xform["scale"] + torch.tensor(xform["translation"], dtype=torch.float64)
+    c = (o + centre_ray[3:6] * 0.5 * (centre_ray[6] + centre_ray[7])).tolist()
+    n_primary = rays.shape[0]
+
+    def cube(h):
+        return ObjectBounds([v - h for v in c], [v + h for v in c])
+
+    def share(h):
+        return int(cube(h).cull(rays, xform)[2].item()) / n_primary
+
+    res["gain"] = {}
+    for target in (0.5, 0.1, 0.02):
+        lo_h, hi_h = 1e-4, 64.0
+        for _ in range(40):
+            mid = (lo_h * hi_h) ** 0.5
+            lo_h, hi_h = (mid, hi_h) if share(mid) < target else (lo_h, mid)
+        bounds = cube(hi_h)
+        frame(on_args, object_bounds=bounds, **obj)
+        t = [timed(on_args, object_bounds=bounds, **obj) for _ in range(a.reps)]
+        ms = statistics.median(t)
+        scene_rows, rows = rows_per_level(bounds)
+        # the issue's expectation, app_off + kept_fraction x (unculled - app_off), with the kept fraction over both levels of the
+        # app_off frame; and the expectation by rows, which also knows that this frame traces other rays than the unculled one (a ray
+        # that takes the object is no mirror any more: culling the object at level 0 leaves more rays to reflect)
+        frac = sum(rows) / (2.0 * n_primary)
+        expect = ms_off + frac * (ms_none - ms_off)
+        by_rows = (us_scene * sum(scene_rows) + us_object * sum(rows)) * 1e-3
+        res["gain"][f"primary_{target:g}"] = {
+            "box_half_size": round(hi_h, 5), "primary_rays_hit": round(share(hi_h), 4), "rays_per_level": scene_rows,
+            "kept_rays_per_level": rows, "kept_fraction_per_level": [round(k / max(n, 1), 4) for k, n in zip(rows, scene_rows)],
+            "ms_per_frame": round(ms, 2), "ms_reps": [round(x, 2) for x in t],
+            "kept_over_2x_primary": round(frac, 4), "expected_ms": round(expect, 2), "over_expectation_ms": round(ms - expect, 2),
+            "expected_ms_by_rows": round(by_rows, 2), "over_expectation_by_rows_ms": round(ms - by_rows, 2),
+            "rays_that_took_the_object": int(used.item()), "vs_unculled": round(ms / ms_none, 3)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--levels", type=int, nargs="+", default=[2, 50])
     ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
     ap.add_argument("--no_dnerf", action="store_true", help="skip the leg with a D-NeRF object")
+    ap.add_argument("--obj_bounds", action="store_true", help="run the object-bounds leg instead of the others")
     a = ap.parse_args()
     dev = "cuda:0"
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
@@ -89,6 +235,9 @@ def main():
         return out, statistics.median(times), times, traced
 
     base_args = dict(ARGS)
+    if a.obj_bounds:
+        print(json.dumps(bounds_leg(a, models, emb, rays, dev, base_args)))
+        return
     off, ms_off, t_off, traced_off = run(base_args)
     res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "
                        "all-mirror random-init pair (bench.py config 2)",
@@ -123,19 +272,8 @@ def main():
                             "changed_rays": int((out["rgb_fine"] != off["rgb_fine"]).any(-1).sum().item()),
                             "vs_app_off": round(ms / ms_off, 2)}
     if not a.no_dnerf:
-        # the object of fixture g27_dnerf_office_l2: seed 7, two models, density head x 1000 with the fixture's biases
-        from mirror_nerf_amd.dnerf import DirectTemporalNeRF
-        torch.manual_seed(7)
-        nets = []
-        for bias in (7.06, -5.08):
-            m = DirectTemporalNeRF()
-            with torch.no_grad():
-                m._occ.alpha_linear.weight.mul_(1000.0)
-                m._occ.alpha_linear.bias.fill_(bias)
-            nets.append(m.to(dev).eval())
         used = torch.zeros(1, dtype=torch.int32, device=dev)
-        kw = dict(network_fn=nets[0], network_fine=nets[1], N_samples=64, N_importance=64, white_bkgd=False, use_two_models_for_fine=True,
-                  lindisp=False, perturb=False, raw_noise_std=0.0)
+        kw = dnerf_object(dev)
         extra.update(render_kwargs_test_d_nerf=kw, frame_time=0.37, object_used=used)
         args = dict(base_args, app_reflect_newly_placed_objects=True, obj_model_type="d_nerf", root_dir="office", near=0.05)
         out, ms, t, traced = run(args)

@@ -31,6 +31,9 @@ the object's nerf_pl checkpoint (recursion.load_object_system) and hands it to b
 the scene and in its mirrors; the preset of the ray move follows --root_dir as in the reference.  --obj_model_type d_nerf (the
 reference's default) loads a D-NeRF `.tar` checkpoint with the `config.txt` beside it (dnerf.load_dnerf_object) and renders
 frame i at frame_time = i / n_frames (eval.py:1130, 1154): the object moves from frame to frame, and in the mirrors with it.
+--obj_bounds x0 y0 z0 x1 y1 z1 | auto renders the object only along the rays that can touch the given box of ITS frame, or
+the cells `auto` finds occupied inside --obj_region at --obj_bounds_res cells per axis (object_bounds.py): the rays that are
+kept get exactly what they get without the flag.
 
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
 and the other scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
@@ -84,7 +87,25 @@ def get_opts(argv=None):
                     help="show a newly placed object in the scene and in its mirrors")
     ap.add_argument("--obj_ckpt_path", type=str, default=None, help="radiance field of the object (a nerf_pl .ckpt, or a D-NeRF .tar beside its config.txt)")
     ap.add_argument("--obj_model_type", type=str, default="d_nerf", choices=("nerf_pl", "d_nerf"))
-    return ap.parse_args(argv)
+    ap.add_argument("--obj_bounds", nargs="+", default=None, metavar="x0 y0 z0 x1 y1 z1 | auto",
+                    help="render the object only along rays that can touch these bounds, in the OBJECT's frame: a box, or `auto` "
+                         "(estimated from the object's density inside --obj_region)")
+    ap.add_argument("--obj_region", nargs=6, type=float, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar="V",
+                    help="x0 y0 z0 x1 y1 z1 of the region `--obj_bounds auto` looks for the object in.  The default is the extent of the "
+                         "Blender-synthetic scenes such objects are trained in (cameras at radius 4, near 2, far 6): a guess, override it")
+    ap.add_argument("--obj_bounds_res", type=int, default=64, help="cells per axis of the estimated bounds")
+    args = ap.parse_args(argv)
+    if args.obj_bounds is not None:
+        if not args.app_reflect_newly_placed_objects:
+            ap.error("--obj_bounds bounds the object of --app_reflect_newly_placed_objects")
+        if args.obj_bounds != ["auto"]:
+            try:
+                args.obj_bounds = [float(v) for v in args.obj_bounds]
+            except ValueError:
+                args.obj_bounds = []
+            if len(args.obj_bounds) != 6:
+                ap.error("--obj_bounds takes six numbers (x0 y0 z0 x1 y1 z1) or `auto`")
+    return args
 
 
 def load_system(args, device):
@@ -114,12 +135,45 @@ def load_object(args, device):
     return {"system_obj": load_object_system(args.obj_ckpt_path, device, args.N_importance, trusted=args.trusted)}
 
 
+_BOUNDS = {}      # id(the nerf_pl object) -> its bounds: estimated once; a D-NeRF object is estimated per frame
+
+
+def object_bounds(args, obj, frame_time=None):
+    """--obj_bounds as the ObjectBounds batched_inference takes (None without the flag).  `auto` estimates them from the
+    object's density inside --obj_region and says what it found: the share of set cells, the tight box around them, and a
+    warning when set cells touch the region's border (the object may continue outside: widen --obj_region)."""
+    from mirror_nerf_amd import ObjectBounds, estimate_object_bounds
+    spec = getattr(args, "obj_bounds", None)
+    if spec is None or not obj:
+        return None
+    if spec != ["auto"]:
+        return ObjectBounds(spec[:3], spec[3:])
+    moving = "render_kwargs_test_d_nerf" in obj
+    target = obj["render_kwargs_test_d_nerf"] if moving else obj["system_obj"]
+    if not moving and id(target) in _BOUNDS:
+        return _BOUNDS[id(target)]
+    region = args.obj_region
+    b = estimate_object_bounds(target, region[:3], region[3:], res=args.obj_bounds_res, frame_time=frame_time if moving else None)
+    total = b.res[0] * b.res[1] * b.res[2]
+    when = f" at frame_time {frame_time:.4f}" if moving else ""
+    print(f"[info] object bounds{when}: {b.n_set} of {total} cells set ({100.0 * b.n_set / total:.1f} %), tight box {b.tight_box()}")
+    if b.touches_region_border():
+        print("[warning] object bounds: set cells touch the border of --obj_region; the object may continue outside it, where it "
+              "would be culled: widen --obj_region")
+    if not moving:
+        _BOUNDS[id(target)] = b
+    return b
+
+
 def render(system, rays, args, obj=None, frame_time=None):
     """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object."""
     import mirror_nerf_amd as M
     extra = dict(obj or {})
     if "render_kwargs_test_d_nerf" in extra:
         extra["frame_time"] = frame_time
+    bounds = object_bounds(args, obj, frame_time)
+    if bounds is not None:
+        extra["object_bounds"] = bounds
     return M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
                                args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
                                white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
