@@ -37,6 +37,11 @@
 extern "C" {
 #endif
 
+/* Marks a single-level pointer parameter as HOST memory, read (or written) during the call; every unmarked one is device memory
+ * (or `void* stream`, or an argument struct).  `T* const*` parameters are always host arrays of device pointers and carry no
+ * marker.  Expands to nothing: it is what the Python binding (mirror_nerf_amd/_abi.py) types the argument from. */
+#define MNRF_HOST
+
 #define MNRF_OK 0
 #define MNRF_ERR_ARG (-1)      /* bad argument (null pointer, size, flag combination) */
 #define MNRF_ERR_LAUNCH (-2)   /* HIP reported an error at launch */
@@ -207,7 +212,7 @@ int mnrf_place_mirror(const float* rays, int64_t n_rays, int axis, float positio
 /* Transform secondary rays (n_rays,8) in place before a reflection-substitution render (eval.py:550-594): with rotation (a
  * HOST array of 9 floats, row-major R; null = none) o = R o and d = l2_normalize(R d) (utils/func.py:5-7); then
  * o = o * scale + (tx, ty, tz).  Columns 6..7 (near, far) are left as they are. */
-int mnrf_transform_rays(float* rays, int64_t n_rays, const float* rotation, float scale, float tx, float ty, float tz,
+int mnrf_transform_rays(float* rays, int64_t n_rays, MNRF_HOST const float* rotation, float scale, float tx, float ty, float tz,
                         void* stream);
 
 /* Reflect a newly placed object (eval.py:173-291, app_reflect_newly_placed_objects; the object is a plain NeRF field that
@@ -217,7 +222,7 @@ int mnrf_transform_rays(float* rays, int64_t n_rays, const float* rotation, floa
  * (a HOST array of 12 floats, the row-major 3x4 [A | p] of the reference's pose_align; null = none) o = A o + p and
  * d = l2_normalize(A d) (utils/func.py:5-7); then o = o * scale, then o = o + (tx, ty, tz) -- two roundings, as the reference
  * writes them.  Columns 6..7 (near, far) are copied.  out (n_rays,8) must not be rays. */
-int mnrf_object_rays(const float* rays, int64_t n_rays, const float* pose, float scale, float tx, float ty, float tz,
+int mnrf_object_rays(const float* rays, int64_t n_rays, MNRF_HOST const float* pose, float scale, float tx, float ty, float tz,
                      float* out, void* stream);
 
 /* Merge the object's maps into the level's, ordered by depth (eval.py:261-291).  Per ray: d = obj_depth / scale / pose_scale0
@@ -254,8 +259,8 @@ int mnrf_occupancy_bits(const float* volume, int Rx, int Ry, int Rz, float sigma
  * An empty segment (far < near) is culled.  Kept rays are written compacted and in source order: out_rays (n_rays,8) row p
  * = q of ray index[p], index (n_rays) int32 strictly increasing, *count (int32, device) their number; rows from *count on are
  * not defined (index is also the pass's scratch).  No atomic decides an order.  out_rays must not be rays. */
-int mnrf_object_cull(const float* rays, int64_t n_rays, const float* pose, float scale, float tx, float ty, float tz,
-                     const float* box_lo, const float* box_hi, int Rx, int Ry, int Rz, const uint32_t* bits,
+int mnrf_object_cull(const float* rays, int64_t n_rays, MNRF_HOST const float* pose, float scale, float tx, float ty, float tz,
+                     MNRF_HOST const float* box_lo, MNRF_HOST const float* box_hi, int Rx, int Ry, int Rz, const uint32_t* bits,
                      float* out_rays, int32_t* index, int32_t* count, void* stream);
 
 /* mnrf_object_merge's per-ray rule (the same device function) for the kept rays: row i of the object's maps (rendered on
@@ -354,12 +359,12 @@ int mnrf_field_backward2(float* packed, int64_t B, const float* xyz, int64_t xyz
  * by level: planes[level * B + sample] = the level's two features (float2), 32 * B floats.  Samples: rows of `xyz` (stride >= 3)
  * or rays + z_vals.  The first of the two launches of mnrf_tcnn_forward(enc_workspace != null); bench.py prices it against the
  * L2 roofline (`hash_grid_variant.gather_roofline`). */
-int mnrf_tcnn_encode(const float* table, const int64_t* offsets17_host, double log2_per_level_scale, int base_resolution,
+int mnrf_tcnn_encode(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale, int base_resolution,
                      float bound, int64_t B, const float* xyz, int64_t xyz_stride, const float* rays, const float* z_vals,
                      int spr, float* planes, void* stream);
 
 /* ... with flags (0 or MNRF_TCNN_TABLE_F16), and the half2 copy of a table those launches read (entries = offsets[16]). */
-int mnrf_tcnn_encode_flags(const float* table, const int64_t* offsets17_host, double log2_per_level_scale, int base_resolution,
+int mnrf_tcnn_encode_flags(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale, int base_resolution,
                            float bound, int64_t B, const float* xyz, int64_t xyz_stride, const float* rays, const float* z_vals,
                            int spr, float* planes, unsigned flags, void* stream);
 int mnrf_tcnn_table_half(const float* table, int64_t entries, void* table_half, void* stream);
@@ -427,8 +432,8 @@ int mnrf_field_backward_planes(float* packed, int64_t B, const float* xyz, int64
 /* Weight gradients of n_eval (1..8) evaluations of one module: x_planes[e] from mnrf_field_forward_train, dy_planes[e] and
  * seedmax[e] from mnrf_field_backward_planes, B[e] their sample counts (HOST arrays).  d_params: HOST array of MNRF_N_PARAMS
  * device pointers, overwritten (accumulate = 0) or added to.  workspace: mnrf_dw_planes_workspace_floats(n_eval, B) floats. */
-int64_t mnrf_dw_planes_workspace_floats(int n_eval, const int64_t* B);
-int mnrf_dw_planes(int n_eval, const void* const* x_planes, const void* const* dy_planes, const int64_t* B,
+int64_t mnrf_dw_planes_workspace_floats(int n_eval, MNRF_HOST const int64_t* B);
+int mnrf_dw_planes(int n_eval, const void* const* x_planes, const void* const* dy_planes, MNRF_HOST const int64_t* B,
                    const uint32_t* const* seedmax, float* workspace, float* const* d_params, int accumulate, void* stream);
 
 /* Round 4: the second-order term (mnrf_field_backward2) on the planes route.  mnrf_field_backward2_planes runs the tangent pass
@@ -445,9 +450,9 @@ int mnrf_field_backward2_planes(float* packed, int64_t B, const float* xyz, int6
                                 const float* rays, const float* z_vals, int spr, const float* g_normal,
                                 const float* normal, const float* save_invj, const uint64_t* save_mask,
                                 void* x2_planes, void* y2_planes, uint32_t* jmax, float* d_xyz, void* stream);
-int64_t mnrf_dw_planes2_workspace_floats(int n_eval, const int64_t* B, const int* kinds);
-int mnrf_dw_planes2(int n_eval, const void* const* x_planes, const void* const* dy_planes, const int64_t* B,
-                    const uint32_t* const* seedmax, const int* kinds, float* workspace, float* const* d_params, int accumulate,
+int64_t mnrf_dw_planes2_workspace_floats(int n_eval, MNRF_HOST const int64_t* B, MNRF_HOST const int* kinds);
+int mnrf_dw_planes2(int n_eval, const void* const* x_planes, const void* const* dy_planes, MNRF_HOST const int64_t* B,
+                    const uint32_t* const* seedmax, MNRF_HOST const int* kinds, float* workspace, float* const* d_params, int accumulate,
                     void* stream);
 
 /* ---- optimizer step (training.FlatAdam) ------------------------------------------------------------------------------------
@@ -568,8 +573,8 @@ int mnrf_field_backward2_planes_n(float* packed, int64_t B, const float* xyz, in
  * workgroup contracts which 32-sample stages) is made by a one-workgroup launch in front of it and lives at the head of the
  * workspace: mnrf_dw_planes2_n_workspace_floats(n_eval) floats, whatever the counts. */
 int64_t mnrf_dw_planes2_n_workspace_floats(int n_eval);
-int mnrf_dw_planes2_n(int n_eval, const void* const* x_planes, const void* const* dy_planes, const int64_t* B,
-                      const int32_t* const* n_live, const int* spr, const uint32_t* const* seedmax, const int* kinds,
+int mnrf_dw_planes2_n(int n_eval, const void* const* x_planes, const void* const* dy_planes, MNRF_HOST const int64_t* B,
+                      const int32_t* const* n_live, MNRF_HOST const int* spr, const uint32_t* const* seedmax, MNRF_HOST const int* kinds,
                       float* workspace, float* const* d_params, int accumulate, void* stream);
 /* mnrf_adam_step with every scalar of the step in DEVICE memory (a captured step must not freeze the learning rate or the step
  * count).  mnrf_adam_prep, one thread: *step += 1 (the count of steps, this one included), then state[0..7] = [veto, lr / bias
@@ -583,7 +588,7 @@ int mnrf_adam_step_dev(float* param, const float* grad, float* exp_avg, float* e
                        int32_t* skipped, void* stream);
 /* mnrf_adam_step_dev for up to 4 flat tensors in ONE launch (a step's coarse and fine model): arrays of n_tensors entries each. */
 int mnrf_adam_step_dev_n(int n_tensors, float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
-                         const int64_t* n, const float* state, int32_t* const* skipped, void* stream);
+                         MNRF_HOST const int64_t* n, const float* state, int32_t* const* skipped, void* stream);
 
 /* ---- hash-grid field, BASELINE config 5 (models/mirror_nerf_tcnn.py:151-259) ---------------------
  * table: (entries, 2) fp32 hash-grid features; offsets17_host: 17 level offsets in entries (HOST);
@@ -599,7 +604,7 @@ int mnrf_tcnn_weight_floats(void);
 /* The blob from the model's 11 MLP parameter tensors (HOST array of device pointers in the order above: contiguous fp32 in
  * nn.Linear layout, models/mirror_nerf_tcnn.py:51-149) in one launch; padded columns and the tail are written as zeros. */
 int mnrf_tcnn_pack_weights(const float* const* params, float* weights, void* stream);
-int mnrf_tcnn_forward(const float* table, const int64_t* offsets17_host, double log2_per_level_scale,
+int mnrf_tcnn_forward(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale,
                       int base_resolution, float bound, const float* weights, unsigned flags, int64_t B,
                       const float* xyz, int64_t xyz_stride, const float* rays, const float* z_vals, int spr,
                       const float* dirs, int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
@@ -620,12 +625,12 @@ int mnrf_tcnn_forward(const float* table, const int64_t* offsets17_host, double 
  * adds the SECOND-ORDER term -- the gradient that reaches the table, sigma_net and the position through
  * normal = l2n(-d sigma/dx), i.e. what autograd.grad(sigma, x, create_graph=True) propagates in
  * models/mirror_nerf_tcnn.py:172-218 / utils/func.py:10-25 -- to d_table, d_weights and d_xyz. */
-int64_t mnrf_tcnn_backward_workspace_floats(const int64_t* offsets17_host);
-int64_t mnrf_tcnn_backward_workspace_floats2(const int64_t* offsets17_host, unsigned flags /* MNRF_TCNN_GRAD_F16 or 0 */);
+int64_t mnrf_tcnn_backward_workspace_floats(MNRF_HOST const int64_t* offsets17_host);
+int64_t mnrf_tcnn_backward_workspace_floats2(MNRF_HOST const int64_t* offsets17_host, unsigned flags /* MNRF_TCNN_GRAD_F16 or 0 */);
 /* With MNRF_TCNN_GRAD_F16 the LAST FOUR floats of that workspace are an overflow word (uint32, first of the four): non-zero after
  * the call when a half2 sum left the f16 range (it was clamped to +-65504 / scale, not inf) -- fall back to fp32 atomics then. */
-int64_t mnrf_tcnn_backward_workspace_floats3(const int64_t* offsets17_host, unsigned flags, int64_t B);
-int mnrf_tcnn_backward(const float* table, const int64_t* offsets17_host, double log2_per_level_scale,
+int64_t mnrf_tcnn_backward_workspace_floats3(MNRF_HOST const int64_t* offsets17_host, unsigned flags, int64_t B);
+int mnrf_tcnn_backward(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale,
                        int base_resolution, float bound, const float* weights, int64_t B, const float* xyz,
                        int64_t xyz_stride, const float* rays, const float* z_vals, int spr, const float* dirs,
                        int64_t dir_stride, const float* g_sigma, const float* g_rgb, const float* g_pred_normal,
@@ -641,12 +646,12 @@ int mnrf_tcnn_backward(const float* table, const int64_t* offsets17_host, double
  * below): ray mode only; B = the capacity the buffers (and the [level][B] planes) are sized for, the kernels evaluate / differentiate
  * the first *n_live * spr samples; rows past them are neither read nor written and add nothing to any gradient.  n_live null =
  * mnrf_tcnn_forward / mnrf_tcnn_backward. */
-int mnrf_tcnn_forward_n(const float* table, const int64_t* offsets17_host, double log2_per_level_scale,
+int mnrf_tcnn_forward_n(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale,
                         int base_resolution, float bound, const float* weights, unsigned flags, int64_t B,
                         const float* xyz, int64_t xyz_stride, const float* rays, const float* z_vals, int spr,
                         const float* dirs, int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
                         float* is_mirror, float* normal, float* geo_feat, float* enc_workspace, const int32_t* n_live, void* stream);
-int mnrf_tcnn_backward_n(const float* table, const int64_t* offsets17_host, double log2_per_level_scale,
+int mnrf_tcnn_backward_n(const float* table, MNRF_HOST const int64_t* offsets17_host, double log2_per_level_scale,
                          int base_resolution, float bound, const float* weights, int64_t B, const float* xyz,
                          int64_t xyz_stride, const float* rays, const float* z_vals, int spr, const float* dirs,
                          int64_t dir_stride, const float* g_sigma, const float* g_rgb, const float* g_pred_normal,
@@ -655,7 +660,7 @@ int mnrf_tcnn_backward_n(const float* table, const int64_t* offsets17_host, doub
                          const int32_t* n_live, void* stream);
 
 /* Pin-hole ray generation on device (datasets/ray_utils.py:6-53): rays (H*W, 8). */
-int mnrf_generate_rays(int H, int W, float focal, const float* c2w_host12, float near, float far,
+int mnrf_generate_rays(int H, int W, float focal, MNRF_HOST const float* c2w_host12, float near, float far,
                        float* rays, void* stream);
 
 /* ---- loss reductions of the training step (losses.py:7-255: ColorLoss, MirrorMaskLoss, PlaneConsistentLoss,
@@ -733,8 +738,8 @@ int mnrf_mse_psnr(const float* pred, const float* gt, const unsigned char* mask,
  * border is smaller and may take fewer tiles); 0 for a non-positive argument.  No atomics: deterministic, and
  * out[f] does not depend on the other frames.  H and W must hold a window, frames and channels must be positive. */
 int64_t mnrf_ssim_blocks(int H, int W, int frames, int channels);
-int mnrf_ssim(const float* pred, const int64_t* pred_strides4, const float* gt, const int64_t* gt_strides4, int H, int W,
-              int channels, int frames, const double* taps, int radius, int reflect, double cov_norm, double c1, double c2,
+int mnrf_ssim(const float* pred, MNRF_HOST const int64_t* pred_strides4, const float* gt, MNRF_HOST const int64_t* gt_strides4, int H, int W,
+              int channels, int frames, MNRF_HOST const double* taps, int radius, int reflect, double cov_norm, double c1, double c2,
               double* partials, float* out, float* map, void* stream);
 
 /* ---- mesh extraction (extract_color_mesh.py): density grid, marching cubes, connected components, vertex colours.
@@ -791,7 +796,7 @@ int mnrf_cc_count(const int32_t* triangles, int64_t n_triangles, const int32_t* 
  * occ_threshold), color_sum += colors * w, weight_sum += w (float64; a NaN opacity counts as 0, as numpy.nan_to_num does
  * the way the reference calls it). */
 int mnrf_project_colors(const float* vertices, int64_t n_vertices, const uint8_t* image, int H, int W,
-                        const double* w2c_host12, const float* origin_host3, float focal, float near, float* colors,
+                        MNRF_HOST const double* w2c_host12, MNRF_HOST const float* origin_host3, float focal, float near, float* colors,
                         double* depth, float* rays, void* stream);
 int mnrf_accumulate_colors(const float* colors, const double* depth, const float* opacity, float occ_threshold,
                            int64_t n_vertices, double* color_sum, double* weight_sum, void* stream);

@@ -33,11 +33,7 @@ from . import _lib
 from . import dist as D
 
 
-class _Bank(ctypes.Structure):
-    """MnrfBank of include/mnrf.h."""
-    _fields_ = [("poses", ctypes.c_void_p), ("images", ctypes.c_void_p), ("masks", ctypes.c_void_p), ("frames", ctypes.c_void_p),
-                ("n_frames", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("channels", ctypes.c_int),
-                ("slots", ctypes.c_int), ("focal", ctypes.c_float), ("near", ctypes.c_float), ("far", ctypes.c_float)]
+_Bank = _lib.STRUCTS["MnrfBank"]
 
 
 def _device_array(x, dtype, device, what):

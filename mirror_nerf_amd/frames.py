@@ -22,12 +22,7 @@ from . import _lib
 STEMS = ("rgb", "mirror_mask", "depth", "depth_reflect", "surface_normal", "surface_normal_grad", "x_surface")
 
 
-class _Maps(ctypes.Structure):          # MnrfFrameMaps
-    _fields_ = [(s, ctypes.c_void_p) for s in STEMS]
-
-
-class _Images(ctypes.Structure):        # MnrfFrameImages
-    _fields_ = [(s, ctypes.c_void_p) for s in STEMS]
+_Maps, _Images = _lib.STRUCTS["MnrfFrameMaps"], _lib.STRUCTS["MnrfFrameImages"]      # one field per stem
 
 
 def jet_table():

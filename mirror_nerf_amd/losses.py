@@ -24,23 +24,12 @@ from torch import nn
 from . import _lib
 
 _TYPS = ("coarse", "fine")
-_F = ctypes.c_void_p
+_Args = _lib.STRUCTS["MnrfLossArgs"]
 
-
-class _Args(ctypes.Structure):
-    """MnrfLossArgs of include/mnrf.h."""
-    _fields_ = [("rgb", _F * 2), ("mirror_mask", _F * 2), ("normal_dif", _F * 2), ("pred_normal", _F * 2),
-                ("weights", _F * 2), ("x_surface", _F * 2), ("normal_fine", _F), ("n_samples", ctypes.c_int * 2),
-                ("targets", _F), ("gt_mask", _F), ("rays", _F), ("valid_mask", _F), ("n_rays", ctypes.c_int64),
-                ("plane_idx", _F * 2), ("plane_times", ctypes.c_int64 * 2), ("plane_u", _F * 2), ("plane_cap", ctypes.c_int64 * 2),
-                ("w_color", ctypes.c_float), ("w_normal", ctypes.c_float), ("w_normal_reg", ctypes.c_float),
-                ("w_mask", ctypes.c_float), ("w_plane", ctypes.c_float), ("flags", ctypes.c_uint),
-                ("g_rgb", _F * 2), ("g_mirror_mask", _F * 2), ("g_normal_dif", _F * 2), ("g_pred_normal", _F * 2),
-                ("g_weights", _F * 2), ("g_x_surface", _F * 2), ("g_normal_fine", _F), ("out", _F)]
-
-
-FLAG_GEOMETRY_STAGE, FLAG_WO_MASK, FLAG_ONLY_INSIDE, FLAG_EXT_GRAD, FLAG_TCNN_BCE = 1, 2, 4, 8, 16
-FLAG_USE_MASK, FLAG_USE_PLANE, FLAG_USE_NORMAL, FLAG_PLANE_ON_DEVICE = 32, 64, 128, 256
+FLAG_GEOMETRY_STAGE, FLAG_WO_MASK, FLAG_ONLY_INSIDE = (_lib.MNRF_LOSS_GEOMETRY_STAGE, _lib.MNRF_LOSS_WO_MASK_RGB_TO_BLACK,
+                                                       _lib.MNRF_LOSS_NORMAL_ONLY_INSIDE_MIRROR)
+FLAG_EXT_GRAD, FLAG_TCNN_BCE, FLAG_USE_MASK = _lib.MNRF_LOSS_EXT_GRAD_NORMAL, _lib.MNRF_LOSS_TCNN_BCE, _lib.MNRF_LOSS_USE_MASK
+FLAG_USE_PLANE, FLAG_USE_NORMAL, FLAG_PLANE_ON_DEVICE = _lib.MNRF_LOSS_USE_PLANE, _lib.MNRF_LOSS_USE_NORMAL, _lib.MNRF_LOSS_PLANE_ON_DEVICE
 TERMS = ("color_loss", "mirror_mask_loss", "plane_consistent_loss", "normal_loss", "normal_reg_loss")
 
 # (dict key pattern, struct field, gradient field); order fixes the order of the autograd inputs

@@ -65,10 +65,12 @@ def set_precision(mode):
 # later step runs on fp32): a synchronous read there drains the queue before the optimizer step and costs 6 % of the step.
 # MNRF_GUARD=0 disables the host side.
 GUARD = os.environ.get("MNRF_GUARD", "1") != "0"
-GUARD_NAMES = {1: "an activation reached the f16 maximum (65504)", 2: "a weight is non-finite or >= 65504",
-               4: "a sample position has |x| >= 64 (encoding argument >= 2^15)",
-               128: "in a forward evaluation", 256: "in the training backward: a scaled activation gradient",
-               512: "in the second-order pass: a scaled tangent or signal"}
+GUARD_NAMES = {_lib.MNRF_GUARD_SATURATED: "an activation reached the f16 maximum (65504)",
+               _lib.MNRF_GUARD_WEIGHT: "a weight is non-finite or >= 65504",
+               _lib.MNRF_GUARD_ENC_RANGE: "a sample position has |x| >= 64 (encoding argument >= 2^15)",
+               _lib.MNRF_GUARD_IN_FORWARD: "in a forward evaluation",
+               _lib.MNRF_GUARD_IN_BACKWARD: "in the training backward: a scaled activation gradient",
+               _lib.MNRF_GUARD_IN_SECOND_ORDER: "in the second-order pass: a scaled tangent or signal"}
 
 
 def precision_of(module):
@@ -136,7 +138,14 @@ RANGE_TRIPS_BEFORE_PIN = 3
 
 def _range_only(w):
     """A guard word that says nothing but "a position was beyond the fast sin/cos range" (MNRF_GUARD_ENC_RANGE)."""
-    return bool(w & 4) and not (w & (1 | 2))
+    return bool(w & _lib.MNRF_GUARD_ENC_RANGE) and not (w & (_lib.MNRF_GUARD_SATURATED | _lib.MNRF_GUARD_WEIGHT))
+
+
+def _backward_saturation_only(w):
+    """A guard word that says nothing but "a scaled activation gradient of the training backward reached the f16 maximum".  (The
+    kernels set a MNRF_GUARD_IN_* bit only together with MNRF_GUARD_SATURATED.)"""
+    return bool((w & _lib.MNRF_GUARD_SATURATED) and (w & _lib.MNRF_GUARD_IN_BACKWARD)) and not (
+        w & (_lib.MNRF_GUARD_WEIGHT | _lib.MNRF_GUARD_ENC_RANGE | _lib.MNRF_GUARD_IN_FORWARD | _lib.MNRF_GUARD_IN_SECOND_ORDER))
 
 
 def release_transient(modules):
@@ -189,7 +198,7 @@ def _lower_gradient_scale(m, w):
     amplify gradients on their way down the trunk; the per-sample scale puts the largest seed at 2^6 and the planes hold up to
     2^12): lower that scale by 2^4 for this module instead of giving up the split arithmetic -- the loss-scaling move, downwards.
     Returns True when it did."""
-    if (w & 1) and (w & 256) and not (w & (2 | 4 | 128 | 512)):
+    if _backward_saturation_only(w):
         r = m.__dict__.get("_mnrf_seed_reduction", 0)
         if r + GRAD_SCALE_STEP <= GRAD_SCALE_MAX:
             import warnings
@@ -213,7 +222,7 @@ def guard_async_end(token, adapt=False):
     tripped = False
     for m, w, r0 in zip(modules, host.tolist(), issued_with):
         if w and precision_of(m) == "split":
-            if adapt and r0 is not None and m.__dict__.get("_mnrf_seed_reduction", 0) > r0 and (w & 256) and not (w & (2 | 4 | 128 | 512)):
+            if adapt and r0 is not None and m.__dict__.get("_mnrf_seed_reduction", 0) > r0 and _backward_saturation_only(w):
                 # the step behind this token was queued before the previous trip's adaptation took effect (flags are settled one
                 # step late): its backward overflowed at the OLD scale -- the update was vetoed on the device like the first one's,
                 # but it says nothing about the new scale.  Without this one overflow cost two adaptations.

@@ -221,7 +221,7 @@ def _place_mirror(r, rays_chunk, sel, plane, near, flag):
     nx, ny, nz = plane["normal"]
     u0, u1, w0, w1 = plane["rect"]
     _lib.check(_lib.lib().mnrf_place_mirror(
-        p(rays_chunk), N, 1 if plane["axis"] == "y" else 0, plane["position"], nx, ny, nz, u0, u1, w0, w1, float(near),
+        p(rays_chunk), N, _lib.MNRF_PLANE_Y if plane["axis"] == "y" else _lib.MNRF_PLANE_X, plane["position"], nx, ny, nz, u0, u1, w0, w1, float(near),
         p(depth), p(mask), p(normal), p(r[f"x_surface_{sel}"]), ctypes.c_void_p(merged.data_ptr()), p(flag), _lib.stream()),
         "mnrf_place_mirror")
     r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged

@@ -222,7 +222,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
             e0.record()
         rc = L.mnrf_field_composite_fused(p(folded_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], flags,
                                           None, p(opacity), p(rgb_map), p(depth), p(mask), p(sn), p(xs), _lib.stream())
-        if rc == -3:          # MNRF_ERR_UNSUPPORTED: the 48-samples-per-wave tuning is switched off
+        if rc == _lib.MNRF_ERR_UNSUPPORTED:          # the 48-samples-per-wave tuning is switched off
             return False
         _lib.check(rc, "mnrf_field_composite_fused")
         if _mn.LAUNCH_LOG is not None:

@@ -639,7 +639,7 @@ class GraphedTrainStep:
         waits only for replays more than `block_beyond` behind the one it is about to queue: with 1 it queues replay N+1 while
         replay N runs and never drains the device (a synchronize() on the previous replay at every call left a launch
         bubble per step)."""
-        from .mirror_nerf import GUARD, GUARD_NAMES, _lower_gradient_scale, pin_fp32
+        from .mirror_nerf import GUARD, GUARD_NAMES, _backward_saturation_only, _lower_gradient_scale, pin_fp32
         while self._pending:
             ev, host, issued_with = self._pending[0]
             if len(self._pending) > block_beyond:
@@ -652,7 +652,7 @@ class GraphedTrainStep:
             words = host.tolist()
             models = list(self.system.models.values())
             # (a backward overflow of a replay queued before an adaptation took effect says nothing about the new scale)
-            words = [0 if (w and (w & 256) and not (w & (2 | 4 | 128 | 512)) and m.__dict__.get("_mnrf_seed_reduction", 0) > r0) else w
+            words = [0 if (_backward_saturation_only(w) and m.__dict__.get("_mnrf_seed_reduction", 0) > r0) else w
                      for m, w, r0 in zip(models, words, issued_with)]
             if not any(words):
                 continue
