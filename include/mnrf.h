@@ -390,11 +390,28 @@ int mnrf_bench_gather(const void* table, int64_t table_bytes, int bytes_per_gath
  * Returns MNRF_ERR_UNSUPPORTED when the 48-samples-per-wave tuning is off (MNRF_SPLIT48=0). */
 #define MNRF_FUSED_WHITE_BACK 1u
 #define MNRF_FUSED_RGB_DEPTH 2u
+/* MNRF_FUSED_BLENDED_LEVEL: the caller will blend this level's colour with the thresholded mirror mask, m * reflected +
+ * (1 - m) * colour with m = 1 where the composited mirror value is not below 0.5 (batched_inference, every level that traces).
+ * The colour of such a ray cannot reach the frame, so the launch does not evaluate it: a workgroup is one ray, it runs the
+ * mirror head in front of the colour branch, forms the ray's mirror value with the operations of the compositing, and where
+ * that is not below 0.5 (a NaN included) it leaves out dir_encoding / view / rgb -- 76 of the 1112 tile pairs -- and writes 0
+ * to the ray's rgb_map row.  Every other map, and the rgb_map rows of the rays below 0.5, equal those of the launch without
+ * the flag bit for bit.  Needs mirror_mask; not together with MNRF_FUSED_RGB_DEPTH.  (Value 4 stays unused.)  The range guard
+ * does not see the colour-branch activations of a ray that is left out: nobody reads them.
+ * mnrf_field_composite_fused_pn is the same call with one more output, the per-sample predicted normals (n_rays, 192, 3), or
+ * null: with them and `weights` a level can take the ray-fused launch under the full result contract.  A non-null pred_normal
+ * or the flag selects the blended-level kernel (which then skips no ray unless the flag is set); pred_normal is refused
+ * together with MNRF_FUSED_RGB_DEPTH, whose launch forms no normal. */
+#define MNRF_FUSED_BLENDED_LEVEL 8u
 int mnrf_fused_samples_per_ray(void);
 int mnrf_field_composite_fused(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
                                const float* dir_emb, int64_t dir_stride, int flags,
                                float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
                                float* surf_normal, float* x_surface, void* stream);
+int mnrf_field_composite_fused_pn(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
+                                  const float* dir_emb, int64_t dir_stride, int flags,
+                                  float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
+                                  float* surf_normal, float* x_surface, float* pred_normal, void* stream);
 
 /* ---- training, round 3: operand planes (split arithmetic only) --------------------------------------------------------
  * The weight gradients dW = dY^T X contract over samples.  With MNRF_TRAIN_PLANES the training forward keeps the inputs X

@@ -4,7 +4,8 @@
 // maps bit for bit: the transmittance T_i = prod_{j<i} (1 - alpha_j + 1e-10) is an exclusive prefix product over the lanes
 // (Hillis-Steele over __shfl_up), carried across 64-sample blocks; 13 wave reductions at the end.
 // Included inside a namespace that provides wave_sum(float).  `Src`: has_noise/has_rgb/has_mirror/has_pn/has_gn,
-// z(s), sigma(s), noise(s), rgb(s,k), mirror(s), pn(s,k), gn(s,k) for sample s of this ray.
+// z(s), sigma(s), noise(s), rgb(s,k), mirror(s), pn(s,k), gn(s,k) for sample s of this ray; has_w / w(s): the weights themselves,
+// formed before by composite_mirror_value() from the same inputs (the scan is then not repeated).
 struct CompMaps {
     float* weights;      // this ray's row of the (n_rays, S) weights, or null
     float* opacity; float* rgb_map; float* depth; float* mirror_mask;
@@ -12,6 +13,56 @@ struct CompMaps {
     const float* rays;   // (n_rays, 8): x_surface = o + d * depth
     int white_back;
 };
+
+// One 64-sample block of the weights: alpha of sample s (rendering.py:182-192), the exclusive prefix product of the transmittance
+// over the lanes (195), carried across blocks in `carry`, w = alpha * T (197-199).  The ONE place where weights are formed: whoever
+// calls it with the same inputs gets the same bits.  `zv`: the sample's depth (0 outside the ray).
+template <class Src>
+__device__ __forceinline__ float composite_weight(const Src& src, int S, int s, bool in, int lane, float& carry, float& zv) {
+    float alpha = 0.f;
+    zv = 0.f;
+    if (in) {
+        zv = src.z(s);
+        const float delta = s + 1 < S ? src.z(s + 1) - zv : 1e10f;   // rendering.py:182-186
+        float sv = src.sigma(s);
+        if (src.has_noise()) sv = sv + src.noise(s);
+        alpha = 1.f - expf(-delta * fmaxf(sv, 0.f));                 // 190-192
+    }
+    const float t = in ? (1.f - alpha) + 1e-10f : 1.f;              // 195
+    float incl = t;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o);
+        if (lane >= o) incl *= up;
+    }
+    float excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = 1.f;
+    const float w = alpha * (carry * excl);                         // 197-199
+    carry = carry * __shfl(incl, 63);
+    return w;
+}
+
+// The composited mirror value of the ray alone, in every lane: the weights of composite_weight() and the mirror sum in the order
+// and with the reduction of composite_ray() below, so the value equals the mirror_mask that composite_ray() writes for the same
+// inputs bit for bit.  For a kernel that decides from it BEFORE the colours exist (the blended-level variant of the ray-fused
+// pass).  `w_keep` (or null): the weights are kept there for the composite_ray() that follows (Src::has_w / w).
+template <class Src>
+__device__ __forceinline__ float composite_mirror_value(const Src& src, int S, int lane, float* w_keep) {
+    float carry = 1.f;
+    float a_m = 0.f;
+#pragma unroll
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool in = s < S;
+        float zv;
+        const float w = composite_weight(src, S, s, in, lane, carry, zv);
+        if (in) {
+            if (w_keep) w_keep[s] = w;
+            a_m += w * src.mirror(s);
+        }
+    }
+    return wave_sum(a_m);
+}
 
 template <class Src>
 __device__ __forceinline__ void composite_ray(const Src& src, int S, int lane, long long ray, const CompMaps& A) {
@@ -21,25 +72,13 @@ __device__ __forceinline__ void composite_ray(const Src& src, int S, int lane, l
     for (int base = 0; base < S; base += 64) {
         const int s = base + lane;
         const bool in = s < S;
-        float alpha = 0.f, zv = 0.f;
-        if (in) {
-            zv = src.z(s);
-            const float delta = s + 1 < S ? src.z(s + 1) - zv : 1e10f;   // rendering.py:182-186
-            float sv = src.sigma(s);
-            if (src.has_noise()) sv = sv + src.noise(s);
-            alpha = 1.f - expf(-delta * fmaxf(sv, 0.f));                 // 190-192
+        float zv, w;
+        if (src.has_w()) {      // the weights were formed before, by composite_mirror_value()
+            zv = in ? src.z(s) : 0.f;
+            w = in ? src.w(s) : 0.f;
+        } else {
+            w = composite_weight(src, S, s, in, lane, carry, zv);
         }
-        const float t = in ? (1.f - alpha) + 1e-10f : 1.f;              // 195
-        float incl = t;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float up = __shfl_up(incl, o);
-            if (lane >= o) incl *= up;
-        }
-        float excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.f;
-        const float w = alpha * (carry * excl);                         // 197-199
-        carry = carry * __shfl(incl, 63);
         if (in) {
             if (A.weights) A.weights[s] = w;
             a_op += w;

@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off: every fused multiply-add below is an explicit fmaf().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "mnrf_layout.h"
@@ -220,29 +221,53 @@ extern "C" int mnrf_field_forward(float* packed, unsigned flags, int64_t B, cons
 // ---------------------------------------------------------------------- ray-fused fine pass (eval, maps only)
 extern "C" int mnrf_fused_samples_per_ray(void) { return split48_ray_samples(); }
 
+static int composite_fused(const char* who, float* packed, int64_t n_rays, const float* rays, const float* z_vals,
+                           const float* dir_emb, int64_t dir_stride, int flags,
+                           float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
+                           float* surf_normal, float* x_surface, float* pred_normal, void* stream) {
+    const auto fail = [&](int code, const char* what) {
+        static thread_local char msg[256];
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return mnrf_fail(code, msg);
+    };
+    if (!packed || !rays || !z_vals || !dir_emb) return fail(MNRF_ERR_ARG, "null pointer");
+    if (n_rays < 0) return fail(MNRF_ERR_ARG, "negative ray count");
+    if (flags & ~(int)(MNRF_FUSED_WHITE_BACK | MNRF_FUSED_RGB_DEPTH | MNRF_FUSED_BLENDED_LEVEL)) return fail(MNRF_ERR_ARG, "unknown flag bits");
+    const bool rgb_depth = flags & MNRF_FUSED_RGB_DEPTH;
+    const bool blended = flags & MNRF_FUSED_BLENDED_LEVEL;
+    if (rgb_depth && (mirror_mask || surf_normal || pred_normal))
+        return fail(MNRF_ERR_ARG, "MNRF_FUSED_RGB_DEPTH evaluates neither the mirror head nor the normal map");
+    if (blended && rgb_depth)
+        return fail(MNRF_ERR_ARG, "MNRF_FUSED_BLENDED_LEVEL decides from the mirror head, which MNRF_FUSED_RGB_DEPTH does not evaluate");
+    if (blended && !mirror_mask)
+        return fail(MNRF_ERR_ARG, "MNRF_FUSED_BLENDED_LEVEL needs the mirror_mask output: the caller blends with it");
+    if (n_rays == 0) return MNRF_OK;
+    if (!split48_enabled()) return fail(MNRF_ERR_UNSUPPORTED, "needs the 48-samples-per-wave tuning (MNRF_SPLIT48 != 0)");
+    const int spr = split48_ray_samples();
+    FieldArgs A{packed, MNRF_SPLIT_F16, (long long)n_rays * spr, nullptr, 3, rays, z_vals, spr, dir_emb, (long long)dir_stride,
+                nullptr, nullptr, pred_normal, nullptr, nullptr, nullptr};
+    A.fuse = rgb_depth ? 2 : blended ? 3 : pred_normal ? 4 : 1;      // (mnrf_field_split.inc: 3 / 4 = the blended-level kernel, 4 skips no ray)
+    A.white_back = (flags & MNRF_FUSED_WHITE_BACK) != 0;
+    A.f_weights = weights; A.f_opacity = opacity; A.f_rgb_map = rgb_map; A.f_depth = depth; A.f_mirror_mask = mirror_mask;
+    A.f_surf_normal = surf_normal; A.f_x_surface = x_surface;
+    if (launch_split48(A, false, (hipStream_t)stream) != 0) return fail(MNRF_ERR_ARG, "too many samples for one launch");
+    return mnrf_check_launch(who);
+}
+
 extern "C" int mnrf_field_composite_fused(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
                                           const float* dir_emb, int64_t dir_stride, int flags,
                                           float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
                                           float* surf_normal, float* x_surface, void* stream) {
-    if (!packed || !rays || !z_vals || !dir_emb) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: null pointer");
-    if (n_rays < 0) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: negative ray count");
-    if (flags & ~(int)(MNRF_FUSED_WHITE_BACK | MNRF_FUSED_RGB_DEPTH)) return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: unknown flag bits");
-    const bool rgb_depth = flags & MNRF_FUSED_RGB_DEPTH;
-    if (rgb_depth && (mirror_mask || surf_normal))
-        return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: MNRF_FUSED_RGB_DEPTH evaluates neither the mirror head nor the normal map");
-    if (n_rays == 0) return MNRF_OK;
-    if (!split48_enabled())
-        return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_composite_fused: needs the 48-samples-per-wave tuning (MNRF_SPLIT48 != 0)");
-    const int spr = split48_ray_samples();
-    FieldArgs A{packed, MNRF_SPLIT_F16, (long long)n_rays * spr, nullptr, 3, rays, z_vals, spr, dir_emb, (long long)dir_stride,
-                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    A.fuse = rgb_depth ? 2 : 1;
-    A.white_back = (flags & MNRF_FUSED_WHITE_BACK) != 0;
-    A.f_weights = weights; A.f_opacity = opacity; A.f_rgb_map = rgb_map; A.f_depth = depth; A.f_mirror_mask = mirror_mask;
-    A.f_surf_normal = surf_normal; A.f_x_surface = x_surface;
-    if (launch_split48(A, false, (hipStream_t)stream) != 0)
-        return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_composite_fused: too many samples for one launch");
-    return mnrf_check_launch("mnrf_field_composite_fused");
+    return composite_fused("mnrf_field_composite_fused", packed, n_rays, rays, z_vals, dir_emb, dir_stride, flags, weights, opacity,
+                           rgb_map, depth, mirror_mask, surf_normal, x_surface, nullptr, stream);
+}
+
+extern "C" int mnrf_field_composite_fused_pn(float* packed, int64_t n_rays, const float* rays, const float* z_vals,
+                                             const float* dir_emb, int64_t dir_stride, int flags,
+                                             float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
+                                             float* surf_normal, float* x_surface, float* pred_normal, void* stream) {
+    return composite_fused("mnrf_field_composite_fused_pn", packed, n_rays, rays, z_vals, dir_emb, dir_stride, flags, weights, opacity,
+                           rgb_map, depth, mirror_mask, surf_normal, x_surface, pred_normal, stream);
 }
 
 // ---------------------------------------------------------------------- training entry points

@@ -40,7 +40,9 @@ struct FieldArgs {
     // ray-fused fine pass (eval, maps only: round 3).  spr == 192 samples of ONE ray per workgroup of the 48-samples-per-wave
     // tuning: the four head outputs go to LDS instead of HBM and the workgroup composites its ray itself (mnrf_composite.inc,
     // the body of composite_kernel: identical maps); sigma / rgb / pred_normal / is_mirror above are then unused.
-    int fuse;                      // 1: fused compositing on
+    int fuse;                      // 1: fused compositing on; 2: its rgb / depth variant; 3: its blended-level variant (rays whose
+                                   // composited mirror value is not below 0.5 get no colour branch and an rgb_map row of 0; also
+                                   // writes `pred_normal` per sample when that is set); 4: the kernel of 3, no ray skipped
     // dynamic tile queue (48-samples-per-wave kernels, round 3): one resident workgroup per CU takes 192-sample tiles from a
     // global counter instead of one workgroup per tile -- the hardware deals workgroup ids to the 8 XCDs round robin, so a
     // static grid ends when the SLOWEST XCD has worked off its eighth (the XCDs of one package run up to 9 % apart under

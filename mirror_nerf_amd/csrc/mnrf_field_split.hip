@@ -147,7 +147,24 @@ __global__ void split_fold_kernel(FoldImages I) {
     float* packed = I.packed[blockIdx.y];
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     constexpr long long FOLD_LANES = (long long)SPLIT_FOLD_PAIRS * 64;
-    if (q >= FOLD_LANES + BIAS_FLOATS) return;
+    if (q >= FOLD_LANES + BIAS_FLOATS + (long long)FOLD_MIRB_PAIRS * 64) return;
+    if (q >= FOLD_LANES + BIAS_FLOATS) {
+        // ---- the mirror head once more, chunk-aligned behind the bias block, for the blended-level variant of the ray-fused kernel
+        //      (mnrf_layout.h FOLD_POS_MIRB): is_mirror_net.0 and .2 from the split stream (1036 ..), then four pairs of zeros
+        const int j = (int)((q - FOLD_LANES - BIAS_FLOATS) >> 6), l = (int)(q & 63);
+        typedef _Float16 h8c __attribute__((ext_vector_type(8)));
+        h8c hi, lo;
+        for (int e = 0; e < 8; ++e) hi[e] = lo[e] = (_Float16)0.f;
+        if (j < 64 + 4) {
+            const char* src = (const char*)(packed + OFF_SPLIT_FWD) + (long long)(1036 + j) * PAIR_BYTES + l * 16;
+            hi = *(const h8c*)src;
+            lo = *(const h8c*)(src + PAIR_BYTES / 2);
+        }
+        char* dst = (char*)(packed + OFF_FOLD_FWD) + (long long)(FOLD_POS_MIRB + j) * PAIR_BYTES + l * 16;
+        *(h8c*)dst = hi;
+        *(h8c*)(dst + PAIR_BYTES / 2) = lo;
+        return;
+    }
     const float* bias = packed + OFF_BIAS;
     if (q >= FOLD_LANES) {
         // ---- bias block: a copy, the folded biases in place (fp64 dot product, then the second bias, then one rounding)
@@ -228,7 +245,7 @@ void launch_split_fold(const float* const* params, float* const* packed, int n_i
         I.wn1[m] = p[24];
         I.wn2[m] = p[26];
     }
-    const long long n = (long long)SPLIT_FOLD_PAIRS * 64 + BIAS_FLOATS;
+    const long long n = (long long)SPLIT_FOLD_PAIRS * 64 + BIAS_FLOATS + (long long)FOLD_MIRB_PAIRS * 64;
     hipLaunchKernelGGL(split_fold_kernel, dim3((unsigned)((n + 255) / 256), n_images), dim3(256), 0, s, I);
 }
 

@@ -62,7 +62,8 @@ constexpr int LDS_BYTES_GRAD = LDS_MASK + 8 * S * WG_THREADS * 8;
 static_assert(LDS_BYTES_GRAD <= 160 * 1024, "LDS budget");
 // ray-fused fine pass (S = 3): the head outputs of the workgroup's 192 samples and their depths, [sigma | r | g | b | pn x 3 | mirror | z][sample]
 constexpr int LDS_FUSE = LDS_BYTES;
-constexpr int LDS_BYTES_FUSE = LDS_BYTES + 9 * WG_SAMPLES * 4;
+// (+ a tenth row, the ray's compositing weights, in the blended-level variant)
+constexpr int LDS_BYTES_FUSE = LDS_BYTES + 10 * WG_SAMPLES * 4;
 static_assert(LDS_BYTES_FUSE <= 160 * 1024, "LDS budget");
 
 #include "mnrf_field_split_common.inc"
@@ -77,6 +78,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 struct CompLdsSrc {
     const float* f;      // LDS: [9][WG_SAMPLES]: sigma | r g b | predicted normal x 3 | mirror | depth
     bool pn_on, mir_on;
+    __device__ __forceinline__ bool has_w() const { return false; }
+    __device__ __forceinline__ float w(int) const { return 0.f; }
     __device__ __forceinline__ bool has_noise() const { return false; }
     __device__ __forceinline__ bool has_rgb() const { return true; }
     __device__ __forceinline__ bool has_mirror() const { return mir_on; }
@@ -92,6 +95,14 @@ struct CompLdsSrc {
 };
 // ... of the rgb / depth variant (RGB_DEPTH): no mirror head, no normal map -- known at compile time, so the compositing forms
 // the colour, depth and opacity sums alone
+// ... of the blended-level variant (BLENDED): the colour rows exist only for a ray whose colour branch ran, and the weights were
+// formed (and parked in a tenth row) when the ray's mirror value was
+struct CompLdsSrcBlended : CompLdsSrc {
+    bool colour;
+    __device__ __forceinline__ bool has_rgb() const { return colour; }
+    __device__ __forceinline__ bool has_w() const { return true; }
+    __device__ __forceinline__ float w(int s) const { return f[9 * WG_SAMPLES + s]; }
+};
 struct CompLdsSrcRgbDepth : CompLdsSrc {
     __device__ __forceinline__ bool has_mirror() const { return false; }
     __device__ __forceinline__ bool has_pn() const { return false; }
@@ -171,12 +182,18 @@ __device__ __forceinline__ void conv_task(int q, const f32x4 (&pacc)[S][8], u32x
 // MFMAs of each of its first 32 units: the 64 stores per 256-wide section used to go out in one burst between two GEMMs
 // while all four matrix pipes waited for HBM (0.65 of the 1.9 ms of the training forward per step).  `sp`: this lane's corner
 // of tile 0 of the section.
+// JUMP != 0 (blended-level variant of the ray-fused kernel): behind the piece that unit JUMP_T / U issues -- the last piece of
+// its chunk -- the FILL pointer moves by JUMP bytes (if `jump_on`, wave-uniform), so that the chunks filled from there on come
+// from another place of the image (mnrf_layout.h FOLD_POS_MIRB).  Everything else of the schedule counts chunks, not addresses.
+// SKIP: the part's pairs are stepped over -- reads, pieces and seams as ever, no MFMA (padding pairs of that variant's stream).
 template <int NT, int NB, int NACC, int NTA, int JOB, bool WANT_MASK, int USTART, int TPU, int POS, int NPARK = 0, int STB = -1,
-          int STN = 4, bool SSCALE = false>
+          int STN = 4, bool SSCALE = false, int JUMP_T = -1, long long JUMP = 0, bool SKIP = false>
 __device__ __forceinline__ void gemm_part_impl(f32x4 (&acc)[S][NACC], const u32x4 (&bh)[S][NTA], const u32x4 (&bl)[S][NTA],
                                                Stream& st, int wave, int lane16, const f32x4 (&pacc)[S][8],
                                                u32x4 (&oh)[S][8], u32x4 (&ol)[S][8], int t0, int half, uint64_t (&mk)[S],
-                                               const StoreCtx& sc = StoreCtx{}) {
+                                               const StoreCtx& sc = StoreCtx{}, bool jump_on = true) {
+    static_assert(JUMP == 0 || (JUMP_T >= 0 && JUMP_T % U == 0 && JUMP_T < NT * NB && ((POS + JUMP_T) / U) % PIECES == PIECES - 1 && JUMP % CHUNK_BYTES == 0),
+                  "the fill pointer jumps between two chunks");
     static_assert(STB < 0 || (S == 2 && NT * NB / U >= 8 * STN && STB + STN <= NTA), "8 store tasks per operand ride on the part's first units");
     static_assert(NT <= NTA, "B operand count");
     static_assert(JOB < 0 || NTASKS % TPU == 0, "tasks per unit");
@@ -247,7 +264,7 @@ __device__ __forceinline__ void gemm_part_impl(f32x4 (&acc)[S][NACC], const u32x
             for (int s = 0; s < S; ++s) {
                 const u32x4& a = ph == 1 ? al[(t + u) % NBUF] : ah[(t + u) % NBUF];
                 const u32x4& b = ph == 2 ? (T < NPARK ? pk[T % NSLOT][s] : bl[s][T]) : bh[s][T];
-                acc[s][nb] = mfma_f16(a, b, acc[s][nb]);
+                if (!SKIP) acc[s][nb] = mfma_f16(a, b, acc[s][nb]);
             }
             if (JOB >= 0 && (sg == 0 || sg == 2) && TPU == 2) {
                 const int unit = t / U - USTART;
@@ -320,6 +337,7 @@ __device__ __forceinline__ void gemm_part_impl(f32x4 (&acc)[S][NACC], const u32x
                     else if (piece == 5) issue_piece<(PIECES == 8 ? 5 : 0)>(st);
                     else if (piece == 6) issue_piece<(PIECES == 8 ? 6 : 0)>(st);
                     else issue_piece<(PIECES == 8 ? 7 : 0)>(st);
+                    if (JUMP != 0 && t == JUMP_T) st.fill_src += jump_on ? (unsigned long long)JUMP : 0ull;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -333,25 +351,36 @@ __device__ __forceinline__ void gemm_part_impl(f32x4 (&acc)[S][NACC], const u32x
 }
 
 // POS: position of the part in its stream, in pairs (mnrf_layout.h)
-template <int NT, int NB, int POS, int NPARK = 0, int STB = -1, int STN = 4, bool SSCALE = false, int NACC, int NTA>
+template <int NT, int NB, int POS, int NPARK = 0, int STB = -1, int STN = 4, bool SSCALE = false, int JUMP_T = -1, long long JUMP = 0,
+          int NACC, int NTA>
 __device__ __forceinline__ void gemm_part(f32x4 (&acc)[S][NACC], const u32x4 (&bh)[S][NTA], const u32x4 (&bl)[S][NTA],
                                           Stream& st, int wave, int lane16, const StoreCtx& sc = StoreCtx{}) {
     f32x4 pacc[S][8];
     u32x4 oh[S][8], ol[S][8];
     uint64_t mk[S];
-    gemm_part_impl<NT, NB, NACC, NTA, -1, false, 0, S, POS, NPARK, STB, STN, SSCALE>(acc, bh, bl, st, wave, lane16, pacc, oh, ol, 0, 0,
-                                                                                      mk, sc);
+    gemm_part_impl<NT, NB, NACC, NTA, -1, false, 0, S, POS, NPARK, STB, STN, SSCALE, JUMP_T, JUMP>(acc, bh, bl, st, wave, lane16, pacc,
+                                                                                                  oh, ol, 0, 0, mk, sc);
+}
+
+// four pairs at POS stepped over (gemm_part_impl SKIP)
+template <int POS>
+__device__ __forceinline__ void skip_pairs4(Stream& st, int wave, int lane16) {
+    f32x4 acc[S][1], pacc[S][8];
+    u32x4 b[S][4], oh[S][8], ol[S][8];
+    uint64_t mk[S];
+    gemm_part_impl<4, 1, 1, 4, -1, false, 0, S, POS, 0, -1, 4, false, -1, 0, true>(acc, b, b, st, wave, lane16, pacc, oh, ol, 0, 0, mk);
 }
 
 // One half (8 row blocks) of a 256-wide trunk layer from NT k-steps of `bh/bl`, while converting the finished half
 // `pacc` (relu) into hh/hl[t0 .. t0+3].
 // STB: see gemm_part_impl -- the half that converts INTO operands 4..7 (t0 = 4) may store operands 0..3 of its input, the
 // half that converts into 0..3 (t0 = 0, from unit 4 T' + 4 on) operands 4..7
-template <int NT, int NTA, bool WANT_MASK, int USTART, int TPU, int POS, int STB = -1>
+template <int NT, int NTA, bool WANT_MASK, int USTART, int TPU, int POS, int STB = -1, int JUMP_T = -1, long long JUMP = 0>
 __device__ __forceinline__ void gemm_half(f32x4 (&acc)[S][8], const u32x4 (&bh)[S][NTA], const u32x4 (&bl)[S][NTA], Stream& st,
                                           int wave, int lane16, const f32x4 (&pacc)[S][8], u32x4 (&hh)[S][8], u32x4 (&hl)[S][8],
-                                          int t0, int half, uint64_t (&mk)[S], const StoreCtx& sc = StoreCtx{}) {
-    gemm_part_impl<NT, 8, 8, NTA, 1, WANT_MASK, USTART, TPU, POS, 0, STB>(acc, bh, bl, st, wave, lane16, pacc, hh, hl, t0, half, mk, sc);
+                                          int t0, int half, uint64_t (&mk)[S], const StoreCtx& sc = StoreCtx{}, bool jump_on = true) {
+    gemm_part_impl<NT, 8, 8, NTA, 1, WANT_MASK, USTART, TPU, POS, 0, STB, 4, false, JUMP_T, JUMP>(acc, bh, bl, st, wave, lane16, pacc, hh,
+                                                                                                 hl, t0, half, mk, sc, jump_on);
 }
 
 // all tasks of a half layer at once (the last half of the trunk has no MFMA stream behind it to hide in)
@@ -536,11 +565,26 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // RGB_DEPTH (FUSE only): the caller reads colour and depth alone (the last reflection level of a frame): the stream stops in front
 // of the mirror head, which the folded order puts last (mnrf_layout.h FOLD_POS_MIR1), and the compositing wave forms only the
 // rgb / depth / opacity sums.
-template <bool SIGMA_ONLY, bool GRAD, bool PLANES, bool FUSE, bool RGB_DEPTH>
+// BLENDED (FUSE only; FieldArgs::fuse 3 / 4): the pass of a level whose colour the caller will blend with the thresholded mirror
+// mask, m * reflected + (1 - m) * colour (recursion.stage_b).  A workgroup is one ray, so whether the ray's colour can reach the
+// frame is uniform over it: the mirror head runs BEFORE the colour branch, every wave forms the ray's composited mirror value
+// from the sigma and mirror rows in LDS (composite_mirror_value: the operations of composite_ray, so the value is the one the
+// mirror map gets), and if it is not below 0.5 (m = 1; a NaN too) the workgroup leaves out dir_encoding / view / rgb -- 76 of the
+// 1112 pairs -- and writes 0 to the ray's rgb_map row.  The stream is the folded one up to the sigma | normal block; there the
+// fill pointer jumps to a chunk-aligned copy of the mirror head behind the bias block (mnrf_layout.h FOLD_POS_MIRB: 68 pairs and 4
+// of padding, which are stepped over) and from its end back to dir_encoding, so the other kernels keep their stream as it is.
+// Logical positions: is_mirror_net.0 968, is_mirror_net.2 1032, padding 1036, dir_encoding 1040, view 1104, rgb 1112, end 1116.
+// The variant also writes the per-sample predicted normals (FieldArgs::pred_normal) when asked: with them and the weights a
+// level can take the fused launch under the full result contract.  fuse == 4: the same kernel, no ray skipped.
+template <bool SIGMA_ONLY, bool GRAD, bool PLANES, bool FUSE, bool RGB_DEPTH, bool BLENDED = false>
 __device__ __forceinline__ void field_split_body(FieldArgs A) {
     static_assert(!PLANES || (GRAD && !SIGMA_ONLY && S == 2), "operand planes: the training forward (32 samples per wave)");
     static_assert(!FUSE || (S == 3 && !SIGMA_ONLY && !GRAD), "ray-fused compositing: the 192-sample fine pass");
     static_assert(!RGB_DEPTH || FUSE, "rgb / depth only: a variant of the ray-fused pass");
+    static_assert(!BLENDED || (FUSE && !RGB_DEPTH && CHUNK_PAIRS == 8), "blended level: a variant of the ray-fused pass; its jumps are whole 8-pair chunks");
+    constexpr long long JUMP_TO_MIRB = BLENDED ? (long long)(FOLD_POS_MIRB - FOLD_POS_DIR) * PAIR_BYTES : 0;
+    constexpr long long JUMP_FROM_MIRB = BLENDED ? (long long)(FOLD_POS_DIR - (FOLD_POS_MIRB + FOLD_MIRB_PAIRS)) * PAIR_BYTES : 0;
+    constexpr int JT = BLENDED ? 54 : -1;      // the unit of a 64-pair part that issues the last piece of the first chunk BEHIND the part
     constexpr bool FOLD = !SIGMA_ONLY && !GRAD;
     float* const fz = (float*)(smem + LDS_FUSE);      // FUSE: [9][WG_SAMPLES]
     // Dynamic tile queue (S = 3, FieldArgs::tile_queue): the launch has one workgroup per CU; the first tile is the workgroup's
@@ -809,7 +853,8 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             if (keep) save_acc<8, 1>(A.save_x + (long long)(SEC_H + 256 * (5 + l)) * A.B, 256, 0, accA, idx, valid, g, unused_bits);
             if constexpr (S == 2 && !WEAVE) { if (pl) store_planes<8, 8>(sc, SEC_H / 16 + 16 * (4 + l), hh, hl); }      // h5..h7
             init_bias_half(accB, BIAS_L + 256 * (5 + l), 1, gq());
-            gemm_half<8, 8, GRAD, 4, S, 640, ST4>(accB, hh, hl, st, wave, lane16, accA, hh, hl, 0, 0, mk, at_h(4 + l, 4));
+            // (BLENDED: the chunk behind L8 -- sigma | normal -- is the last one of the common stream)
+            gemm_half<8, 8, GRAD, 4, S, 640, ST4, JT, JUMP_TO_MIRB>(accB, hh, hl, st, wave, lane16, accA, hh, hl, 0, 0, mk, at_h(4 + l, 4), l == 2);
             if (keep) save_acc<8, 1>(A.save_x + (long long)(SEC_H + 256 * (5 + l)) * A.B, 256, 8, accB, idx, valid, g, unused_bits);
         }
         // half 2 of L8 has nothing to hide behind
@@ -849,6 +894,12 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
                     const float inv = 1.f / sqrtf(fmaxf(a0 * a0 + a1 * a1 + a2 * a2, 1.1920928955078125e-07f));
                     const int q = wave * (S * 16) + s * 16 + (int)m15();
                     fz[4 * WG_SAMPLES + q] = a0 * inv; fz[5 * WG_SAMPLES + q] = a1 * inv; fz[6 * WG_SAMPLES + q] = a2 * inv;
+                    if constexpr (BLENDED) {
+                        if (A.pred_normal && sval(s)) {
+                            float* o = A.pred_normal + (long long)sidx(s) * 3;
+                            out_store(o, a0 * inv); out_store(o + 1, a1 * inv); out_store(o + 2, a2 * inv);
+                        }
+                    }
                 }
             }
         } else if (A.pred_normal && g == 0) {
@@ -883,6 +934,7 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
         if constexpr (FOLD && !RGB_DEPTH) put_normal(acc, std::integral_constant<int, 1>{});
     }
 
+    bool colour = true;      // BLENDED: false for a ray whose colour the caller's blend multiplies by zero
     if (!SIGMA_ONLY) {
         // ---- predicted normal: 256 -> 128 -> 3, no activation in between (mirror_nerf.py:85-88); FOLD: done above
         if constexpr (!FOLD) {
@@ -907,7 +959,8 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             {
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_MIR1, gq());
-                gemm_part<8, 8, FOLD ? FOLD_POS_MIR1 : 1036, HP, ST4>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
+                // (BLENDED: the chunk behind this part is the last one of the mirror head's copy; dir_encoding follows)
+                gemm_part<8, 8, BLENDED ? 968 : FOLD ? FOLD_POS_MIR1 : 1036, HP, ST4, 4, false, JT, JUMP_FROM_MIRB>(acc, hh, hl, st, wave, lane16, at_h(7, 4));
                 if (keep) {
                     uint64_t bits[S];
                     save_acc<8, 2>(A.save_x + (long long)SEC_HM * A.B, 128, 0, acc, idx, valid, g, bits);
@@ -921,7 +974,7 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_MIR2, gq());
-            gemm_part<4, 1, FOLD ? FOLD_POS_MIR2 : 1100>(acc, mh, ml, st, wave, lane16);
+            gemm_part<4, 1, BLENDED ? 1032 : FOLD ? FOLD_POS_MIR2 : 1100>(acc, mh, ml, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll
@@ -934,6 +987,19 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             }
         };
         if constexpr (!FOLD) mirror_head();
+        if constexpr (BLENDED) {
+            mirror_head();
+            skip_pairs4<1036>(st, wave, lane16);
+            // sigma, mirror and depth rows of all four waves (raw barrier: the LDS-DMA pieces on their way stay on their way)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            int dl;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(dl));
+            // (wave 0, which composites the ray at the end, keeps the weights it forms here)
+            const float mv = composite_mirror_value(CompLdsSrc{fz, false, true}, WG_SAMPLES, dl, wave == 0 ? fz + 9 * WG_SAMPLES : nullptr);
+            colour = __builtin_amdgcn_readfirstlane((int)(mv < 0.5f)) != 0 || A.fuse == 4;
+        }
         // ---- colour: final(256->256, no act) ; cat[final, dir] -> 128 relu ; 128 -> 3 sigmoid.  FOLD: dir_encoding reads h8
         //      through the folded map (final's 256 outputs are never formed)
         // view-encoding B operands (32 padded columns: one k-step)
@@ -954,15 +1020,15 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             split_b<8>(de, vh, vl, st.sat);
             if constexpr (S == 2) { if (pl) store_planes<1, 1>(sc, SEC_DIRE / 16, vh, vl); }
         };
-        {
+        if (colour) {
             u32x4 dh[S][4], dl[S][4];
             if constexpr (FOLD) {
                 u32x4 vh[S][1], vl[S][1];
                 view_operands(vh, vl);
                 f32x4 acc[S][8];
                 init_bias<8>(acc, BIAS_DIR, gq());
-                gemm_part<8, 8, FOLD_POS_DIR, HP>(acc, hh, hl, st, wave, lane16);
-                gemm_part<1, 8, FOLD_POS_VIEW>(acc, vh, vl, st, wave, lane16);
+                gemm_part<8, 8, BLENDED ? 1040 : FOLD_POS_DIR, HP>(acc, hh, hl, st, wave, lane16);
+                gemm_part<1, 8, BLENDED ? 1104 : FOLD_POS_VIEW>(acc, vh, vl, st, wave, lane16);
                 acc_to_b<8, 1, false>(dh, dl, acc, 0, tid, st.sat);
             } else {
                 u32x4 fh[S][8], fl[S][8];
@@ -993,7 +1059,7 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
             }
             f32x4 acc[S][1];
             init_bias<1>(acc, BIAS_RGB, gq());
-            gemm_part<4, 1, FOLD ? FOLD_POS_RGB : 1304>(acc, dh, dl, st, wave, lane16);
+            gemm_part<4, 1, BLENDED ? 1112 : FOLD ? FOLD_POS_RGB : 1304>(acc, dh, dl, st, wave, lane16);
             if (FUSE) {
                 if (gq() == 0) {
 #pragma unroll
@@ -1015,7 +1081,7 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
                     }
             }
         }
-        if constexpr (FOLD && !RGB_DEPTH) mirror_head();
+        if constexpr (FOLD && !RGB_DEPTH && !BLENDED) mirror_head();
     }
 
     if (GRAD) {
@@ -1129,6 +1195,14 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
                 const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, A.f_rgb_map, A.f_depth, nullptr,
                                    nullptr, nullptr, nullptr, A.f_x_surface, A.rays, A.white_back};
                 composite_ray(CompLdsSrcRgbDepth{fz, false, false}, WG_SAMPLES, cl, ray, out);
+            } else if constexpr (BLENDED) {
+                // (`colour` is what every wave decided above from the same rows: a row is 0 exactly where the mirror map written
+                // here is not below 0.5)
+                const CompLdsSrcBlended src{{fz, A.f_surf_normal != nullptr, A.f_mirror_mask != nullptr}, colour};
+                const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, colour ? A.f_rgb_map : nullptr, A.f_depth,
+                                   A.f_mirror_mask, A.f_surf_normal, nullptr, nullptr, A.f_x_surface, A.rays, A.white_back};
+                composite_ray(src, WG_SAMPLES, cl, ray, out);
+                if (!colour && A.f_rgb_map && cl < 3) A.f_rgb_map[ray * 3 + cl] = 0.f;
             } else {
                 const CompLdsSrc src{fz, A.f_surf_normal != nullptr, A.f_mirror_mask != nullptr};
                 const CompMaps out{A.f_weights ? A.f_weights + ray * WG_SAMPLES : nullptr, A.f_opacity, A.f_rgb_map, A.f_depth, A.f_mirror_mask,
@@ -1167,6 +1241,12 @@ __global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_ke
     field_split_body<false, false, false, ON, ON>(A);
 }
 
+// the blended-level variant of the ray-fused pass (field_split_body BLENDED)
+template <bool ON = true>
+__global__ __launch_bounds__(WG_THREADS, MIN_WAVES_PER_SIMD) void field_split_kernel_blended(FieldArgs A) {
+    field_split_body<false, false, false, ON, false, ON>(A);
+}
+
 // (a template only so that the discarded branch below never instantiates the ray-fused kernels in the S = 2 tunings)
 template <bool UNUSED = false>
 inline int launch(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s) {
@@ -1181,6 +1261,8 @@ inline int launch(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s)
     if (sigma_only && !grad) hipLaunchKernelGGL((field_split_kernel<true, false>), grid, block, LDS_BYTES, s, A);
     else if (!sigma_only && !grad && S == 3 && A.fuse == 2) {
         if constexpr (S == 3) hipLaunchKernelGGL((field_split_kernel_rgb_depth<>), grid, block, LDS_BYTES_FUSE, s, A);
+    } else if (!sigma_only && !grad && S == 3 && A.fuse >= 3) {
+        if constexpr (S == 3) hipLaunchKernelGGL((field_split_kernel_blended<>), grid, block, LDS_BYTES_FUSE, s, A);
     } else if (!sigma_only && !grad && S == 3 && A.fuse)
         hipLaunchKernelGGL((field_split_kernel<false, false, false, S == 3>), grid, block, LDS_BYTES_FUSE, s, A);
     else if (!sigma_only && !grad) hipLaunchKernelGGL((field_split_kernel<false, false>), grid, block, LDS_BYTES, s, A);

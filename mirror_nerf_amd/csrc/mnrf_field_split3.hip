@@ -78,6 +78,7 @@ int launch_split48(const FieldArgs& A0, bool sigma_only, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)h3::field_split_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    h3::LDS_BYTES_FUSE);
         (void)hipFuncSetAttribute((const void*)h3::field_split_kernel_rgb_depth<>, hipFuncAttributeMaxDynamicSharedMemorySize, h3::LDS_BYTES_FUSE);
+        (void)hipFuncSetAttribute((const void*)h3::field_split_kernel_blended<>, hipFuncAttributeMaxDynamicSharedMemorySize, h3::LDS_BYTES_FUSE);
         return true;
     }();
     (void)once;

@@ -152,6 +152,18 @@ static_assert(SPLIT_FOLD_USED == 960 + 8 + 64 + 4 + 64 + 8 + 4, "the folded stre
 constexpr int64_t OFF_FOLD_FWD = OFF_SPLIT_HBWD + (int64_t)SPLIT_HBWD_PAIRS * (PAIR_BYTES / 4);
 constexpr int64_t OFF_FOLD_BIAS = OFF_FOLD_FWD + (int64_t)SPLIT_FOLD_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
 constexpr int64_t PACKED_FLOATS = OFF_FOLD_FWD + (int64_t)FOLD_REGION_PAIRS * (PAIR_BYTES / 4) + SPLIT_TAIL_FLOATS;
+//      Behind that bias block, at pair FOLD_POS_MIRB of the region, lies a COPY of the mirror head for the blended-level variant of
+//      the ray-fused kernel (mnrf_field_split.inc BLENDED), which needs the mirror value of a ray BEFORE the colour branch:
+//      is_mirror_net.0 (64 pairs), is_mirror_net.2 (4 pairs) and 4 pairs of zeros, so that the copy begins and ends on a boundary
+//      of that kernel's 8-pair chunks.  The variant reads the stream above up to the sigma | normal block, moves its fill pointer
+//      to the copy, and from the copy's end back to dir_encoding (968); the pairs it consumes are, in its own count:
+//      is_mirror_net.0 968, is_mirror_net.2 1032, padding 1036, dir_encoding 1040, view 1104, rgb 1112, end 1116.  Every other
+//      kernel reads the stream above as it is: no part of it moved, and the image keeps its size.
+constexpr int FOLD_MIRB_PAIRS = 64 + 4 + 4;                                                          // 72
+constexpr int FOLD_POS_MIRB = 1160;
+static_assert(FOLD_POS_MIRB % 8 == 0 && FOLD_MIRB_PAIRS % 8 == 0 && FOLD_POS_DIR % 8 == 0, "the copy is whole chunks of the 48-sample tuning");
+static_assert(OFF_FOLD_FWD + (int64_t)FOLD_POS_MIRB * (PAIR_BYTES / 4) >= OFF_FOLD_BIAS + BIAS_FLOATS, "the copy lies behind the folded bias block");
+static_assert(FOLD_POS_MIRB + FOLD_MIRB_PAIRS <= FOLD_REGION_PAIRS, "the copy fits the reserved region");
 // The last words of the image (inside the tail pad, whose contents no kernel consumes) are CALLER-OWNED device state of the
 // launches that use this image: [PACKED_FLOATS - 1] the range-guard word (mnrf.h), before it TQ_PAIRS {next, done} counter
 // pairs of the dynamic tile queue (mnrf_field_split3.hip).  mnrf_pack_weights zeroes all of them.

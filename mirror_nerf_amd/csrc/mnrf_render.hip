@@ -115,6 +115,8 @@ struct CompArgs {
 struct CompGlobalSrc {
     const CompArgs& A;
     long long ray;
+    __device__ __forceinline__ bool has_w() const { return false; }
+    __device__ __forceinline__ float w(int) const { return 0.f; }
     __device__ __forceinline__ bool has_noise() const { return A.noise != nullptr; }
     __device__ __forceinline__ bool has_rgb() const { return A.rgb != nullptr; }
     __device__ __forceinline__ bool has_mirror() const { return A.is_mirror != nullptr; }

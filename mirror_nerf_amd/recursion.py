@@ -21,6 +21,7 @@ through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 import ctypes
 import os
 from collections import defaultdict
+import weakref
 from types import SimpleNamespace
 
 import torch
@@ -32,6 +33,11 @@ from .dnerf import render_rays_dnerf
 from .rendering import render_rays
 
 RAY_FORWARD_OFFSET = 0.1   # train.py:232, eval.py:529 (absolute near of a reflected ray)
+# Share of rays above the mirror threshold from which the blended-level launch is the faster route for a chunk of a level that
+# traces (batched_inference stage_a): measured, profiles/blended_level_ab.txt section 4 -- 13.60 ms without and 12.55 ms with
+# every ray a mirror, against 13.21 ms for the field launch and the compositing launch it replaces
+BLENDED_BREAK_EVEN = 0.37
+_MIRROR_FRACTION = weakref.WeakKeyDictionary()      # model of the selected pass -> {recursion level: share last counted}
 JITTER_RAYS = 262144       # rays per batched group of jittered reflections (roughness, eval.py:622-674)
 
 # app_place_new_mirror presets (eval.py:369-433), restated as data: the first entry whose key is a substring of args.root_dir
@@ -684,7 +690,10 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     everything on the device; "maps": return only the per-ray maps -- rgb, depth, opacity, mirror mask, normals,
     x_surface, ~100 B/ray instead of ~3 KB/ray of per-sample tensors nobody downstream of eval.py:743-894 reads -- on
     the CPU), batch_jitter (roughness: render the trace_ray_times jittered reflections of a level in groups through one
-    recursion call each instead of one by one; default on unless draws are injected),
+    recursion call each instead of one by one; default on unless draws are injected), blended_level (default "auto": a chunk
+    of a level that traces renders its fine pass with the blended-level launch, which leaves out the colour of mirror rays,
+    when the chunk last counted at that level held enough of them for it to pay -- same result either way; True / False force
+    the choice, see stage_a),
     _normal_noise (iterator of pre-drawn (n,3) standard-normal tensors, for tests).
 
     Applications (the reference's flags, unchanged): args.app_place_new_mirror with args.plane_pos / args.root_dir (the
@@ -748,6 +757,10 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     one_field = getattr(args, "only_one_field", False)
     fine_epoch = getattr(args, "only_one_field_fine_epoch", 2)
     sel = "fine" if (N_importance > 0 and not one_field) else "coarse"
+    blend_mode = kwargs.get("blended_level", "auto")      # True / False / "auto": see stage_a
+    if blend_mode not in (True, False, "auto"):
+        raise ValueError(f"blended_level must be True, False or 'auto', not {blend_mode!r}")
+    mirror_fraction = _MIRROR_FRACTION.setdefault(models.get(sel, models["coarse"]), {})      # level -> share of mirror rays in the chunk last counted
 
     def draw(n, dev):
         if noise_iter is not None:
@@ -762,12 +775,33 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
         # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
         rgb_depth = 1 <= level == args.max_recursive_level and not rough
+        # A level that traces has its colour replaced by m * reflected + (1 - m) * colour in stage_b, m = 1 wherever the
+        # composited mirror value is not below 0.5 (the threshold, then `!= 0`): the colour of such a ray reaches nothing --
+        # no other key of the result carries it -- so the final pass may leave it out and write 0 (render_rays
+        # `_blended_level`, mnrf_field_composite_fused MNRF_FUSED_BLENDED_LEVEL; 0 * colour and 0 * 0 are the same +0).  A chunk
+        # whose "any mirror" flag comes back false is returned unblended -- and then holds no ray above the threshold, so no
+        # row of it was left out.  Not with roughness jitters, a placed mirror, reflection substitution or placed objects:
+        # those read or edit more of the level than the blend does.  (render_rays falls back to the launches of before when
+        # the pass is not one the fused kernel covers: fp32 arithmetic, another sample count, density-gradient normals.)
+        # Both routes give the same result, so the choice is one of speed alone, and it is made PER CHUNK from evidence: a chunk
+        # with no ray above the threshold is about 3 % slower through the ray-fused form than through the two-kernel path, one
+        # with every ray above it 5 % faster, and the two meet at BLENDED_BREAK_EVEN.  The evidence is the share of rays above
+        # the threshold in the chunk of this level whose count was last known (neighbouring chunks of a frame, and the same
+        # chunks of the frame before, see much the same scene); it is kept per model across calls (_MIRROR_FRACTION).  Without
+        # evidence -- the first chunk ever rendered with a model -- the launches of before are used, so a scene with few mirror
+        # pixels never takes the slower route for more than the chunks it takes to notice a change.
+        # `blended_level=True` / `False` forces the choice (tests, measurements).
+        can_blend = bool(level < args.max_recursive_level and trace_flag and test_time and blend_mode is not False
+                         and not (rough or place or subst or objects))
+        evidence = mirror_fraction.get(level)
+        blended = can_blend and (blend_mode is True or (evidence is not None and evidence >= BLENDED_BREAK_EVEN))
+        count_it = can_blend and blend_mode is not True
         r = render_rays(models, embeddings, rays_chunk, N_samples, use_disp, 0, 0, N_importance, chunk,
                         white_back, test_time=test_time,
                         compute_normal=trace_flag and (not args.predict_normal),
                         only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
                         current_epoch=fine_epoch + 1, _guard=False, _maps_only=maps_only or rgb_depth,
-                        _rgb_depth_only=rgb_depth)
+                        _rgb_depth_only=rgb_depth, _blended_level=blended)
         r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
         r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
         if objects:                                                       # eval.py:173-291, ahead of the hard clip
@@ -784,13 +818,21 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         edit = None
         if place and not last:
             edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
-        pending, any_mirror = None, False
+        pending, any_mirror, counted = None, False, None
         if mask is not None:
             if host_flags is not None and not last and rays_chunk.shape[0]:
                 pending = _threshold_async(mask, host_flags, slot, edit)
+                if count_it:      # the count follows the flag to pinned memory; stage_b reads it behind its own event
+                    host = host_counts[slot:slot + 1]
+                    host.copy_(torch.count_nonzero(mask).view(1), non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    counted = (host, ev)
             else:
                 any_mirror = _threshold_(mask, want_any=not last, edit=edit)
-        return r, rays_chunk, level, mask, any_mirror, pending
+                if count_it and rays_chunk.shape[0]:
+                    mirror_fraction[level] = (int(torch.count_nonzero(mask).item()) if any_mirror else 0) / rays_chunk.shape[0]
+        return r, rays_chunk, level, mask, any_mirror, pending, counted
 
     def render_object(obj_rays):
         if obj_dnerf is not None:
@@ -808,9 +850,12 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         return stage_b(stage_a(rays_chunk, level))
 
     def stage_b(state):
-        r, rays_chunk, level, mask, any_mirror, pending = state
+        r, rays_chunk, level, mask, any_mirror, pending, counted = state
         if pending is not None:
             any_mirror = _flag_ready(pending)
+        if counted is not None:
+            counted[1].synchronize()
+            mirror_fraction[level] = int(counted[0].item()) / rays_chunk.shape[0]
         N = rays_chunk.shape[0]
         dev = rays_chunk.device
         only_in = not (level < 1)                                         # eval.py:159
@@ -892,6 +937,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     starts = list(range(0, rays.shape[0], chunk))
     pipelined = rays.is_cuda and not rough and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
     host_flags = torch.zeros(2, dtype=torch.int32).pin_memory() if pipelined else None
+    host_counts = torch.zeros(2, dtype=torch.int64).pin_memory() if pipelined else None
     ahead = stage_a(rays[:chunk].contiguous(), 0, host_flags, 0) if (pipelined and starts) else None
     for n_c, i in enumerate(starts):
         if pipelined:

@@ -24,6 +24,10 @@ Differences from the reference that do not change values:
     (set by batched_inference for a render of which only rgb_* / depth_* are read: the last reflection level, the substitution
     render) that pass produces only opacity_*, rgb_*, depth_* and z_vals_*: the kernel skips the mirror head
     (mnrf_field_composite_fused MNRF_FUSED_RGB_DEPTH); those maps are again identical bit for bit.
+  * `_blended_level=True` (set by batched_inference for a level that traces): the caller promises to replace rgb_* by
+    m * reflected + (1 - m) * rgb_* with m = 1 where mirror_mask_* is not below 0.5.  In eval the final pass then runs ray-fused
+    with MNRF_FUSED_BLENDED_LEVEL: rays at or above 0.5 get no colour branch and an rgb_* row of 0; every other key, the
+    per-sample ones included (unless `_maps_only`), is what the two-kernel path gives, bit for bit.
 Outputs live on rays.device.  When autograd is enabled and a model parameter (or `rays`) requires
 grad, the field evaluation and the compositing run through `autograd.FieldFn` / `CompositeFn`,
 whose backward passes are HIP kernels too (including the second-order term that reaches the
@@ -200,15 +204,21 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
     has_fine = "fine" in models
     results = {}
 
-    def inference_fused(model, typ, z):
+    def inference_fused(model, typ, z, blended=False):
         """Eval, per-ray maps only (`_maps_only`): field evaluation and compositing of the final pass in ONE kernel
         (mnrf_field_composite_fused): a workgroup owns a ray, the four head outputs never leave LDS.  Same maps bit for bit
         as the two-kernel path; the per-sample keys (weights_*, pred_normal_*) are not produced.  Returns False when the
-        launch class is not covered (the caller then takes the two-kernel path)."""
+        launch class is not covered (the caller then takes the two-kernel path).
+        `blended` (`_blended_level`: the caller will blend this level's colour with the thresholded mirror mask): the
+        blended-level launch (MNRF_FUSED_BLENDED_LEVEL), which leaves out the colour branch of every ray whose mirror value is
+        not below 0.5 and writes 0 to its rgb row -- the blend multiplies that row by zero.  It also writes the per-sample
+        weights and predicted normals unless `_maps_only`, so the level keeps every key of the two-kernel path."""
         from . import mirror_nerf as _mn
         from .weights import folded_of
         if _mn.precision_of(model) != "split" or z.shape[1] != L.mnrf_fused_samples_per_ray():
             return False
+        if blended:
+            return inference_fused_blended(model, typ, z)
         rgb_depth = bool(kwargs.get("_rgb_depth_only"))
         has_m = not rgb_depth and getattr(model, "predict_mirror_mask", True)
         has_n = not rgb_depth and getattr(model, "predict_normal", True)
@@ -241,6 +251,46 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
             results[f"_x_surface_{typ}"] = xs
         return True
 
+    def inference_fused_blended(model, typ, z):
+        from . import mirror_nerf as _mn
+        from .weights import folded_of
+        if not getattr(model, "predict_mirror_mask", True):      # nothing to decide from: the caller will not blend either
+            return False
+        S = z.shape[1]
+        has_n = getattr(model, "predict_normal", True)
+        per_sample = not kwargs.get("_maps_only")
+        opacity, rgb_map, depth, xs, mask = f(N), f(N, 3), f(N), f(N, 3), f(N)
+        sn = f(N, 3) if has_n else None
+        weights = f(N, S) if per_sample else None
+        pn = f(N, S, 3) if (per_sample and has_n) else None
+        flags = (_lib.MNRF_FUSED_WHITE_BACK if white_back else 0) | _lib.MNRF_FUSED_BLENDED_LEVEL
+        if _mn.LAUNCH_LOG is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        rc = L.mnrf_field_composite_fused_pn(p(folded_of(model)), N, p(rays), p(z), p(dir_emb), dir_emb.shape[1], flags,
+                                             p(weights), p(opacity), p(rgb_map), p(depth), p(mask), p(sn), p(xs), p(pn),
+                                             _lib.stream())
+        if rc == _lib.MNRF_ERR_UNSUPPORTED:          # the 48-samples-per-wave tuning is switched off
+            return False
+        _lib.check(rc, "mnrf_field_composite_fused_pn")
+        if _mn.LAUNCH_LOG is not None:
+            e1.record()
+            # 0x2000: ray-fused launch, 0x8000: its blended-level variant
+            _mn.LAUNCH_LOG.append((_lib.MNRF_SPLIT_F16 | 0x2000 | 0x8000, N * S, e0, e1))
+        if weights is not None:
+            results[f"weights_{typ}"] = weights
+        results[f"opacity_{typ}"] = opacity
+        results[f"z_vals_{typ}"] = z
+        results[f"rgb_{typ}"] = rgb_map
+        results[f"depth_{typ}"] = depth
+        results[f"mirror_mask_{typ}"] = mask
+        if pn is not None:
+            results[f"pred_normal_{typ}"] = pn
+        if has_n:
+            results[f"surface_normal_{typ}"] = sn
+        results[f"_x_surface_{typ}"] = xs
+        return True
+
     def inference(model, typ, z, noise_key):
         """rendering.py:108-264 for one pass.  In the sigma-only coarse pass the reference also
         evaluates (and discards) the normals; they are not computed here."""
@@ -249,8 +299,11 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         B = N * S
         if train and not sigma_only and N:
             return inference_train(model, typ, z, noise_key)
-        if (kwargs.get("_maps_only") and test_time and not sigma_only and N and not hashgrid and not compute_normal
-                and noise_std == 0 and kwargs.get(noise_key) is None and inference_fused(model, typ, z)):
+        fusable = (test_time and not sigma_only and N and not hashgrid and not compute_normal and noise_std == 0
+                   and kwargs.get(noise_key) is None)
+        if fusable and kwargs.get("_blended_level") and inference_fused(model, typ, z, blended=True):
+            return
+        if kwargs.get("_maps_only") and fusable and inference_fused(model, typ, z):
             return
         if N and hashgrid:
             o = model.field(B, rays=rays, z_vals=z, spr=S, dirs=dir_emb, sigma_only=sigma_only,
