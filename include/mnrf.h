@@ -915,6 +915,28 @@ int mnrf_frame_finish(const MnrfFrameMaps* maps, const MnrfFrameImages* images, 
 int mnrf_depth_colormap(const float* depth, const float* mask, int64_t frames, int64_t n, const float* extrema, float* stats,
                         const uint8_t* table, uint8_t* out, void* stream);
 
+/* ---- the validation panel (csrc/mnrf_frames.hip; utils/visualization.py:26-184 with add_text=False): the (n_tiles, 3, H, W)
+ * float32 stack the reference logs as val/GT_pred_depth, from the maps of one validation frame, read in place.  Two launches:
+ * the extrema launch reduces min and max of every GLOBAL and every DEPTH tile, the write launch produces the whole stack,
+ * every element once.  Each tile is the reference's expression in single fp32 operations (header comment of the kernels).
+ * maps: host array of n_tiles device pointers; kinds: one MNRF_PANEL_* per tile.  COPY, NORMAL and GLOBAL read an (H W, 3)
+ * map, MASK and DEPTH an (H W) map.  stats: n_tiles slots of mnrf_val_panel_stats_floats() floats, tile t's at
+ * [t * that]: [0] min, [1] max, the rest the reduction's state, ZERO before the first launch and left zero; only GLOBAL and
+ * DEPTH slots are touched, and stats may be null when there is no such tile.  At most 32 tiles.  n_tiles == 0 or H W == 0 is
+ * a no-op; a null array, a null map, a negative size or an unknown kind is refused before anything is launched. */
+#define MNRF_PANEL_COPY 0     /* out[c][p] = map[p][c] */
+#define MNRF_PANEL_MASK 1     /* out[c][p] = map[p] */
+#define MNRF_PANEL_NORMAL 2   /* out[c][p] = (map[p][c] + 1) / 2 */
+#define MNRF_PANEL_GLOBAL 3   /* visualize_rgb_map_global: (map - min) / (max - min) over the whole map; ones when min == max */
+#define MNRF_PANEL_DEPTH 4    /* visualize_depth with the map's own extremes, coloured through `table`, / 255 */
+int mnrf_val_panel_stats_floats(void);
+int mnrf_val_panel_extrema(const float* const* maps, MNRF_HOST const int* kinds, int n_tiles, int H, int W, float* stats,
+                           void* stream);
+/* table: (256, 3) bytes on the device as for mnrf_frame_finish (required with a DEPTH tile); stats as the extrema launch
+ * left it on the same stream; out: (n_tiles, 3, H, W) floats. */
+int mnrf_val_panel_write(const float* const* maps, MNRF_HOST const int* kinds, int n_tiles, int H, int W, const float* stats,
+                         const uint8_t* table, float* out, void* stream);
+
 /* ---- the ingest step of the ray bank (csrc/mnrf_resample.hip; datasets/real_arkit.py:236-237, 251-264): decoded frames are
  * resized on the device.  The arithmetic is Pillow's 8-bit resampler, stated in the header comment of csrc/mnrf_resample.hip:
  * a pass along x into `tmp`, rounded to 8 bits, then a pass along y; a pass whose sizes agree is not run.  src (frames, src_h,

@@ -8,6 +8,7 @@ rendering hot path behind the reference's own Python interfaces.
     from mirror_nerf_amd import get_loss                                # losses.py:258 (TotalLoss, fused value + gradient)
     from mirror_nerf_amd import RayBank, read_blender                   # datasets/blender.py: training batches drawn on the device
     from mirror_nerf_amd import finish_frame, SplitExtrema, colormap_depth   # eval.py:743-978: the 8-bit images of a frame
+    from mirror_nerf_amd import validation_step, validate, val_panel    # train.py:460-543, utils/visualization.py:26-184
 
 All arithmetic runs in libmnrf_hip.so (include/mnrf.h).  There is no CPU fallback.
 """
@@ -20,9 +21,10 @@ from .object_bounds import ObjectBounds, estimate_object_bounds  # noqa: F401
 from .losses import TotalLoss, get_loss  # noqa: F401
 from .data import RayBank, read_blender  # noqa: F401
 from . import frames  # noqa: F401
-from .frames import SplitExtrema, colormap_depth, finish_frame, jet_table  # noqa: F401
+from .frames import SplitExtrema, colormap_depth, finish_frame, jet_table, val_panel  # noqa: F401
+from .validation import validate, validation_step  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["Embedding", "MirrorNeRF", "render_rays", "sample_pdf", "NeRFSystem", "batched_inference",
            "render_rays_chunk_recursively", "DirectTemporalNeRF", "load_dnerf_object", "render_rays_dnerf", "ObjectBounds", "estimate_object_bounds", "TotalLoss", "get_loss", "RayBank", "read_blender", "frames", "finish_frame", "SplitExtrema",
-           "colormap_depth", "jet_table"]
+           "colormap_depth", "jet_table", "val_panel", "validation_step", "validate"]

@@ -67,3 +67,96 @@ def save_ckpt(path, system, epoch=0, global_step=0):
             for k, v in m.state_dict().items():
                 sd[f"{name}.{k}"] = v.detach().cpu()
     torch.save({"state_dict": sd, "epoch": epoch, "global_step": global_step}, path)
+
+
+_FIELDS = ("nerf_coarse", "nerf_fine")
+
+
+def _to_cpu(o):
+    """An optimizer state dict with every tensor as a CPU copy; dicts, lists and tuples keep their type."""
+    if isinstance(o, torch.Tensor):
+        return o.detach().cpu().clone()
+    if isinstance(o, dict):
+        return {k: _to_cpu(v) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return type(o)(_to_cpu(v) for v in o)
+    return o
+
+
+def save_training_state(path, system, optimizer, epoch, global_step, stream=None):
+    """A checkpoint a run can be resumed from (train.py:554-564, 574).  The file is Lightning-shaped: the `state_dict`, `epoch`
+    and `global_step` of save_ckpt, so load_ckpt, scripts/eval_scene.py --ckpt_path and the reference's load_ckpt read it as any
+    checkpoint, plus
+      optimizer_states  [optimizer.state_dict()] (training.FlatAdam's or torch Adam's), Lightning's key;
+      mnrf_training     lr (the first group's current value), grad_scale {field: the gradient-scale reductions of the split
+                        backward}, stream (the caller's position in the bank's shuffled stream: seed, step, epoch, stage ...,
+                        plain numbers), rng {cpu, cuda: the generators' states}.
+    Only tensors and plain containers are written: load_training_state reads it with the tensors-only unpickler."""
+    sd = {}
+    for name in _FIELDS:
+        m = getattr(system, name, None)
+        if m is not None:
+            for k, v in m.state_dict().items():
+                sd[f"{name}.{k}"] = v.detach().cpu().clone()
+    opt = optimizer.state_dict()
+    dev = next(system.parameters()).device
+    rng = {"cpu": torch.get_rng_state()}
+    if dev.type == "cuda":
+        rng["cuda"] = torch.cuda.get_rng_state(dev)
+    extra = {"lr": float(optimizer.param_groups[0]["lr"]),
+             "grad_scale": {name: int(getattr(system, name).__dict__.get("_mnrf_seed_reduction", 0))
+                            for name in _FIELDS if getattr(system, name, None) is not None},
+             "stream": {k: (v if isinstance(v, (bool, int, float, str)) or v is None else int(v)) for k, v in dict(stream or {}).items()},
+             "rng": rng}
+    torch.save({"state_dict": sd, "epoch": int(epoch), "global_step": int(global_step), "optimizer_states": [_to_cpu(opt)],
+                "lr_schedulers": [], "mnrf_training": extra}, path)
+
+
+def _set_rng(rng, device):
+    torch.set_rng_state(rng["cpu"])
+    if device.type == "cuda" and "cuda" in rng:
+        torch.cuda.set_rng_state(rng["cuda"], device)
+
+
+def restore_rng(path, device, trusted=False):
+    """The generators as save_training_state found them, for a caller that draws between loading a state and continuing
+    (load_training_state(..., restore_rng=False) first: capturing a training.GraphedTrainStep rehearses steps, which draw)."""
+    _set_rng(_load_file(os.fspath(path), trusted)["mnrf_training"]["rng"], torch.device(device))
+
+
+def load_training_state(path, system, optimizer=None, trusted=False, restore_rng=True):
+    """Put a save_training_state file back: the fields' parameters (in place: training.FlatAdam's views stay views), the
+    optimizer state and learning rate, the gradient-scale state and -- restore_rng -- the generators.  Load BEFORE a
+    GraphedTrainStep is built on the optimizer.  Unpickling follows _load_file (tensors and plain containers unless `trusted`).
+    Returns {"epoch", "global_step", "lr", "stream"}."""
+    ckpt = _load_file(os.fspath(path), trusted)
+    if "mnrf_training" not in ckpt:
+        raise RuntimeError(f"{path}: a checkpoint without training state (written by save_ckpt or by the reference): it can "
+                           "initialise the weights (load_ckpt) but a run cannot be resumed from it")
+    extra = ckpt["mnrf_training"]
+    with torch.no_grad():
+        for name in _FIELDS:
+            m = getattr(system, name, None)
+            if m is None:
+                continue
+            got = extract_model_state_dict(ckpt, name)
+            own = m.state_dict()
+            if sorted(got) != sorted(own):
+                raise RuntimeError(f"{path}: the parameters of {name} differ from the model's: {sorted(set(got) ^ set(own))}")
+            for k, v in own.items():
+                v.copy_(got[k])
+            m.__dict__.pop("_mnrf_seed_reduction", None)
+            if int(extra["grad_scale"].get(name, 0)):
+                m.__dict__["_mnrf_seed_reduction"] = int(extra["grad_scale"][name])
+            from .weights import invalidate_packed
+            invalidate_packed(m)
+    if optimizer is not None:
+        optimizer.load_state_dict(ckpt["optimizer_states"][0])
+        for g in optimizer.param_groups:
+            g["lr"] = float(extra["lr"])
+        if hasattr(optimizer, "_step_dev"):          # training.FlatAdam with device-resident state: the count lives there too
+            optimizer._step_dev.fill_(int(optimizer._calls))
+    if restore_rng:
+        _set_rng(extra["rng"], next(system.parameters()).device)
+    return {"epoch": int(ckpt["epoch"]), "global_step": int(ckpt["global_step"]), "lr": float(extra["lr"]),
+            "stream": dict(extra["stream"])}

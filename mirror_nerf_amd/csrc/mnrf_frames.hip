@@ -7,6 +7,8 @@
 //   frame_finish_kernel    every requested (n, 3) uint8 image, read in place from the float maps
 // and one more for the second pass over a split (save_depth_unified_normalization):
 //   depth_colormap_kernel  a stack of (F, n) resident depth maps coloured with one pair of extremes read from the device
+// and two for the validation panel of the training loop (utils/visualization.py:26-184; stated where they are defined, below):
+//   panel_extrema_kernel, panel_write_kernel    the (N_pics, 3, H, W) float32 stack of visualize_val_image(add_text=False)
 //
 // ARITHMETIC.  Every image is the reference's expression, one IEEE fp32 operation after the other in its order (compiled with
 // -ffp-contract=off, hipcc's correctly rounded fp32 division, no fast-math), so the bytes are numpy's:
@@ -306,6 +308,164 @@ __global__ __launch_bounds__(TPB) void depth_colormap_kernel(const float* depth,
                 (long long)blockIdx.x * TPB + threadIdx.x, (long long)gridDim.x * TPB);
 }
 
+// ---------------------------------------------------------------- the validation panel (utils/visualization.py:26-184)
+//
+// The (N_pics, 3, H, W) float32 stack of visualize_val_image(..., add_text=False), two launches:
+//   panel_extrema_kernel   min and max of every global and every depth tile into that tile's 8-float stats slot
+//                          ([0] min, [1] max, [2] [3] accumulators, [4] ticket; zero before the first launch, left zero)
+//   panel_write_kernel     the whole stack: a thread takes 4 consecutive pixels of one tile, reads its map in place and stores
+//                          one 16-byte row piece per channel, so every output element is written once, along W
+// Tile t of kind k from map m, n = H W pixels p, channel c:
+//   copy    out[c][p] = m[3 p + c]                                        view(H, W, 3).permute(2, 0, 1)
+//   mask    out[c][p] = m[p]                                              unsqueeze(-1).repeat(1, 3)
+//   normal  out[c][p] = (m[3 p + c] + 1) / 2
+//   global  out[c][p] = mn == mx ? 1 : (m[3 p + c] - mn) / (mx - mn)      mn, mx over all 3 n values, NaN propagating
+//   depth   x = clip(n2n(m[p]), mi, ma); x = (x - mi) / max(ma - mi, 1e-8f); k = u8(255 x); out[c][p] = float(T[k][c]) / 255
+//           with mi, ma the min and max of n2n(m)
+
+constexpr int PANEL_MAX_TILES = 32;        // the reference's panel has at most 24
+constexpr int PANEL_STATS = 8;
+
+struct PanelExtremaArgs {
+    const float* src[PANEL_MAX_TILES];     // the tiles that need extremes, compacted
+    float* stats[PANEL_MAX_TILES];         // their slots
+    unsigned char depth[PANEL_MAX_TILES];  // 1: n values through n2n; 0: 3 n values, a NaN poisons both extremes
+    long long n;
+};
+
+__global__ __launch_bounds__(TPB) void panel_extrema_kernel(PanelExtremaArgs A) {
+    __shared__ uint32_t red[WAVES][2];
+    __shared__ int last;
+    const int t = blockIdx.y;
+    const float* p = A.src[t];
+    const bool depth = A.depth[t] != 0;
+    const long long total = depth ? A.n : 3 * A.n;
+    const long long t0 = (long long)blockIdx.x * TPB + threadIdx.x, step = (long long)gridDim.x * TPB;
+    uint32_t a[2] = {0u, 0u};
+    for (long long i = t0; i < total; i += step) {
+        const float raw = p[i];
+        const bool poison = !depth && raw != raw;
+        const uint32_t k = key_of(depth ? n2n(raw) : raw);
+        a[0] = umax(a[0], poison ? 0xffffffffu : ~k);
+        a[1] = umax(a[1], poison ? 0xffffffffu : k);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        for (int o = 32; o > 0; o >>= 1) a[i] = umax(a[i], (uint32_t)__shfl_xor((int)a[i], o));
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = a[0];
+        red[threadIdx.x >> 6][1] = a[1];
+    }
+    __syncthreads();
+    uint32_t* acc = reinterpret_cast<uint32_t*>(A.stats[t]);
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < 2; ++i) {
+            uint32_t m = red[0][i];
+            for (int w = 1; w < WAVES; ++w) m = umax(m, red[w][i]);
+            if (m) atomicMax(acc + 2 + i, m);
+        }
+        __threadfence();
+        last = atomicAdd(acc + 4, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || threadIdx.x != 0) return;
+    __threadfence();
+    for (int i = 0; i < 2; ++i) {
+        const uint32_t e = atomicExch(acc + 2 + i, 0u);
+        A.stats[t][i] = (e == 0u || e == 0xffffffffu) ? __builtin_nanf("") : float_of(i ? e : ~e);
+    }
+    atomicExch(acc + 4, 0u);
+}
+
+struct PanelWriteArgs {
+    const float* src[PANEL_MAX_TILES];
+    unsigned char kind[PANEL_MAX_TILES];
+    long long n;
+    const float* stats;                    // (tiles, PANEL_STATS)
+    const uint8_t* table;
+    float* out;                            // (tiles, 3, n)
+};
+
+__global__ __launch_bounds__(TPB) void panel_write_kernel(PanelWriteArgs A) {
+    const int t = blockIdx.y, kind = A.kind[t];
+    const long long n = A.n;
+    const float* m = A.src[t];
+    float* out = A.out + (long long)t * 3 * n;
+    const bool pixel_map = kind == MNRF_PANEL_MASK || kind == MNRF_PANEL_DEPTH;
+    const bool ia = aligned(m, 16);
+    float lo = 0.f, hi = 0.f;
+    if (kind == MNRF_PANEL_GLOBAL || kind == MNRF_PANEL_DEPTH) {
+        lo = A.stats[t * PANEL_STATS];
+        hi = A.stats[t * PANEL_STATS + 1];
+    }
+    const float range = hi - lo;
+    const float den = (1e-8f > range) ? 1e-8f : range;               // Python's max(ma - mi, 1e-8)
+    const long long q0 = (long long)blockIdx.x * TPB + threadIdx.x, step = (long long)gridDim.x * TPB;
+    for (long long q = q0; 4 * q < n; q += step) {
+        const long long p = 4 * q;
+        const int cnt = n - p < 4 ? (int)(n - p) : 4;
+        float o[3][4];
+        if (pixel_map) {
+            float v[4];
+            load4(m, p, n, ia, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (kind == MNRF_PANEL_MASK) {
+                    o[0][j] = o[1][j] = o[2][j] = v[j];
+                } else {
+                    const float x = (clip(n2n(v[j]), lo, hi) - lo) / den;
+                    const uint32_t k = u8(255.0f * x);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) o[c][j] = (float)A.table[k * 3 + c] / 255.0f;     // ToTensor()
+                }
+            }
+        } else {
+            float v[12];
+#pragma unroll
+            for (int g = 0; g < 3; ++g) load4(m, 3 * p + 4 * g, 3 * n, ia, v + 4 * g);
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                float x = v[j];
+                if (kind == MNRF_PANEL_NORMAL) x = (x + 1.0f) / 2.0f;
+                else if (kind == MNRF_PANEL_GLOBAL) x = (lo == hi) ? 1.0f : (x - lo) / range;
+                o[j % 3][j / 3] = x;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float* row = out + c * n + p;
+            if (cnt == 4 && aligned(row, 16)) {
+                *reinterpret_cast<float4*>(row) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < cnt) row[j] = o[c][j];
+            }
+        }
+    }
+}
+
+// the checks the two panel entry points share; 0, or the error already recorded
+int panel_check(const char* who, const float* const* maps, const int* kinds, int n_tiles, int H, int W, const void* stats) {
+    char msg[160];
+    const auto fail = [&](const char* what) {
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return mnrf_fail(MNRF_ERR_ARG, msg);
+    };
+    if (n_tiles < 0 || n_tiles > PANEL_MAX_TILES) return fail("bad tile count (0 .. 32)");
+    if (H < 0 || W < 0) return fail("negative frame size");
+    if (n_tiles == 0) return MNRF_OK;
+    if (!maps || !kinds) return fail("null maps or kinds array");
+    bool reduced = false;
+    for (int t = 0; t < n_tiles; ++t) {
+        if (kinds[t] < MNRF_PANEL_COPY || kinds[t] > MNRF_PANEL_DEPTH) return fail("unknown tile kind");
+        if (!maps[t]) return fail("null map");
+        reduced |= kinds[t] == MNRF_PANEL_GLOBAL || kinds[t] == MNRF_PANEL_DEPTH;
+    }
+    if (reduced && !stats) return fail("a global or depth tile needs the stats block");
+    return MNRF_OK;
+}
+
 unsigned blocks_for(int64_t items, int per_thread, unsigned cap) {
     const int64_t b = (items + (int64_t)TPB * per_thread - 1) / ((int64_t)TPB * per_thread);
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -362,4 +522,47 @@ extern "C" int mnrf_depth_colormap(const float* depth, const float* mask, int64_
                        depth, mask, (long long)n, extrema ? extrema : (const float*)stats,
                        (long long)(extrema ? 0 : STATS_FLOATS), table, out);
     return mnrf_check_launch("mnrf_depth_colormap");
+}
+
+extern "C" int mnrf_val_panel_stats_floats(void) { return PANEL_STATS; }
+
+extern "C" int mnrf_val_panel_extrema(const float* const* maps, const int* kinds, int n_tiles, int H, int W, float* stats,
+                                      void* stream) {
+    if (const int e = panel_check("mnrf_val_panel_extrema", maps, kinds, n_tiles, H, W, stats)) return e;
+    const int64_t n = (int64_t)H * W;
+    if (n_tiles == 0 || n == 0) return MNRF_OK;
+    PanelExtremaArgs A;
+    A.n = n;
+    int r = 0;
+    for (int t = 0; t < n_tiles; ++t) {
+        if (kinds[t] != MNRF_PANEL_GLOBAL && kinds[t] != MNRF_PANEL_DEPTH) continue;
+        A.src[r] = maps[t];
+        A.stats[r] = stats + (int64_t)t * PANEL_STATS;
+        A.depth[r++] = kinds[t] == MNRF_PANEL_DEPTH;
+    }
+    if (r == 0) return MNRF_OK;
+    hipLaunchKernelGGL(panel_extrema_kernel, dim3(blocks_for(3 * n, 4, 256), (unsigned)r), dim3(TPB), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_val_panel_extrema");
+}
+
+extern "C" int mnrf_val_panel_write(const float* const* maps, const int* kinds, int n_tiles, int H, int W, const float* stats,
+                                    const uint8_t* table, float* out, void* stream) {
+    if (const int e = panel_check("mnrf_val_panel_write", maps, kinds, n_tiles, H, W, stats)) return e;
+    const int64_t n = (int64_t)H * W;
+    if (n_tiles == 0) return MNRF_OK;
+    PanelWriteArgs A;
+    for (int t = 0; t < n_tiles; ++t) {
+        if (kinds[t] == MNRF_PANEL_DEPTH && !table)
+            return mnrf_fail(MNRF_ERR_ARG, "mnrf_val_panel_write: a depth tile needs the colour table");
+        A.src[t] = maps[t];
+        A.kind[t] = (unsigned char)kinds[t];
+    }
+    if (n == 0) return MNRF_OK;
+    if (!out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_val_panel_write: null output stack");
+    A.n = n;
+    A.stats = stats;
+    A.table = table;
+    A.out = out;
+    hipLaunchKernelGGL(panel_write_kernel, dim3(blocks_for(n, 4, 1024), (unsigned)n_tiles), dim3(TPB), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_val_panel_write");
 }

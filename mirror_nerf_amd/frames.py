@@ -10,6 +10,9 @@ numpy gives for them.
     ...                                                  # after the last frame: save_depth_unified_normalization
     unified = colormap_depth(depth_stack, extrema.depth)
 
+`val_panel(img_wh, batch, results)` is the training loop's counterpart (utils/visualization.py:26-184, add_text=False): the
+(N_pics, 3, H, W) float32 panel the reference logs as val/GT_pred_depth, with the reference's tile labels, in two launches.
+
 The colour table is an argument: `jet_table()` restates the classic piecewise-linear jet in the channel order cv2 emits; it
 is not pinned against cv2.COLORMAP_JET (neither cv2 nor its table is available to this project)."""
 import ctypes
@@ -186,3 +189,64 @@ def colormap_depth(depth_stack, extrema=None, mask_stack=None, table=None):
                                      None if ex is None else ex.data_ptr(), None if stats is None else stats.data_ptr(),
                                      tab.data_ptr(), out.data_ptr(), _lib.stream()), "mnrf_depth_colormap")
     return out[0] if single else out
+
+
+_PANEL_VECTOR = (_lib.MNRF_PANEL_COPY, _lib.MNRF_PANEL_NORMAL, _lib.MNRF_PANEL_GLOBAL)
+
+
+def val_panel_tiles(batch, results):
+    """The tiles of visualize_val_image in its order (utils/visualization.py:32-179) as (name, kind, map) triples; a key that
+    is absent from `results` or `batch` contributes no tile."""
+    COPY, MASK, NORMAL = _lib.MNRF_PANEL_COPY, _lib.MNRF_PANEL_MASK, _lib.MNRF_PANEL_NORMAL
+    GLOBAL, DEPTH = _lib.MNRF_PANEL_GLOBAL, _lib.MNRF_PANEL_DEPTH
+    typs = ("fine", "coarse")
+    tiles = [("gt_img", COPY, batch["rgbs"])]
+    for key, name, kind in (("rgb_{}", "img_{}", COPY), ("rgb_{}_reflect", "img_reflect_{}", COPY),
+                            ("rgb_{}_direct", "img_direct_{}", COPY), ("depth_{}", "depth_{}", DEPTH),
+                            ("depth_{}_reflect", "depth_reflect_{}", DEPTH)):
+        tiles += [(name.format(t), kind, results[key.format(t)]) for t in typs if key.format(t) in results]
+    if "mirror_mask" in batch:
+        tiles.append(("gt_mirror_mask", MASK, batch["mirror_mask"]))
+    tiles += [(f"mirror_mask_pred_{t}", MASK, results[f"mirror_mask_{t}"]) for t in typs if f"mirror_mask_{t}" in results]
+    for t in typs:
+        if f"surface_normal_{t}" in results:
+            tiles.append((f"normal_pred_{t}", NORMAL, results[f"surface_normal_{t}"]))
+        if f"surface_normal_grad_{t}" in results:
+            tiles.append((f"normal_grad_{t}", NORMAL, results[f"surface_normal_grad_{t}"]))
+    for key in ("secondary_rays_o", "reflect_direction"):
+        if key in results:
+            tiles += [(key, COPY, results[key]), (f"{key}_vis", GLOBAL, results[key])]
+    tiles += [(f"x_surface_{t}", GLOBAL, results[f"x_surface_{t}"]) for t in typs if f"x_surface_{t}" in results]
+    return tiles
+
+
+def val_panel(img_wh, batch, results, table=None):
+    """visualize_val_image(img_wh, batch, results, add_text=False) (utils/visualization.py:26-184) on the device: `(stack,
+    names)` with stack the (N_pics, 3, H, W) float32 panel the reference logs as val/GT_pred_depth and names the reference's
+    label of every tile in the same order ("gt_img", "img_fine", ..., "x_surface_coarse").  batch: {"rgbs": (H W, 3)[,
+    "mirror_mask": (H W)]} and results: the eval-semantics maps, all float32 on the device; they are read in place and left
+    unchanged.  Every tile is the reference's expression in single fp32 operations; the depth tiles are coloured
+    through `table` (default jet_table()).  Two launches (csrc/mnrf_frames.hip), no host synchronisation.  Only the
+    reference's --for_vis form: no captions are drawn into the tiles."""
+    L = _lib.lib()
+    W, H = (int(v) for v in img_wh)
+    n = H * W
+    tiles = val_panel_tiles(batch, results)
+    maps = []
+    for name, kind, t in tiles:
+        if isinstance(t, torch.Tensor) and kind not in _PANEL_VECTOR:
+            t = t.reshape(-1)                  # the reference's .squeeze(): (1, n) and (n, 1) maps are (n)
+        elif isinstance(t, torch.Tensor) and t.dim() == 3 and t.shape[0] == 1:
+            t = t[0]
+        maps.append(_map(t, name, n, (3,) if kind in _PANEL_VECTOR else ()))
+    dev = maps[0].device
+    names = [name for name, _, _ in tiles]
+    kinds = (ctypes.c_int * len(tiles))(*[kind for _, kind, _ in tiles])
+    ptrs = (ctypes.c_void_p * len(tiles))(*[m.data_ptr() for m in maps])
+    tab = _table(table, dev) if _lib.MNRF_PANEL_DEPTH in list(kinds) else None
+    stats = torch.zeros((len(tiles), L.mnrf_val_panel_stats_floats()), dtype=torch.float32, device=dev)
+    stack = torch.empty((len(tiles), 3, H, W), dtype=torch.float32, device=dev)
+    _lib.check(L.mnrf_val_panel_extrema(ptrs, kinds, len(tiles), H, W, stats.data_ptr(), _lib.stream()), "mnrf_val_panel_extrema")
+    _lib.check(L.mnrf_val_panel_write(ptrs, kinds, len(tiles), H, W, stats.data_ptr(), None if tab is None else tab.data_ptr(),
+                                      stack.data_ptr(), _lib.stream()), "mnrf_val_panel_write")
+    return stack, names

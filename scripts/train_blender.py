@@ -10,6 +10,18 @@ average pose of transforms.json and divided by --scale_factor, and the frames ar
 (RayBank.from_arkit).
 
     python scripts/train_blender.py --root_dir data/scene --img_wh 400 400 --near 2 --far 6 --steps 20000 --route graph --out weights.npz
+
+The validation half of the reference's loop (train.py:460-564, 574) is opt-in; without these options a run is what it was:
+  --val_every F    validate every F-th of an epoch (the reference's val_check_interval is 0.25) on the frames of
+                   transforms_val.json / the ARKit `val` split (--val_frames picks some of them), between two steps on the same
+                   stream; a captured step is kept and replayed afterwards (mirror_nerf_amd/validation.py)
+  --log_dir D      val.jsonl, one line per validation with the reference's val/* names, and val_panel_{step}.png, the
+                   val/GT_pred_depth panel of the first validation frame as a grid (val_panel_{step}.json names the tiles)
+  --ckpt_dir D     epoch={epoch}.ckpt (Lightning's file name for the reference's filename="{epoch:d}") and last.ckpt at the end
+                   of every epoch and of the run, resumable (checkpoint.save_training_state); best.json says which epoch had
+                   the best val/psnr
+  --resume PATH    continue such a checkpoint: weights, optimizer, learning rate, gradient-scale state, the position in the
+                   shuffled stream and the generators; --steps stays the TOTAL, so K steps + a resumed run to 2K is a 2K run
 """
 import argparse
 import json
@@ -25,11 +37,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import mirror_nerf_amd as M  # noqa: E402
-from mirror_nerf_amd import dist, training  # noqa: E402
+from mirror_nerf_amd import checkpoint, dist, training  # noqa: E402
 from mirror_nerf_amd.data import RayBank  # noqa: E402
 
 
-def main():
+def save_panel(path, stack, names):
+    """The (N, 3, H, W) panel as one PNG: the tiles in a grid, row-major in the reference's order, a one-pixel gap between them
+    (PIL; the 8-bit cast is the output stage's: clip to [0, 1], times 255, truncated).  The tile names go beside it as JSON."""
+    from PIL import Image
+    n, _, h, w = stack.shape
+    cols = int(np.ceil(np.sqrt(n)))
+    rows = (n + cols - 1) // cols
+    tiles = (stack.clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()      # a NaN tile casts to 0
+    grid = np.zeros((rows * (h + 1) - 1, cols * (w + 1) - 1, 3), np.uint8)
+    for i in range(n):
+        r, c = divmod(i, cols)
+        grid[r * (h + 1):r * (h + 1) + h, c * (w + 1):c * (w + 1) + w] = tiles[i]
+    Image.fromarray(grid).save(path)
+    with open(os.path.splitext(path)[0] + ".json", "w") as f:
+        json.dump({"names": names, "cols": cols, "rows": rows, "tile_wh": [w, h], "gap": 1}, f)
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--root_dir", required=True)
     ap.add_argument("--img_wh", type=int, nargs=2, default=(800, 800))
@@ -51,7 +80,15 @@ def main():
                     help="epochs of the geometry stage at the start (--train_geometry_stage): no reflections, frames with a valid mask only")
     ap.add_argument("--precision", default="split")
     ap.add_argument("--out", default="blender_weights.npz", help="where the weights are written")
-    a = ap.parse_args()
+    ap.add_argument("--val_every", type=float, default=0.0, help="validate every this fraction of an epoch (the reference: 0.25); 0 = never")
+    ap.add_argument("--val_frames", type=int, nargs="*", default=None, help="frames of the validation split to validate on (default: all)")
+    ap.add_argument("--ckpt_dir", default=None, help="epoch={epoch}.ckpt and last.ckpt every epoch, best.json (train.py:554-564)")
+    ap.add_argument("--resume", default=None, help="a checkpoint of --ckpt_dir to continue (train.py:574)")
+    ap.add_argument("--trusted", action="store_true", help="--resume: unpickle the checkpoint fully (only for files you wrote)")
+    ap.add_argument("--log_dir", default=None, help="val.jsonl and the validation panels")
+    a = ap.parse_args(argv)
+    if a.val_every < 0:
+        raise SystemExit("--val_every must not be negative")
     dev = torch.device("cuda", 0)
     M.set_precision(a.precision)
     torch.manual_seed(a.seed)
@@ -83,20 +120,78 @@ def main():
             else training.color_mask_loss
         return bank, loss_fn, (stage or len(full.frames_with_mask) == full.n_frames)
 
+    val_bank = val_loss = None
+    if a.val_every > 0:
+        from mirror_nerf_amd import get_loss, validation
+        if a.dataset_name == "real_arkit":
+            val_bank = RayBank.from_arkit(a.root_dir, "val", tuple(a.img_wh), a.near, a.far, a.scale_factor, a.val_idx, device=dev)
+        else:
+            val_bank = RayBank.from_blender(a.root_dir, "val", tuple(a.img_wh), a.near, a.far, device=dev)
+        val_loss = get_loss(SimpleNamespace(model_type="nerf"))
+    for d in (a.ckpt_dir, a.log_dir):
+        if d:
+            os.makedirs(d, exist_ok=True)
+    best = {"monitor": "val/psnr", "best_epoch": None, "best_score": None}
+    last_val = [None]
+
+    def validate_now(step):
+        """train.py:460-543 between two steps; one host read.  The training state, a captured step included, is left as it was."""
+        means, _logs, panel = validation.validate(system, val_bank, val_loss, epoch, hp, frames=a.val_frames,
+                                                  want_panel=a.log_dir is not None)
+        last_val[0] = means["val/psnr"]
+        print(f"step {step:6d}  epoch {epoch}  " + "  ".join(f"{k} {v:.4f}" for k, v in means.items() if k in ("val/loss", "val/psnr")), flush=True)
+        if a.log_dir and rank == 0:
+            with open(os.path.join(a.log_dir, "val.jsonl"), "a") as f:
+                f.write(json.dumps(dict(means, step=step, epoch=epoch)) + "\n")
+            if panel is not None:
+                save_panel(os.path.join(a.log_dir, f"val_panel_{step}.png"), *panel)
+
+    def save_epoch(ep, steps_done, final=False):
+        """train.py:554-564: the epoch's checkpoint and last.ckpt; the best val/psnr so far is recorded beside them."""
+        stream = dict(seed=a.seed, step=steps_done, epoch=epoch, first=first, epoch_first=epoch_first, batch=a.batch,
+                      stage=bool(system.train_geometry_stage), total_steps=a.steps)
+        checkpoint.save_training_state(os.path.join(a.ckpt_dir, "last.ckpt"), system, opt, ep, steps_done, stream=stream)
+        if not final:
+            import shutil
+            shutil.copyfile(os.path.join(a.ckpt_dir, "last.ckpt"), os.path.join(a.ckpt_dir, f"epoch={ep}.ckpt"))
+            if last_val[0] is not None and last_val[0] == last_val[0] and (best["best_score"] is None or last_val[0] > best["best_score"]):
+                best.update(best_epoch=ep, best_score=last_val[0])
+        with open(os.path.join(a.ckpt_dir, "best.json"), "w") as f:
+            json.dump(best, f)
+
     # the epoch is the stream's: every ray of the bank once.  The stage's bank is a subset, so its epochs are shorter; where the
     # selection changes the stream starts again at position 0 of the new bank (`first`, `epoch_first`)
-    epoch, first, epoch_first = 0, 0, 0
-    bank, loss_fn, gt_valid = setup(0)
-    graphed = training.GraphedTrainStep(system, opt, a.batch, loss_fn, epoch=0, gt_valid=gt_valid) if a.route == "graph" else None
+    epoch, first, epoch_first, start = 0, 0, 0, 0
+    resumed = None
+    if a.resume:
+        # (the generators are put back below, behind the capture of the graph route: its rehearsal steps draw)
+        resumed = checkpoint.load_training_state(a.resume, system, opt, trusted=a.trusted, restore_rng=False)
+        st = resumed["stream"]
+        if (st["seed"], st["batch"], st["total_steps"]) != (a.seed, a.batch, a.steps):
+            raise SystemExit(f"--resume: the checkpoint was written with --seed {st['seed']} --batch {st['batch']} --steps {st['total_steps']}; "
+                             "continue it with the same (the stream and the learning-rate schedule depend on them)")
+        epoch, first, epoch_first, start = st["epoch"], st["first"], st["epoch_first"], st["step"]
+        if a.ckpt_dir and os.path.exists(os.path.join(a.ckpt_dir, "best.json")):
+            with open(os.path.join(a.ckpt_dir, "best.json")) as f:
+                best.update(json.load(f))
+        print(f"resumed {a.resume}: step {start}, epoch {epoch}, lr {resumed['lr']:.3e}", flush=True)
+    bank, loss_fn, gt_valid = setup(epoch)
+    graphed = training.GraphedTrainStep(system, opt, a.batch, loss_fn, epoch=epoch, gt_valid=gt_valid) if a.route == "graph" else None
+    if resumed is not None:
+        if graphed is not None:
+            graphed.capture()
+        checkpoint.restore_rng(a.resume, dev, trusted=a.trusted)
     if graphed is not None:
         out = (graphed.rays, graphed.target, graphed.gt)
     else:
         out = (torch.empty(a.batch, 8, device=dev), torch.empty(a.batch, 3, device=dev), torch.empty(a.batch, device=dev))
     t0 = time.time()
     loss = None
-    for it in range(a.steps):
+    for it in range(start, a.steps):
         e = epoch_first + bank.epoch_of(it - first, a.batch, world)
         if e != epoch:
+            if a.ckpt_dir and rank == 0:
+                save_epoch(epoch, it)
             epoch, n_before = e, bank.n_rays
             bank, loss_fn, gt_valid = setup(epoch)
             if bank.n_rays != n_before:
@@ -112,8 +207,16 @@ def main():
         else:
             loss = training.train_step(system, opt, rays, rgbs, mask, loss_fn, epoch=epoch, gt_valid=gt_valid if a.route == "static" else None)
         opt.param_groups[0]["lr"] *= gamma
+        if val_bank is not None:
+            # val_check_interval (train.py:585): every int(batches per epoch * fraction) batches of the epoch
+            per_epoch = max(1, bank.n_rays // (a.batch * world))
+            every = max(1, int(per_epoch * a.val_every))
+            if ((it - first) % per_epoch + 1) % every == 0:
+                validate_now(it + 1)
         if it % 1000 == 0 or it == a.steps - 1:
             print(f"step {it:6d}  epoch {epoch}  loss {loss.item():.4f}  [{time.time() - t0:.0f} s]", flush=True)
+    if a.ckpt_dir and rank == 0:
+        save_epoch(epoch, a.steps, final=True)
     arrs = {}
     for mname, mod in (("coarse", system.nerf_coarse), ("fine", system.nerf_fine)):
         for k, v in mod.state_dict().items():
