@@ -16,16 +16,14 @@ Trained weights amplify activation gradients on their way down the trunk: on the
 f16 range of the planes (non-finite weight gradients), which training answers by lowering that module's gradient scale by 2^4
 (mirror_nerf._lower_gradient_scale).  `_lowering_scale` does the same here, at most twice, and reports it."""
 import ctypes
-import math
 
 import pytest
 import torch
 
 from tests import torch_ref as TR
+from tests.field_fp64 import DEV, F64, _rel, _rows_forward, _saved, _sec      # shared with tests/test_hip_forward_fp64.py
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-F64 = torch.float64
 
 LADDER = [1, 31, 32, 33, 127, 128, 129, 191, 192, 193, 511, 512, 513, 4096 + 77, 32769]
 BIG = 262145          # dw_small_splits hits its cap of 2048 splits
@@ -40,40 +38,7 @@ def precision(request):
     MN.set_precision(old)
 
 
-# ---------------------------------------------------------------------------------------------- layout (mnrf_layout.h)
-SEC_ENC, SEC_H, SEC_FIN, SEC_DIRE, SEC_HD, SEC_HN, SEC_HM = 0, 64, 2112, 2368, 2400, 2528, 2656
 DY_L, DY_FIN, DY_DIR, DY_NRM1, DY_MIR1, DY_RGB, DY_NRM2, DY_MIR2 = 0, 2048, 2304, 2432, 2560, 2688, 2704, 2720
-
-
-def _enc_col(t, g):
-    P, s = 8 * g + (t >> 1), t & 1
-    if P < 30:
-        return 3 + 6 * (P // 3) + 3 * s + (P % 3)
-    if P == 30:
-        return s
-    return 2 if s == 0 else -1
-
-
-ENCPOS = [0] * 63          # logical column of the 63-wide xyz encoding -> its position in the saved (sin,cos)-pair order
-for _g in range(4):
-    for _t in range(16):
-        _c = _enc_col(_t, _g)
-        if _c >= 0:
-            ENCPOS[_c] = 16 * (_t >> 2) + 4 * _g + (_t & 3)
-
-
-def _sec(buf, off, width, B):
-    return buf[off * B:(off + width) * B].view(B, width)
-
-
-def _rel(a, b):
-    """max |a - b| over the largest |b|; a reference of exact zeros must be met by exact zeros."""
-    a, b = a.double(), b.double()
-    s = float(b.abs().max()) if b.numel() else 0.0
-    d = float((a - b).abs().max()) if b.numel() else 0.0
-    if s == 0.0:
-        return 0.0 if d == 0.0 else math.inf
-    return d / s
 
 
 # ---------------------------------------------------------------------------------------------- weights and inputs
@@ -119,35 +84,6 @@ def _cots(B, profile, seed, normal=None):
     if normal is not None:
         c.append(normal)
     return c
-
-
-# ---------------------------------------------------------------------------------------------- the kernel's own forward
-def _rows_forward(model, inp, split):
-    """Rows-route mnrf_field_forward_train (fp32 rows of every Linear's input) with the arithmetic flag of `split`."""
-    from mirror_nerf_amd import _lib
-    from mirror_nerf_amd.weights import packed_of
-    L, p = _lib.lib(), _lib.ptr
-    B = inp["B"]
-    f = lambda *s: torch.empty(*s, dtype=torch.float32, device=DEV)  # noqa: E731
-    o = (f(B), f(B, 3), f(B, 3), f(B), f(B, 3))
-    sx = f(L.mnrf_train_save_floats(B))
-    sm = torch.zeros(L.mnrf_train_mask_words(B), dtype=torch.int64, device=DEV)
-    si, sj = f(B), f(B)
-    packed = packed_of(model)
-    _lib.check(L.mnrf_field_forward_train(p(packed), B, p(inp["xyz"]), 3, p(inp["rays"]), p(inp["z"]), inp["spr"], p(inp["de"]), 27,
-                                          *[p(t) for t in o], p(sx), p(sm), p(si), p(sj), _lib.MNRF_SPLIT_F16 if split else 0,
-                                          _lib.stream()), "forward rows")
-    return dict(packed=packed, out=o, sx=sx, sm=sm, si=si, sj=sj)
-
-
-def _saved(sx, B, rows=None):
-    """The saved Linear inputs (float64, logical column order), optionally of some samples only."""
-    s = lambda off, w: _sec(sx, off, w, B) if rows is None else _sec(sx, off, w, B)[rows]  # noqa: E731
-    d = {"enc": s(SEC_ENC, 64)[:, ENCPOS]}
-    for i in range(8):
-        d[f"h{i + 1}"] = s(SEC_H + 256 * i, 256)
-    d.update(fin=s(SEC_FIN, 256), dire=s(SEC_DIRE, 32), hd=s(SEC_HD, 128), hn=s(SEC_HN, 128), hm=s(SEC_HM, 128))
-    return {k: v.to(F64) for k, v in d.items()}
 
 
 def _kernel_masks(w64, saved, de64, tag=""):

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import mirror_nerf_oracle as O
+from tests import field_fp64 as FC
 from tests import rays_cases as RC
 from tests import torch_ref as TR
 
@@ -188,3 +189,164 @@ def test_ray_grads_restatement_is_the_stated_sums():
                                    [0, 0]])
             assert np.allclose(g_rays[i].numpy(), want, rtol=1e-13, atol=1e-13)
             assert np.allclose(g_de[i].numpy(), d_dir[rows, :27].double().numpy().sum(0), rtol=1e-13, atol=1e-13)
+
+
+# ---- the extension of TR.field for tests/test_hip_forward_fp64.py: position bands as a parameter, absent heads
+def _field_before(w, xyz, dir_emb, with_normal=False):
+    """TR.field as it stood before the extension (10 bands, both heads), restated: what the extended function must still be."""
+    if with_normal and not xyz.requires_grad:
+        xyz = xyz.requires_grad_(True)
+    enc = TR.embed(xyz, 10)
+    h = enc
+    for i in range(8):
+        if i == 4:
+            h = torch.cat([enc, h], -1)
+        h = torch.relu(h @ w[f"xyz_encoding_{i+1}.0.weight"].T + w[f"xyz_encoding_{i+1}.0.bias"])
+    sigma = (h @ w["sigma.weight"].T + w["sigma.bias"])[:, 0]
+    fin = h @ w["xyz_encoding_final.weight"].T + w["xyz_encoding_final.bias"]
+    hd = torch.relu(torch.cat([fin, dir_emb], -1) @ w["dir_encoding.0.weight"].T + w["dir_encoding.0.bias"])
+    rgb = torch.sigmoid(hd @ w["rgb.0.weight"].T + w["rgb.0.bias"])
+    hn = h @ w["normal_net.0.weight"].T + w["normal_net.0.bias"]
+    pn = TR.l2n(hn @ w["normal_net.1.weight"].T + w["normal_net.1.bias"])
+    hm = torch.nn.functional.leaky_relu(h @ w["is_mirror_net.0.weight"].T + w["is_mirror_net.0.bias"], 0.01)
+    m = torch.sigmoid(hm @ w["is_mirror_net.2.weight"].T + w["is_mirror_net.2.bias"])[:, 0]
+    if with_normal:
+        (grad,) = torch.autograd.grad(sigma, xyz, torch.ones_like(sigma), create_graph=True, retain_graph=True)
+        return sigma, rgb, pn, m, TR.l2n(-grad)
+    return sigma, rgb, pn, m
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_extended_field_with_ten_bands_and_both_heads_is_the_field_of_before(dtype):
+    w = {k: v.to(dtype) for k, v in _weights(5).items()}
+    xyz, de = [t.to(dtype) for t in _inputs(257, 2)]
+    for a, b in zip(TR.field(w, xyz.clone(), de, with_normal=True), _field_before(w, xyz.clone(), de, with_normal=True)):
+        assert a.dtype == dtype and torch.equal(a, b)
+    with torch.no_grad():
+        for a, b in zip(TR.field(w, xyz, de, n_bands=10), _field_before(w, xyz, de)):
+            assert torch.equal(a, b)
+
+
+def test_extended_field_absent_heads_are_none_and_leave_the_rest_alone():
+    w = _weights(5)
+    xyz, de = _inputs(64, 3)
+    with torch.no_grad():
+        full = TR.field(w, xyz, de)
+        for drop in (("normal_net.",), ("is_mirror_net.",), ("normal_net.", "is_mirror_net.")):
+            acts = {}
+            got = TR.field({k: v for k, v in w.items() if not k.startswith(drop)}, xyz, de, acts=acts)
+            assert (got[2] is None) == ("normal_net." in drop) and (got[3] is None) == ("is_mirror_net." in drop)
+            assert ("hn" in acts) == ("normal_net." not in drop) and ("hm" in acts) == ("is_mirror_net." not in drop)
+            for a, b in zip(got, full):
+                assert a is None or torch.equal(a, b)
+
+
+def test_extended_field_meets_fixture_g2():
+    """fp32 TR.field on the inputs of fixture G2 (the reference's MirrorNeRF.forward), at the oracle's bar of that fixture."""
+    from tests.golden import fixtures as FX
+    fx = FX.Fixture("g2_field")
+    w = {k: torch.from_numpy(v) for k, v in fx.state_dicts()[0].items()}
+    x30 = torch.from_numpy(fx.inputs["x30"])
+    sigma, rgb, pn, m, nrm = TR.field(w, x30[:, :3].clone(), x30[:, 3:], with_normal=True)
+    got = {"full__sigma": sigma[:, None], "full__rgb": rgb, "full__pred_normal": pn, "full__is_mirror": m[:, None], "full__normal": nrm,
+           "sigma_only__sigma": sigma[:, None], "sigma_only__pred_normal": pn}
+    for k, v in got.items():
+        err = float((v.detach().double() - torch.from_numpy(fx.outputs[k]).double()).abs().max())
+        print(f"MEAS g2_field {k}: {err:.2e}")
+        assert err <= 2e-6, (k, err)
+
+
+_MAP_KEYS = dict(weights="weights", opacity="opacity", rgb="rgb", depth="depth", mask="mirror_mask", sn="surface_normal",
+                 sng="surface_normal_grad", nd="normal_dif", xs="x_surface")
+
+
+def _render_restated(sds, n_xyz, n_dir, rays, z, white, want_grad_normal):
+    """render_rays' two passes at given depths with TR.field and TR.composite, fp32: {fixture key: tensor}."""
+    out = {}
+    for typ, sd in zip(("coarse", "fine"), sds):
+        w = {k: torch.from_numpy(v) for k, v in sd.items()}
+        zz = z[typ]
+        N, S = zz.shape
+        x = FC.ray_positions(rays, zz)
+        de = TR.embed(rays[:, 3:6], n_dir).repeat_interleave(S, 0)
+        res = TR.field(w, x, de, with_normal=want_grad_normal, n_bands=n_xyz)
+        sigma, rgb, pn, m = [None if t is None else t.detach() for t in res[:4]]
+        nrm = res[4].detach().view(N, S, 3) if want_grad_normal else None
+        comp = TR.composite(rays, sigma.view(N, S), zz, None, rgb.view(N, S, 3), None if m is None else m.view(N, S),
+                            None if pn is None else pn.view(N, S, 3), nrm, white)
+        for k, v in comp.items():
+            out[f"{_MAP_KEYS[k]}_{typ}"] = v
+    return out
+
+
+def _meets(name, got, fx, skip=()):
+    from tests.golden import fixtures as FX
+    n = 0
+    for k, want in fx.outputs.items():
+        g = got.get(k[:-7] if k.endswith("_direct") else k)
+        if g is None or k in skip or k in FX.PER_SAMPLE_FINE[:1]:
+            continue
+        err = float((g.double() - torch.from_numpy(want).double()).abs().max())
+        print(f"MEAS {name} {k}: {err:.2e} (bar {FX.tolerance(k, fx.meta):.1e})")
+        assert err <= FX.tolerance(k, fx.meta), (name, k, err)
+        n += 1
+    return n
+
+
+@pytest.mark.parametrize("name", ["g13_mask_head_only_train", "g13_no_normal_head_eval", "g13_normal_head_only_train", "g13_plain_nerf_test",
+                                  "g13_plain_nerf_train"])
+def test_extended_field_meets_the_fixtures_without_optional_heads(name):
+    """G13 (the reference's render_rays / eval on models without normal_net, is_mirror_net or both): TR.field on those state
+    dicts, composited with TR.composite at the fixture's own depths, against every map of the fixture that a plain render
+    forms, at the fixture's bars (tests/golden/fixtures.py tolerance)."""
+    from tests.golden import fixtures as FX
+    from tests.golden import weights as GW
+    fx = FX.Fixture(name)
+    m = fx.meta
+    sds = GW.make_state_dict(m["seed"], 2, predict_normal=m["predict_normal"], predict_mirror_mask=m["predict_mirror_mask"])
+    for sd in sds:
+        GW.apply_tweaks(sd, m["tweaks"])
+    assert ("normal_net.0.weight" in sds[1]) == m["predict_normal"] and ("is_mirror_net.0.weight" in sds[1]) == m["predict_mirror_mask"]
+    rays = torch.from_numpy(fx.inputs["rays"])
+    z = {t: torch.from_numpy(fx.outputs[f"z_vals_{t}"]) for t in ("coarse", "fine")}
+    got = _render_restated(sds, 10, 4, rays, z, m.get("white_back", False), any(k.startswith("surface_normal_grad") for k in fx.outputs))
+    # the eval fixture holds the frame behind the recursion: its colour is blended with the reflected level's, its mirror mask
+    # is the thresholded one (eval.py: 1 where the composited value is not below 0.5; no ray of the fixture within 1e-3 of it)
+    skip = ("rgb_fine",) if name.endswith("_eval") else ()
+    if name.endswith("_eval"):
+        assert float((got["mirror_mask_fine"] - 0.5).abs().min()) > 1e-3
+        got["mirror_mask_fine"] = (got["mirror_mask_fine"] >= 0.5).float()
+    assert _meets(name, got, fx, skip) >= (6 if name.endswith(("_test", "_eval")) else 10)
+
+
+def test_extended_field_meets_the_fixture_with_fewer_bands():
+    """G16 (--N_emb_xyz 6 --N_emb_dir 2 through the reference's NeRFSystem.forward): TR.field(n_bands=6) on the 39 / 15-channel
+    state dicts; the primary level's maps (rgb: the `_direct` keys, in front of the blend with the reflected level)."""
+    from tests.golden import fixtures as FX
+    fx = FX.Fixture("g16_nemb_6_2_train_grads")
+    sds = fx.state_dicts()
+    assert sds[1]["xyz_encoding_5.0.weight"].shape == (256, 256 + 39)
+    rays = torch.from_numpy(fx.inputs["rays"])
+    z = {t: torch.from_numpy(fx.outputs[f"z_vals_{t}"]) for t in ("coarse", "fine")}
+    got = _render_restated(sds, 6, 2, rays, z, False, True)
+    assert _meets("g16", got, fx, skip=("rgb_coarse", "rgb_fine", "loss")) >= 18
+    with torch.no_grad():      # no bands at all: the raw coordinates are the encoding
+        w = FC.weights("bands_0_0", torch.float64)
+        x, d = FC.cloud("init", "box", 16)
+        s = TR.field(w, x.double(), d.double(), n_bands=0)[0]
+        assert s.shape == (16,) and w["xyz_encoding_1.0.weight"].shape == (256, 3)
+
+
+def test_ray_mode_model_shows_a_wrong_ray_index():
+    """The condition of the ray-mode cases of tests/test_hip_forward_fp64.py, on the reference alone: with every ray given its
+    neighbour's direction the float64 rgb of the model those cases use moves by >= 1e-3 (median over samples) at every
+    samples-per-ray count with 7 rays -- a view-encoding row taken from the wrong ray cannot hide below the bars."""
+    for spr in FC.RAY_SPR:
+        shift = FC.neighbour_shift(FC.RAY_MODEL, 7, spr)
+        print(f"MEAS neighbour direction, spr {spr}: median rgb shift {shift:.2e}")
+        assert shift >= 1e-3, (spr, shift)
+
+
+def test_adversarial_sincos_positions_are_exact_and_in_range():
+    x = FC.adversarial_sincos_positions()
+    assert x.shape == (3072, 3) and x.dtype == torch.float32 and float(x.abs().max()) < 64.0

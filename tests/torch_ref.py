@@ -31,9 +31,14 @@ def masks_of(pre):
     return out
 
 
-def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False, keep_mirror=None, masks=None, acts=None):
+def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False, keep_mirror=None, masks=None, acts=None,
+          n_bands=10):
     """w: dict name -> tensor (reference parameter names); returns sigma (B), rgb, pred_normal, is_mirror (B)
     [, normal = l2n(-d sigma/d xyz) built with create_graph=True like utils/func.py:10-25].
+    n_bands: frequency bands of the position encoding (Embedding(n_bands): 10, 6, 0 -> 63, 39, 3 input channels of
+    xyz_encoding_1 / the skip; the view encoding arrives embedded, as wide as dir_encoding.0 expects).  A head whose
+    parameters `w` does not hold (normal_net.*, is_mirror_net.*: predict_normal / predict_mirror_mask off,
+    models/mirror_nerf.py:80-99) is absent: None stands in its place.
     cut_normal / cut_mirror / keep_mirror (B, bool): the heads see geo_feat.detach() (mirror_nerf.py:154-183).
     masks (dict MASK_NAMES -> tensor shaped like the pre-activation, held constant): every activation becomes y * mask, so
     that the function is the piecewise-linear piece a kernel's own ReLU masks select (pre-activations within rounding of 0
@@ -49,7 +54,7 @@ def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False
             return y * masks[name]
         return torch.nn.functional.leaky_relu(y, 0.01) if name == "mir" else torch.relu(y)
 
-    enc = embed(xyz, 10)
+    enc = embed(xyz, n_bands)
     keep["enc"] = enc
     h = enc
     for i in range(8):
@@ -67,12 +72,15 @@ def field(w, xyz, dir_emb, with_normal=False, cut_normal=False, cut_mirror=False
     hM = h.detach() if cut_mirror else h
     if keep_mirror is not None and not cut_mirror:
         hM = torch.where(keep_mirror[:, None], h, h.detach())
-    hn = hN @ w["normal_net.0.weight"].T + w["normal_net.0.bias"]
-    keep["hn"] = hn
-    pn = l2n(hn @ w["normal_net.1.weight"].T + w["normal_net.1.bias"])
-    hm = act("mir", hM @ w["is_mirror_net.0.weight"].T + w["is_mirror_net.0.bias"])
-    keep["hm"] = hm
-    m = torch.sigmoid(hm @ w["is_mirror_net.2.weight"].T + w["is_mirror_net.2.bias"])[:, 0]
+    pn = m = None
+    if "normal_net.0.weight" in w:
+        hn = hN @ w["normal_net.0.weight"].T + w["normal_net.0.bias"]
+        keep["hn"] = hn
+        pn = l2n(hn @ w["normal_net.1.weight"].T + w["normal_net.1.bias"])
+    if "is_mirror_net.0.weight" in w:
+        hm = act("mir", hM @ w["is_mirror_net.0.weight"].T + w["is_mirror_net.0.bias"])
+        keep["hm"] = hm
+        m = torch.sigmoid(hm @ w["is_mirror_net.2.weight"].T + w["is_mirror_net.2.bias"])[:, 0]
     if with_normal:
         (grad,) = torch.autograd.grad(sigma, xyz, torch.ones_like(sigma), create_graph=True, retain_graph=True)
         return sigma, rgb, pn, m, l2n(-grad)
@@ -97,8 +105,14 @@ def composite(rays, sigma, z, noise, rgb, is_mirror, pn, nrm, white_back=False, 
     if keep_mirror is not None and not detach_mask:
         wm = torch.where(keep_mirror[:, None], w, w.detach())
     wn = w.detach() if detach_normal else w
-    out.update(rgb=rgb_map, depth=depth, mask=(wm * is_mirror).sum(1), sn=(wn[..., None] * pn).sum(1))
-    if nrm is not None:
+    out.update(rgb=rgb_map, depth=depth)
+    if is_mirror is not None:      # (a field without the head: the map is not formed)
+        out["mask"] = (wm * is_mirror).sum(1)
+    if pn is not None:
+        out["sn"] = (wn[..., None] * pn).sum(1)
+    if nrm is not None and pn is None:
+        out["sng"] = (wn[..., None] * nrm).sum(1)
+    elif nrm is not None:
         out["sng"] = (wn[..., None] * nrm).sum(1)
         out["nd"] = (wn * ((nrm - pn) ** 2).sum(-1)).sum(1)
     out["xs"] = rays[:, :3] + rays[:, 3:6] * depth[:, None]
