@@ -478,7 +478,9 @@ int mnrf_dw_planes2(int n_eval, const void* const* x_planes, const void* const* 
  * get_optimizer builds that optimizer, train.py:101-109) with one thread per four elements -- torch's fused multi-tensor kernel
  * gives such a tensor ten thread blocks.  `step` = the caller's count of calls (this one included), `*skipped` (device, the
  * caller zeroes it once) = how many of them found_inf has voided: with *found_inf != 0 nothing is updated and *skipped grows by
- * one, as torch's fused Adam does under GradScaler; grad_scale / found_inf may be null. */
+ * one, as torch's fused Adam does under GradScaler; grad_scale / found_inf may be null.  The bias corrections (for step -
+ * *skipped, at least 1) and 1 - beta1, 1 - beta2 are formed in double and rounded to float once; per element the arithmetic is
+ * float, both moments updated as x + (1 - beta)(new - x). */
 int mnrf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1,
                    double beta2, float eps, float weight_decay, int64_t step, int32_t* skipped, const float* grad_scale,
                    const float* found_inf, void* stream);
@@ -594,11 +596,15 @@ int mnrf_dw_planes2_n(int n_eval, const void* const* x_planes, const void* const
                       const int32_t* const* n_live, MNRF_HOST const int* spr, const uint32_t* const* seedmax, MNRF_HOST const int* kinds,
                       float* workspace, float* const* d_params, int accumulate, void* stream);
 /* mnrf_adam_step with every scalar of the step in DEVICE memory (a captured step must not freeze the learning rate or the step
- * count).  mnrf_adam_prep, one thread: *step += 1 (the count of steps, this one included), then state[0..7] = [veto, lr / bias
- * correction 1, sqrt(bias correction 2), beta1, beta2, 1 / grad_scale, eps, weight_decay] from hyper = [lr, beta1, beta2, eps,
- * weight_decay] (doubles; lr, eps and weight_decay are rounded to float as mnrf_adam_step's arguments are) and *skipped (the
- * first model's counter of vetoed steps); veto = *found_inf != 0 or any of the 0..4 range-guard words (HOST array of device words:
- * the last word of a packed image) non-zero.  mnrf_adam_step_dev: the update of one flat tensor from `state`. */
+ * count).  mnrf_adam_prep, one thread: *step += 1 (the count of steps, this one included, vetoed ones too), then
+ * state[0..MNRF_ADAM_STATE_FLOATS) = [veto, lr / bias correction 1, sqrt(bias correction 2), 1 - beta1, 1 - beta2,
+ * 1 / grad_scale, eps, weight_decay] from hyper = [lr, beta1, beta2, eps, weight_decay] (doubles; lr, eps and weight_decay are
+ * rounded to float as mnrf_adam_step's arguments are; the bias corrections and 1 - beta are formed in double and rounded once,
+ * as mnrf_adam_step forms them: the update uses no beta in float) and *skipped (the first model's counter of vetoed steps; the
+ * step the corrections are made for is *step - *skipped, at least 1); veto = *found_inf != 0 or any of the 0..4 range-guard
+ * words (HOST array of device words: the last word of a packed image) non-zero.  mnrf_adam_step_dev: the update of one flat
+ * tensor from `state`, bit for bit mnrf_adam_step's given the same scalars. */
+#define MNRF_ADAM_STATE_FLOATS 8
 int mnrf_adam_prep(const double* hyper, int64_t* step, const int32_t* skipped, const float* grad_scale, const float* found_inf,
                    const uint32_t* const* guard_words, int n_guard_words, float* state, void* stream);
 int mnrf_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* state,

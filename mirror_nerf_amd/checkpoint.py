@@ -151,11 +151,9 @@ def load_training_state(path, system, optimizer=None, trusted=False, restore_rng
             from .weights import invalidate_packed
             invalidate_packed(m)
     if optimizer is not None:
-        optimizer.load_state_dict(ckpt["optimizer_states"][0])
+        optimizer.load_state_dict(ckpt["optimizer_states"][0])      # (training.FlatAdam: its device-resident step count included)
         for g in optimizer.param_groups:
             g["lr"] = float(extra["lr"])
-        if hasattr(optimizer, "_step_dev"):          # training.FlatAdam with device-resident state: the count lives there too
-            optimizer._step_dev.fill_(int(optimizer._calls))
     if restore_rng:
         _set_rng(extra["rng"], next(system.parameters()).device)
     return {"epoch": int(ckpt["epoch"]), "global_step": int(ckpt["global_step"]), "lr": float(extra["lr"]),

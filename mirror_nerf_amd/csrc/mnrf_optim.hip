@@ -2,9 +2,14 @@
 //
 // torch's fused Adam is a multi-tensor kernel that deals 65 536-element chunks to 512-thread blocks: the 595 k parameters of
 // a field model are TEN blocks on a 256-CU device, 46 us per model and step, for 9.5 MB of traffic.  Here: one thread per four
-// elements, float4 accesses, the same arithmetic (torch/optim/adam.py _single_tensor_adam, non-amsgrad, L2 weight decay; the
-// bias corrections in double like torch's fused kernel), the same found_inf / grad_scale contract as GradScaler's
-// (torch/optim/_functional + fused_adam_utils.cuh: a step with found_inf != 0 changes nothing and does not count).
+// elements, float4 accesses, the same update (torch/optim/adam.py _single_tensor_adam, non-amsgrad, L2 weight decay), the same
+// found_inf / grad_scale contract as GradScaler's (torch/optim/_functional + fused_adam_utils.cuh: a step with found_inf != 0
+// changes nothing and does not count).  Its arithmetic: the bias corrections, 1 - beta1 and 1 - beta2 are formed in double from
+// the double betas and rounded to float once (1.f - (float)0.999 is 1.3e-5 off 1 - 0.999); per element everything is float, one
+// rounding per operation, and BOTH moments are updated as x + (1 - beta)(new - x).  The betas themselves are never used in
+// float: (float)beta2 and (float)(1 - beta2) do not sum to one (1.3e-8 over), and exp_avg_sq of beta2 * v + (1 - beta2) g^2
+// with the two rounded apart settles 1.3e-5 above g^2 -- the weights of the form used here sum to one by construction.
+// Held to a float64 restatement by tests/test_hip_adam_fp64.py (tests/adam_ref.py).
 // Reference: train.py:101-109 builds torch.optim.Adam through utils/__init__.py get_optimizer; this is the same update.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,17 +31,18 @@ struct AdamArgs {
     const float* grad_scale;   // device scalars or null
     const float* found_inf;
     // mnrf_adam_step_dev: every scalar of the step comes from a device block written by adam_prep_kernel (a step captured in a hipGraph
-    // must not freeze them): [veto, lr / bias correction 1, sqrt(bias correction 2), beta1, beta2, 1 / grad_scale, eps, weight_decay]
+    // must not freeze them): MNRF_ADAM_STATE_FLOATS floats [veto, lr / bias correction 1, sqrt(bias correction 2), 1 - beta1,
+    // 1 - beta2, 1 / grad_scale, eps, weight_decay]
     const float* state;
 };
 
 __device__ __forceinline__ void adam_body(AdamArgs A) {
     // thread 0 reads the scalars of the step once per block and leaves what the others need in LDS
-    __shared__ float sh[8];
+    __shared__ float sh[MNRF_ADAM_STATE_FLOATS];
     if (threadIdx.x == 0) {
         if (A.state) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) sh[i] = A.state[i];
+            for (int i = 0; i < MNRF_ADAM_STATE_FLOATS; ++i) sh[i] = A.state[i];
         } else {
             const bool veto = A.found_inf && *A.found_inf != 0.f;
             const long long eff = A.step - (long long)*A.skipped;      // >= 1 when the caller counts as documented
@@ -44,8 +50,8 @@ __device__ __forceinline__ void adam_body(AdamArgs A) {
             sh[0] = veto ? 1.f : 0.f;
             sh[1] = A.lr / (float)(1.0 - pow(A.beta1, t));
             sh[2] = (float)sqrt(1.0 - pow(A.beta2, t));
-            sh[3] = (float)A.beta1;
-            sh[4] = (float)A.beta2;
+            sh[3] = (float)(1.0 - A.beta1);      // (in double, rounded once: the weights of the new gradient in the two moments)
+            sh[4] = (float)(1.0 - A.beta2);
             sh[5] = A.grad_scale ? 1.f / *A.grad_scale : 1.f;
             sh[6] = A.eps;
             sh[7] = A.wd;
@@ -58,7 +64,7 @@ __device__ __forceinline__ void adam_body(AdamArgs A) {
     }
     const float step_size = sh[1];
     const float bc2_sqrt = sh[2];
-    const float b1 = sh[3], b2 = sh[4];
+    const float omb1 = sh[3], omb2 = sh[4];
     const float inv_scale = sh[5];
     const bool scaled = sh[5] != 1.f;
     A.eps = sh[6];
@@ -82,8 +88,8 @@ __device__ __forceinline__ void adam_body(AdamArgs A) {
     for (int c = 0; c < 4; ++c) {
         float gr = scaled ? g[c] * inv_scale : g[c];
         if (A.wd != 0.f) gr = gr + A.wd * p[c];
-        m[c] = m[c] + (1.f - b1) * (gr - m[c]);                    // lerp(exp_avg, grad, 1 - beta1)
-        v[c] = b2 * v[c] + (1.f - b2) * gr * gr;                   // exp_avg_sq * beta2 + (1 - beta2) grad^2
+        m[c] = m[c] + omb1 * (gr - m[c]);                          // lerp(exp_avg, grad, 1 - beta1)
+        v[c] = v[c] + omb2 * (gr * gr - v[c]);                     // exp_avg_sq * beta2 + (1 - beta2) grad^2, as a lerp too
         const float denom = sqrtf(v[c]) / bc2_sqrt + A.eps;
         p[c] = p[c] - step_size * (m[c] / denom);
     }
@@ -128,7 +134,8 @@ extern "C" int mnrf_adam_step(float* param, const float* grad, float* exp_avg, f
 }
 
 // ---- the same update with every scalar in device memory (a step captured in a hipGraph must not freeze the learning rate or the
-// step count).  mnrf_adam_prep: one thread -- *step += 1, then the scalars of this step -> state[8]; mnrf_adam_step_dev: the update.
+// step count).  mnrf_adam_prep: one thread -- *step += 1, then the scalars of this step -> state[MNRF_ADAM_STATE_FLOATS];
+// mnrf_adam_step_dev: the update.
 namespace mnrf {
 struct AdamPrepArgs {
     const double* hyper; long long* step; const int* skipped; const float* grad_scale; const float* found_inf;
@@ -146,8 +153,8 @@ __global__ void adam_prep_kernel(AdamPrepArgs P) {
     P.state[0] = veto ? 1.f : 0.f;
     P.state[1] = lr / (float)(1.0 - pow(beta1, t));
     P.state[2] = (float)sqrt(1.0 - pow(beta2, t));
-    P.state[3] = (float)beta1;
-    P.state[4] = (float)beta2;
+    P.state[3] = (float)(1.0 - beta1);
+    P.state[4] = (float)(1.0 - beta2);
     P.state[5] = P.grad_scale ? 1.f / *P.grad_scale : 1.f;
     P.state[6] = eps;
     P.state[7] = wd;

@@ -284,7 +284,8 @@ class FlatAdam:
     """Opt-in optimizer for field models (MirrorNeRF with all 32 parameters at their full shapes): Adam over ONE flat parameter
     tensor per model instead of 32 -- the parameters become views of it, and its gradient IS the flat buffer the backward pass
     already produced (autograd._Pending: the `.grad`s of the parameters are views of one buffer), so nothing is gathered or
-    copied.  The update is torch.optim.Adam's (same arithmetic, same `found_inf` contract: train_step's range guard) from
+    copied.  The update is torch.optim.Adam's (float32 arithmetic held to a float64 restatement by
+    tests/test_hip_adam_fp64.py, same `found_inf` contract: train_step's range guard) from
     `mnrf_adam_step`, one thread per four elements: torch's fused multi-tensor kernel deals 65 536-element chunks to blocks, TEN
     blocks for a model, 46 us per model and step against 6 (round 4).  `kernel=False` keeps torch's
     fused Adam over the flat tensors.  Build it AFTER moving the models to their device (step() raises when a parameter no longer
@@ -397,7 +398,8 @@ class FlatAdam:
         self._hyper_host = None
         self._hyper = torch.zeros(5, dtype=torch.float64, device=dev)
         self._step_dev = torch.tensor([self._calls], dtype=torch.int64, device=dev)
-        self._state_dev = torch.zeros(8, dtype=torch.float32, device=dev)      # the scalars of a step (mnrf_adam_prep)
+        from . import _lib
+        self._state_dev = torch.zeros(_lib.MNRF_ADAM_STATE_FLOATS, dtype=torch.float32, device=dev)   # the scalars of a step (mnrf_adam_prep)
         self.sync_hyper()
 
     def sync_hyper(self):
@@ -464,6 +466,8 @@ class FlatAdam:
             dst.copy_(src)
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             g.update(saved)
+        if hasattr(self, "_step_dev"):       # device-resident state (enable_device_state seeds the count once): it continues from
+            self._step_dev.fill_(self._calls)    # the loaded count too, or the next step_dev() makes the old count's bias corrections
 
 
 class GraphedTrainStep:
