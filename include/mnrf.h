@@ -613,6 +613,53 @@ int mnrf_adam_step_dev(float* param, const float* grad, float* exp_avg, float* e
 int mnrf_adam_step_dev_n(int n_tensors, float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
                          MNRF_HOST const int64_t* n, const float* state, int32_t* const* skipped, void* stream);
 
+/* ---- SGD with momentum and RAdam over one flat fp32 tensor (training.FlatSGD, training.FlatRAdam; utils/__init__.py:47-74
+ * get_optimizer's other two torch optimizers), in mnrf_adam_step's shape and under its contract: one thread per four elements,
+ * 16-byte aligned tensors, `step` = the caller's count of calls (this one included), `*skipped` (device, zeroed once by the
+ * caller) = how many of them were vetoed; with *found_inf != 0 nothing is updated and *skipped grows by one; grad_scale /
+ * found_inf may be null.  Each has a device-state form as Adam has: `*_prep`, one thread: *step += 1 (vetoed steps too), then
+ * the scalars of the step -> state[]; veto = *found_inf != 0 or any of the 0..4 range-guard words (HOST array of device words)
+ * non-zero; `*_step_dev_n`: the update of 0..4 flat tensors from `state` in ONE launch (arrays of n_tensors entries), bit for
+ * bit the host-scalar entry point's given the same scalars.
+ *
+ * SGD is torch.optim.SGD with dampening 0, no Nesterov, L2 weight decay:
+ *     G = g / grad_scale + weight_decay p,   buf' = momentum buf + G,   p' = p - lr buf'
+ * all in float: G with one rounding per operation (g * (1.f / grad_scale) for the quotient, skipped where grad_scale is null or
+ * 1), buf' = fmaf(momentum, buf, G) and p' = fmaf(-lr, buf', p) with one rounding each, as torch's fused SGD computes them; a
+ * zero-initialised buffer makes the first step torch's buf = G.  Nothing depends on the step: `step` is checked (>= 1) only.
+ * mnrf_sgd_prep: hyper = [lr, momentum, weight_decay] (doubles, rounded to float as mnrf_sgd_step's arguments are);
+ * state[0..MNRF_SGD_STATE_FLOATS) = [veto, lr, momentum, 1 / grad_scale, weight_decay]. */
+#define MNRF_SGD_STATE_FLOATS 5
+int mnrf_sgd_step(float* param, const float* grad, float* momentum_buffer, int64_t n, float lr, float momentum, float weight_decay,
+                  int64_t step, int32_t* skipped, const float* grad_scale, const float* found_inf, void* stream);
+int mnrf_sgd_prep(const double* hyper, int64_t* step, const int32_t* skipped, const float* grad_scale, const float* found_inf,
+                  const uint32_t* const* guard_words, int n_guard_words, float* state, void* stream);
+int mnrf_sgd_step_dev_n(int n_tensors, float* const* param, const float* const* grad, float* const* momentum_buffer,
+                        MNRF_HOST const int64_t* n, const float* state, int32_t* const* skipped, void* stream);
+/* RAdam is torch.optim.RAdam with decoupled_weight_decay=False.  For the effective step t = step - *skipped, at least 1:
+ *     G = g / grad_scale + weight_decay p,   m' = m + (1 - beta1)(G - m),   v' = v + (1 - beta2)(G^2 - v)
+ *     rho_inf = 2 / (1 - beta2) - 1,   rho_t = rho_inf - 2 t beta2^t / (1 - beta2^t)
+ *     rho_t > 5:   p' = p - lr / (1 - beta1^t) * sqrt(1 - beta2^t) r_t * m' / (sqrt(v') + eps)
+ *                  r_t = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t))
+ *     otherwise:   p' = p - lr / (1 - beta1^t) * m'
+ * 1 - beta1^t, the product sqrt(1 - beta2^t) r_t, 1 - beta1 and 1 - beta2 are formed in double from the double betas and
+ * rounded to float once; lr (a float) is divided by the rounded 1 - beta1^t in float, as mnrf_adam_step's is; rho_t > 5 is
+ * decided in double where the scalars are formed -- in mnrf_radam_prep from the DEVICE count, so a captured step passes from the
+ * unrectified to the rectified steps by itself.  Per element the arithmetic is float, one rounding per operation, no beta in
+ * float: a = (lr / bc1) * (sqrt(bc2) r_t), p' = p - a * (m' / (sqrtf(v') + eps)), or p' = p - (lr / bc1) * m'.
+ * mnrf_radam_prep: hyper = [lr, beta1, beta2, eps, weight_decay] (mnrf_adam_prep's block); state[0..MNRF_RADAM_STATE_FLOATS) =
+ * [veto, lr / (1 - beta1^t), sqrt(1 - beta2^t) r_t (0 where not rectified), 1 - beta1, 1 - beta2, 1 / grad_scale, eps,
+ * weight_decay, rectified (1 or 0)]. */
+#define MNRF_RADAM_STATE_FLOATS 9
+int mnrf_radam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1,
+                    double beta2, float eps, float weight_decay, int64_t step, int32_t* skipped, const float* grad_scale,
+                    const float* found_inf, void* stream);
+int mnrf_radam_prep(const double* hyper, int64_t* step, const int32_t* skipped, const float* grad_scale, const float* found_inf,
+                    const uint32_t* const* guard_words, int n_guard_words, float* state, void* stream);
+int mnrf_radam_step_dev_n(int n_tensors, float* const* param, const float* const* grad, float* const* exp_avg,
+                          float* const* exp_avg_sq, MNRF_HOST const int64_t* n, const float* state, int32_t* const* skipped,
+                          void* stream);
+
 /* ---- hash-grid field, BASELINE config 5 (models/mirror_nerf_tcnn.py:151-259) ---------------------
  * table: (entries, 2) fp32 hash-grid features; offsets17_host: 17 level offsets in entries (HOST);
  * log2_per_level_scale, base_resolution, bound: the encoding configuration (mirror_nerf_tcnn.py:36-49);

@@ -83,14 +83,15 @@ def _to_cpu(o):
     return o
 
 
-def save_training_state(path, system, optimizer, epoch, global_step, stream=None):
+def save_training_state(path, system, optimizer, epoch, global_step, stream=None, schedule=None):
     """A checkpoint a run can be resumed from (train.py:554-564, 574).  The file is Lightning-shaped: the `state_dict`, `epoch`
     and `global_step` of save_ckpt, so load_ckpt, scripts/eval_scene.py --ckpt_path and the reference's load_ckpt read it as any
     checkpoint, plus
-      optimizer_states  [optimizer.state_dict()] (training.FlatAdam's or torch Adam's), Lightning's key;
+      optimizer_states  [optimizer.state_dict()] (training.FlatAdam's, FlatSGD's, FlatRAdam's or a torch optimizer's), Lightning's key;
       mnrf_training     lr (the first group's current value), grad_scale {field: the gradient-scale reductions of the split
                         backward}, stream (the caller's position in the bank's shuffled stream: seed, step, epoch, stage ...,
-                        plain numbers), rng {cpu, cuda: the generators' states}.
+                        plain numbers), rng {cpu, cuda: the generators' states}, schedule (schedules.LRSchedule.state_dict(): the
+                        options and the epoch of a learning-rate schedule, or None), optimizer (the class name).
     Only tensors and plain containers are written: load_training_state reads it with the tensors-only unpickler."""
     sd = {}
     for name in _FIELDS:
@@ -107,7 +108,7 @@ def save_training_state(path, system, optimizer, epoch, global_step, stream=None
              "grad_scale": {name: int(getattr(system, name).__dict__.get("_mnrf_seed_reduction", 0))
                             for name in _FIELDS if getattr(system, name, None) is not None},
              "stream": {k: (v if isinstance(v, (bool, int, float, str)) or v is None else int(v)) for k, v in dict(stream or {}).items()},
-             "rng": rng}
+             "rng": rng, "schedule": schedule, "optimizer": type(optimizer).__name__}
     torch.save({"state_dict": sd, "epoch": int(epoch), "global_step": int(global_step), "optimizer_states": [_to_cpu(opt)],
                 "lr_schedulers": [], "mnrf_training": extra}, path)
 
@@ -128,12 +129,17 @@ def load_training_state(path, system, optimizer=None, trusted=False, restore_rng
     """Put a save_training_state file back: the fields' parameters (in place: training.FlatAdam's views stay views), the
     optimizer state and learning rate, the gradient-scale state and -- restore_rng -- the generators.  Load BEFORE a
     GraphedTrainStep is built on the optimizer.  Unpickling follows _load_file (tensors and plain containers unless `trusted`).
-    Returns {"epoch", "global_step", "lr", "stream"}."""
+    A state written by another optimizer class than `optimizer`'s is refused (ValueError; files from before the class was recorded
+    are taken as they are).  Returns {"epoch", "global_step", "lr", "stream"}, and "schedule" where the file carries one."""
     ckpt = _load_file(os.fspath(path), trusted)
     if "mnrf_training" not in ckpt:
         raise RuntimeError(f"{path}: a checkpoint without training state (written by save_ckpt or by the reference): it can "
                            "initialise the weights (load_ckpt) but a run cannot be resumed from it")
     extra = ckpt["mnrf_training"]
+    written_by = extra.get("optimizer")
+    if optimizer is not None and written_by is not None and written_by != type(optimizer).__name__:      # (before anything is changed)
+        raise ValueError(f"{path}: the optimizer state was written by {written_by}, not by {type(optimizer).__name__}: a run "
+                         "continues with the optimizer it was started with")
     with torch.no_grad():
         for name in _FIELDS:
             m = getattr(system, name, None)
@@ -156,5 +162,8 @@ def load_training_state(path, system, optimizer=None, trusted=False, restore_rng
             g["lr"] = float(extra["lr"])
     if restore_rng:
         _set_rng(extra["rng"], next(system.parameters()).device)
-    return {"epoch": int(ckpt["epoch"]), "global_step": int(ckpt["global_step"]), "lr": float(extra["lr"]),
-            "stream": dict(extra["stream"])}
+    out = {"epoch": int(ckpt["epoch"]), "global_step": int(ckpt["global_step"]), "lr": float(extra["lr"]),
+           "stream": dict(extra["stream"])}
+    if extra.get("schedule") is not None:
+        out["schedule"] = extra["schedule"]
+    return out

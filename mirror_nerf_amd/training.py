@@ -280,26 +280,32 @@ def train_step(system, optimizer, rays, target, gt_mask, loss_fn=color_mask_loss
     return loss
 
 
-class FlatAdam:
-    """Opt-in optimizer for field models (MirrorNeRF with all 32 parameters at their full shapes): Adam over ONE flat parameter
-    tensor per model instead of 32 -- the parameters become views of it, and its gradient IS the flat buffer the backward pass
-    already produced (autograd._Pending: the `.grad`s of the parameters are views of one buffer), so nothing is gathered or
-    copied.  The update is torch.optim.Adam's (float32 arithmetic held to a float64 restatement by
-    tests/test_hip_adam_fp64.py, same `found_inf` contract: train_step's range guard) from
-    `mnrf_adam_step`, one thread per four elements: torch's fused multi-tensor kernel deals 65 536-element chunks to blocks, TEN
-    blocks for a model, 46 us per model and step against 6 (round 4).  `kernel=False` keeps torch's
-    fused Adam over the flat tensors.  Build it AFTER moving the models to their device (step() raises when a parameter no longer
-    aliases its flat tensor).  Not a torch.optim.Optimizer: lr_scheduler constructors reject it -- schedule by writing
-    `param_groups[0]["lr"]` (read at every step; GraphedTrainStep copies it to the device between replays)."""
+class _FlatOptimizer:
+    """What FlatAdam, FlatSGD and FlatRAdam share: the flat parameter tensor per model, the kernel form's bookkeeping (call and
+    per-module step counts, skip counters, the found_inf / grad_scale hand-over), the device-resident step count and
+    hyper-parameter block of a captured step, the aliasing check and the state dict.  A subclass names its entry points and its
+    per-element state, builds torch's optimizer over the flat tensors (`kernel=False` runs that one; its param_groups are the
+    hyper-parameters of either form) and lists the scalars of a step in the order its entry points take them -- which is also
+    the layout of its device hyper block."""
 
-    def __init__(self, modules, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel=True):
+    NAME = None
+    STATE = ()                 # ((state-dict key, attribute), ...): the per-element state tensors, in the entry points' order
+    ENTRY = ()                 # (host-scalar step, prep, device-state update of up to four tensors, the state block's size)
+
+    def _make_inner(self, **hyper):
+        raise NotImplementedError
+
+    def _scalars(self, grp):
+        raise NotImplementedError
+
+    def _build(self, modules, kernel, **hyper):
         from .weights import param_refs
         self.modules, self.flats = list(modules), []
         for m in self.modules:
             lay, total = D._field_layout(m)
             refs = param_refs(m)
             if lay is None or len(refs) != len(lay) or any(sub._parameters[pn].numel() != lay[full][1] for sub, pn, full in refs):
-                raise ValueError("FlatAdam: needs MirrorNeRF modules with all 32 parameters at their full shapes")
+                raise ValueError(f"{self.NAME}: needs MirrorNeRF modules with all 32 parameters at their full shapes")
             dev = refs[0][0]._parameters[refs[0][1]].device
             flat = torch.empty(total, dtype=torch.float32, device=dev)
             for sub, pn, full in refs:
@@ -309,17 +315,24 @@ class FlatAdam:
                 q.data = flat[o:o + k].view(q.shape)
             self.flats.append(torch.nn.Parameter(flat))
         self.kernel = bool(kernel)
-        self.inner = torch.optim.Adam(self.flats, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fused=True)
+        self.inner = self._make_inner(**hyper)
         self.defaults = dict(self.inner.defaults)
-        self.param_groups = self.inner.param_groups      # (lr / betas / eps / weight_decay are read from here at every step)
+        self.param_groups = self.inner.param_groups      # (the hyper-parameters are read from here at every step)
         if self.kernel:
-            self._m = [torch.zeros_like(fp.data) for fp in self.flats]
-            self._v = [torch.zeros_like(fp.data) for fp in self.flats]
+            for _key, attr in self.STATE:
+                setattr(self, attr, [torch.zeros_like(fp.data) for fp in self.flats])
             self._skipped = [torch.zeros(1, dtype=torch.int32, device=fp.device) for fp in self.flats]
             self._calls = 0
-            self._steps = [0] * len(self.flats)      # per-module step counts, as torch.optim.Adam keeps per-parameter ones: a module
-                                                     # that sat out k steps (no gradient) resumes with ITS count's bias corrections
+            self._steps = [0] * len(self.flats)      # per-module step counts, as torch's optimizers keep per-parameter ones: a module
+                                                     # that sat out k steps (no gradient) resumes with ITS count's scalars
             self._gs = self._fi = None
+
+    def _state_lists(self):
+        return [getattr(self, attr) for _key, attr in self.STATE]
+
+    def _state_tensors(self):
+        """Every tensor a rehearsal step changes besides the parameters and the device count (GraphedTrainStep.capture)."""
+        return [t for lst in self._state_lists() for t in lst] + self._skipped
 
     # train_step hands the guard flag over as GradScaler does
     def _get(self, name):
@@ -353,8 +366,8 @@ class FlatAdam:
             for sub, pn, full in (refs if n_chk % 16 == 1 else (refs[0], refs[-1])):
                 q = sub._parameters[pn]
                 if q.data_ptr() != fp.data_ptr() + 4 * lay[full][0]:
-                    raise RuntimeError(f"FlatAdam: parameter {full} no longer aliases its flat tensor (the module was moved, cast or "
-                                       "re-assigned after the optimizer was built): build FlatAdam again")
+                    raise RuntimeError(f"{self.NAME}: parameter {full} no longer aliases its flat tensor (the module was moved, cast or "
+                                       f"re-assigned after the optimizer was built): build {self.NAME} again")
 
     def step(self):
         self._check_aliasing()
@@ -362,7 +375,7 @@ class FlatAdam:
         grads = []
         for m, fp in zip(self.modules, self.flats):
             if all(q.grad is None for q in params_of(m)):
-                grads.append(None)                   # no backward pass reached this module: torch.optim.Adam skips such parameters
+                grads.append(None)                   # no backward pass reached this module: torch's optimizers skip such parameters
                 fp.grad = None                       # (an update from a zero gradient would still move them by momentum)
                 continue
             flat = D._flat_bucket(m)                 # the backward pass's buffer when every .grad still is a view of it ...
@@ -376,36 +389,35 @@ class FlatAdam:
         from . import _lib
         from .weights import bump_generation
         L, p = _lib.lib(), _lib.ptr
+        entry = getattr(L, self.ENTRY[0])
         self._calls += 1
         f32 = lambda t: None if t is None else t.to(torch.float32).reshape(-1)  # noqa: E731
         gs, fi = f32(self._gs), f32(self._fi)
         for i, (fp, g) in enumerate(zip(self.flats, grads)):
             if g is None:
                 continue
-            grp = self.param_groups[0]
             self._steps[i] += 1
-            _lib.check(L.mnrf_adam_step(p(fp.data), p(g.contiguous()), p(self._m[i]), p(self._v[i]), fp.numel(), float(grp["lr"]),
-                                        float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]),
-                                        self._steps[i], p(self._skipped[i]), p(gs), p(fi), _lib.stream()), "mnrf_adam_step")
+            _lib.check(entry(p(fp.data), p(g.contiguous()), *[p(lst[i]) for lst in self._state_lists()], fp.numel(),
+                             *self._scalars(self.param_groups[0]), self._steps[i], p(self._skipped[i]), p(gs), p(fi), _lib.stream()),
+                       self.ENTRY[0])
         self._gs = self._fi = None                   # (GradScaler semantics: the flags belong to one step)
         bump_generation()                            # the packed weight images are stale now (torch optimizers do this through a hook)
 
     # ---- hyper-parameters and the step count in device memory: what a step captured in a hipGraph needs (GraphedTrainStep)
     def enable_device_state(self):
         if not self.kernel:
-            raise RuntimeError("FlatAdam(kernel=False) has no device-resident state")
+            raise RuntimeError(f"{self.NAME}(kernel=False) has no device-resident state")
         dev = self.flats[0].device
         self._hyper_host = None
-        self._hyper = torch.zeros(5, dtype=torch.float64, device=dev)
+        self._hyper = torch.zeros(len(self._scalars(self.param_groups[0])), dtype=torch.float64, device=dev)
         self._step_dev = torch.tensor([self._calls], dtype=torch.int64, device=dev)
         from . import _lib
-        self._state_dev = torch.zeros(_lib.MNRF_ADAM_STATE_FLOATS, dtype=torch.float32, device=dev)   # the scalars of a step (mnrf_adam_prep)
+        self._state_dev = torch.zeros(getattr(_lib, self.ENTRY[3]), dtype=torch.float32, device=dev)   # the scalars of a step (the prep launch)
         self.sync_hyper()
 
     def sync_hyper(self):
         """param_groups[0] -> device (call between steps: an lr scheduler changes the group's lr on the host)."""
-        grp = self.param_groups[0]
-        h = (float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]))
+        h = self._scalars(self.param_groups[0])
         if h != self._hyper_host:
             self._hyper.copy_(torch.tensor(h, dtype=torch.float64))
             self._hyper_host = h
@@ -420,8 +432,8 @@ class FlatAdam:
         gs, fi = f32(self._gs), f32(self._fi)
         import ctypes
         gw = (ctypes.c_void_p * max(1, len(guard_words)))(*[w.data_ptr() for w in guard_words]) if guard_words else None
-        _lib.check(L.mnrf_adam_prep(self._hyper.data_ptr(), self._step_dev.data_ptr(), p(self._skipped[0]), p(gs), p(fi), gw,
-                                    len(guard_words), p(self._state_dev), _lib.stream()), "mnrf_adam_prep")
+        _lib.check(getattr(L, self.ENTRY[1])(self._hyper.data_ptr(), self._step_dev.data_ptr(), p(self._skipped[0]), p(gs), p(fi), gw,
+                                             len(guard_words), p(self._state_dev), _lib.stream()), self.ENTRY[1])
         from .weights import params_of
         grads, live = [], []
         for i, (m, fp) in enumerate(zip(self.modules, self.flats)):
@@ -437,37 +449,122 @@ class FlatAdam:
             live.append(i)
         for i in live:
             if self._steps[i] != self._calls:
-                raise RuntimeError("FlatAdam.step_dev: the device-resident step count is shared by the modules of a step, but module "
+                raise RuntimeError(f"{self.NAME}.step_dev: the device-resident step count is shared by the modules of a step, but module "
                                    f"{i} has taken {self._steps[i]} of {self._calls} steps (it sat out earlier): use step()")
         self._live_dev = live
-        for i0 in range(0, len(live), 4):  # all models of the step in one launch (mnrf_adam_step_dev_n takes up to four tensors)
+        for i0 in range(0, len(live), 4):  # all models of the step in one launch (the update takes up to four tensors)
             idx = live[i0:i0 + 4]
             vp = lambda ts: (ctypes.c_void_p * len(idx))(*[t.data_ptr() for t in ts])  # noqa: E731
-            _lib.check(L.mnrf_adam_step_dev_n(len(idx), vp([self.flats[i].data for i in idx]), vp([grads[i] for i in idx]),
-                                              vp([self._m[i] for i in idx]), vp([self._v[i] for i in idx]),
-                                              (ctypes.c_int64 * len(idx))(*[self.flats[i].numel() for i in idx]), p(self._state_dev),
-                                              vp([self._skipped[i] for i in idx]), _lib.stream()), "mnrf_adam_step_dev_n")
+            _lib.check(getattr(L, self.ENTRY[2])(len(idx), vp([self.flats[i].data for i in idx]), vp([grads[i] for i in idx]),
+                                                 *[vp([lst[i] for i in idx]) for lst in self._state_lists()],
+                                                 (ctypes.c_int64 * len(idx))(*[self.flats[i].numel() for i in idx]), p(self._state_dev),
+                                                 vp([self._skipped[i] for i in idx]), _lib.stream()), self.ENTRY[2])
         self._gs = self._fi = None
 
     def state_dict(self):
         if not self.kernel:
             return self.inner.state_dict()
-        return {"kernel": True, "calls": self._calls, "steps": list(self._steps),
-                "exp_avg": [t.clone() for t in self._m], "exp_avg_sq": [t.clone() for t in self._v],
-                "skipped": [t.clone() for t in self._skipped], "param_groups": [{k: v for k, v in g.items() if k != "params"}
-                                                                                for g in self.param_groups]}
+        sd = {"kernel": True, "calls": self._calls, "steps": list(self._steps)}
+        for (key, _attr), lst in zip(self.STATE, self._state_lists()):
+            sd[key] = [t.clone() for t in lst]
+        sd["skipped"] = [t.clone() for t in self._skipped]
+        sd["param_groups"] = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+        return sd
 
     def load_state_dict(self, sd):
         if not self.kernel:
             return self.inner.load_state_dict(sd)
+        missing = [key for key, _attr in self.STATE if key not in sd]
+        if missing or not sd.get("kernel"):
+            raise ValueError(f"{self.NAME}.load_state_dict: not a kernel-form {self.NAME} state (it lacks {missing or ['kernel']}): "
+                             "the state of another optimizer cannot continue this one")
         self._calls = int(sd["calls"])
         self._steps = [int(v) for v in sd.get("steps", [self._calls] * len(self.flats))]
-        for dst, src in zip(self._m + self._v + self._skipped, sd["exp_avg"] + sd["exp_avg_sq"] + sd["skipped"]):
+        for dst, src in zip(self._state_tensors(), [t for key, _attr in self.STATE for t in sd[key]] + list(sd["skipped"])):
             dst.copy_(src)
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             g.update(saved)
         if hasattr(self, "_step_dev"):       # device-resident state (enable_device_state seeds the count once): it continues from
-            self._step_dev.fill_(self._calls)    # the loaded count too, or the next step_dev() makes the old count's bias corrections
+            self._step_dev.fill_(self._calls)    # the loaded count too, or the next step_dev() makes the old count's scalars
+
+
+class FlatAdam(_FlatOptimizer):
+    """Opt-in optimizer for field models (MirrorNeRF with all 32 parameters at their full shapes): Adam over ONE flat parameter
+    tensor per model instead of 32 -- the parameters become views of it, and its gradient IS the flat buffer the backward pass
+    already produced (autograd._Pending: the `.grad`s of the parameters are views of one buffer), so nothing is gathered or
+    copied.  The update is torch.optim.Adam's (float32 arithmetic held to a float64 restatement by
+    tests/test_hip_adam_fp64.py, same `found_inf` contract: train_step's range guard) from
+    `mnrf_adam_step`, one thread per four elements: torch's fused multi-tensor kernel deals 65 536-element chunks to blocks, TEN
+    blocks for a model, 46 us per model and step against 6 (round 4).  `kernel=False` keeps torch's
+    fused Adam over the flat tensors.  Build it AFTER moving the models to their device (step() raises when a parameter no longer
+    aliases its flat tensor).  Not a torch.optim.Optimizer: lr_scheduler constructors reject it -- schedule by writing
+    `param_groups[0]["lr"]` (read at every step; GraphedTrainStep copies it to the device between replays)."""
+
+    NAME = "FlatAdam"
+    STATE = (("exp_avg", "_m"), ("exp_avg_sq", "_v"))
+    ENTRY = ("mnrf_adam_step", "mnrf_adam_prep", "mnrf_adam_step_dev_n", "MNRF_ADAM_STATE_FLOATS")
+
+    def __init__(self, modules, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel=True):
+        self._build(modules, kernel, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _make_inner(self, **hyper):
+        return torch.optim.Adam(self.flats, fused=True, **hyper)
+
+    def _scalars(self, grp):
+        return (float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]))
+
+
+class FlatSGD(_FlatOptimizer):
+    """torch.optim.SGD (momentum, dampening 0, no Nesterov, L2 weight decay: what the reference's `--optimizer sgd` builds,
+    utils/__init__.py:52-58) over FlatAdam's flat tensors, from `mnrf_sgd_step`: buf' = momentum buf + G, p' = p - lr buf', the
+    buffer zero at the start (the first step is then torch's buf = G).  Same surface as FlatAdam, the device-resident form for
+    GraphedTrainStep included (held to float64 by tests/test_hip_optim_fp64.py).  `kernel=False` is torch's fused SGD over the
+    flat tensors."""
+
+    NAME = "FlatSGD"
+    STATE = (("momentum_buffer", "_buf"),)
+    ENTRY = ("mnrf_sgd_step", "mnrf_sgd_prep", "mnrf_sgd_step_dev_n", "MNRF_SGD_STATE_FLOATS")
+
+    def __init__(self, modules, lr=5e-4, momentum=0.9, weight_decay=0.0, kernel=True):
+        self._build(modules, kernel, lr=lr, momentum=momentum, weight_decay=weight_decay)
+
+    def _make_inner(self, **hyper):
+        return torch.optim.SGD(self.flats, fused=True, **hyper)
+
+    def _scalars(self, grp):
+        if grp.get("dampening") or grp.get("nesterov") or grp.get("maximize"):
+            raise ValueError("FlatSGD: dampening 0, no Nesterov momentum, no maximize (mnrf_sgd_step has none of them)")
+        return (float(grp["lr"]), float(grp["momentum"]), float(grp["weight_decay"]))
+
+
+class FlatRAdam(_FlatOptimizer):
+    """torch.optim.RAdam (decoupled_weight_decay=False; the reference's `--optimizer radam` is torch_optimizer's class of the same
+    paper, utils/__init__.py:63-66) over FlatAdam's flat tensors, from `mnrf_radam_step`: Adam's two moments, no second-moment
+    term while rho_t <= 5 (the first five steps with beta2 = 0.999), the rectified step afterwards.  torch has no fused RAdam,
+    only `foreach`, a dozen launches per tensor; `kernel=False` is that one over the flat tensors (it takes no found_inf:
+    train_step then checks the range guard on the host).  In the device-resident form the branch is taken from the device count in
+    the prep launch, so a captured step crosses the threshold without being captured again."""
+
+    NAME = "FlatRAdam"
+    STATE = (("exp_avg", "_m"), ("exp_avg_sq", "_v"))
+    ENTRY = ("mnrf_radam_step", "mnrf_radam_prep", "mnrf_radam_step_dev_n", "MNRF_RADAM_STATE_FLOATS")
+
+    def __init__(self, modules, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel=True):
+        self._build(modules, kernel, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+        if self.kernel:
+            self.mnrf_found_inf = True               # (train_step: the kernel form takes the guard flag; torch's foreach RAdam does not)
+
+    def _make_inner(self, **hyper):
+        return torch.optim.RAdam(self.flats, foreach=True, **hyper)
+
+    def _scalars(self, grp):
+        if grp.get("decoupled_weight_decay") or grp.get("maximize"):
+            raise ValueError("FlatRAdam: L2 weight decay, no maximize (mnrf_radam_step has neither decoupled decay nor maximize)")
+        return (float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]))
+
+
+FLAT_OPTIMIZERS = {"adam": FlatAdam, "sgd": FlatSGD, "radam": FlatRAdam}
 
 
 class GraphedTrainStep:
@@ -501,8 +598,8 @@ class GraphedTrainStep:
     _BITS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048)
 
     def __init__(self, system, optimizer, batch, loss_fn=None, epoch=0, gt_valid=True, warmup=2):
-        if not isinstance(optimizer, FlatAdam) or not optimizer.kernel:
-            raise ValueError("GraphedTrainStep needs training.FlatAdam (its kernel form)")
+        if not isinstance(optimizer, _FlatOptimizer) or not optimizer.kernel:
+            raise ValueError("GraphedTrainStep needs training.FlatAdam, training.FlatSGD or training.FlatRAdam (the kernel form)")
         if not static_step_ok(system):
             raise RuntimeError("GraphedTrainStep: MirrorNeRF fields on the split arithmetic with operand planes only")
         self.system, self.opt, self.loss_fn, self.epoch, self.gt_valid = system, optimizer, loss_fn or color_mask_loss, epoch, bool(gt_valid)
@@ -572,7 +669,7 @@ class GraphedTrainStep:
     def capture(self):
         opt = self.opt
         self._check_stage()
-        keep = [t.clone() for t in opt.flats] + [t.clone() for t in opt._m + opt._v + opt._skipped] + [opt._step_dev.clone()]
+        keep = [t.clone() for t in opt.flats] + [t.clone() for t in opt._state_tensors()] + [opt._step_dev.clone()]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):     # warm-up off the capture: lazy initialisations, allocator, autograd threads
@@ -580,7 +677,7 @@ class GraphedTrainStep:
                 self._body()
         torch.cuda.current_stream().wait_stream(side)
         with torch.no_grad():             # the warm-up steps were rehearsals: weights and optimizer state as before
-            for dst, src in zip([t.data for t in opt.flats] + opt._m + opt._v + opt._skipped + [opt._step_dev], keep):
+            for dst, src in zip([t.data for t in opt.flats] + opt._state_tensors() + [opt._step_dev], keep):
                 dst.copy_(src)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()

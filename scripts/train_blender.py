@@ -22,6 +22,18 @@ The validation half of the reference's loop (train.py:460-564, 574) is opt-in; w
                    the best val/psnr
   --resume PATH    continue such a checkpoint: weights, optimizer, learning rate, gradient-scale state, the position in the
                    shuffled stream and the generators; --steps stays the TOTAL, so K steps + a resumed run to 2K is a 2K run
+
+The reference's optimizers and learning-rate schedules (opt.py:106-153, utils/__init__.py:47-101) are opt-in as well; without
+these options the run keeps Adam and its own decay, lr *= 0.1 ** (1 / steps) after every step:
+  --optimizer sgd|adam|radam   with --momentum and --weight_decay; on the graph route training.FlatSGD / FlatAdam / FlatRAdam
+                   (the HIP kernels), on the other routes torch's optimizer.  `ranger` is refused (torch_optimizer's
+                   Lookahead-RAdam is not part of this package)
+  --lr_scheduler steplr|cosine|poly   with --decay_step, --decay_gamma, --poly_exp, --warmup_epochs, --warmup_multiplier and
+                   --num_epochs (mirror_nerf_amd/schedules.py): the rate is set at every epoch boundary of the stream, as
+                   Lightning steps an epoch-interval scheduler, and is constant within an epoch.  run.sh:259-280's recipe is
+                   --optimizer adam --lr_scheduler steplr --decay_step 2 4 8 --decay_gamma 0.5 --num_epochs 30
+  --num_epochs N   the run ends with epoch N - 1 (or with --steps, whichever comes first)
+The schedule's options and position travel in the checkpoint; --resume refuses another schedule or optimizer.
 """
 import argparse
 import json
@@ -86,9 +98,34 @@ def main(argv=None):
     ap.add_argument("--resume", default=None, help="a checkpoint of --ckpt_dir to continue (train.py:574)")
     ap.add_argument("--trusted", action="store_true", help="--resume: unpickle the checkpoint fully (only for files you wrote)")
     ap.add_argument("--log_dir", default=None, help="val.jsonl and the validation panels")
+    ap.add_argument("--optimizer", choices=("sgd", "adam", "radam", "ranger"), default="adam")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd")
+    ap.add_argument("--weight_decay", type=float, default=0.0)
+    ap.add_argument("--lr_scheduler", choices=("steplr", "cosine", "poly"), default=None,
+                    help="the reference's epoch schedules (default: none of them, lr *= 0.1 ** (1 / steps) after every step)")
+    ap.add_argument("--decay_step", type=int, nargs="+", default=[20], help="steplr: the epochs at which the rate drops")
+    ap.add_argument("--decay_gamma", type=float, default=0.1, help="steplr: by this factor")
+    ap.add_argument("--poly_exp", type=float, default=0.9)
+    ap.add_argument("--warmup_epochs", type=int, default=0, help="linear warm-up over this many epochs (sgd and adam only)")
+    ap.add_argument("--warmup_multiplier", type=float, default=1.0, help="the rate reaches lr times this at the end of the warm-up")
+    ap.add_argument("--num_epochs", type=int, default=None, help="end the run with epoch N - 1; T_max of cosine, the end of poly (default there: 16)")
     a = ap.parse_args(argv)
     if a.val_every < 0:
         raise SystemExit("--val_every must not be negative")
+    if a.optimizer == "ranger":
+        raise SystemExit("--optimizer ranger: torch_optimizer's Ranger (Lookahead around RAdam) is not part of this package and there is "
+                         "no implementation here to hold one against; use sgd, adam or radam")
+    if a.num_epochs is not None and a.num_epochs < 1:
+        raise SystemExit("--num_epochs must be at least 1")
+    sched = None
+    if a.lr_scheduler is not None:
+        from mirror_nerf_amd.schedules import lr_schedule
+        try:
+            sched = lr_schedule(SimpleNamespace(lr=a.lr, lr_scheduler=a.lr_scheduler, decay_step=a.decay_step, decay_gamma=a.decay_gamma,
+                                                num_epochs=16 if a.num_epochs is None else a.num_epochs, poly_exp=a.poly_exp,
+                                                warmup_epochs=a.warmup_epochs, warmup_multiplier=a.warmup_multiplier, optimizer=a.optimizer))
+        except ValueError as e:
+            raise SystemExit(str(e))
     dev = torch.device("cuda", 0)
     M.set_precision(a.precision)
     torch.manual_seed(a.seed)
@@ -107,9 +144,18 @@ def main(argv=None):
     rank, world = dist.world()
     gamma = 0.1 ** (1.0 / max(1, a.steps))
     if a.route == "graph":
-        opt = training.FlatAdam(list(system.models.values()), lr=a.lr)
+        if a.optimizer == "adam":
+            opt = training.FlatAdam(list(system.models.values()), lr=a.lr, weight_decay=a.weight_decay)
+        elif a.optimizer == "sgd":
+            opt = training.FlatSGD(list(system.models.values()), lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay)
+        else:
+            opt = training.FlatRAdam(list(system.models.values()), lr=a.lr, weight_decay=a.weight_decay)
+    elif a.optimizer == "adam":
+        opt = torch.optim.Adam(list(system.parameters()), lr=a.lr, weight_decay=a.weight_decay, fused=True)
+    elif a.optimizer == "sgd":
+        opt = torch.optim.SGD(list(system.parameters()), lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, fused=True)
     else:
-        opt = torch.optim.Adam(list(system.parameters()), lr=a.lr, fused=True)
+        opt = torch.optim.RAdam(list(system.parameters()), lr=a.lr, eps=1e-8, weight_decay=a.weight_decay)
 
     def setup(epoch):
         """The bank, the loss and the validity statement of an epoch (the stage's frames all have a valid mask)."""
@@ -149,8 +195,9 @@ def main(argv=None):
     def save_epoch(ep, steps_done, final=False):
         """train.py:554-564: the epoch's checkpoint and last.ckpt; the best val/psnr so far is recorded beside them."""
         stream = dict(seed=a.seed, step=steps_done, epoch=epoch, first=first, epoch_first=epoch_first, batch=a.batch,
-                      stage=bool(system.train_geometry_stage), total_steps=a.steps)
-        checkpoint.save_training_state(os.path.join(a.ckpt_dir, "last.ckpt"), system, opt, ep, steps_done, stream=stream)
+                      stage=bool(system.train_geometry_stage), total_steps=a.steps, optimizer=a.optimizer)
+        checkpoint.save_training_state(os.path.join(a.ckpt_dir, "last.ckpt"), system, opt, ep, steps_done, stream=stream,
+                                       schedule=None if sched is None else sched.state_dict())
         if not final:
             import shutil
             shutil.copyfile(os.path.join(a.ckpt_dir, "last.ckpt"), os.path.join(a.ckpt_dir, f"epoch={ep}.ckpt"))
@@ -165,8 +212,19 @@ def main(argv=None):
     resumed = None
     if a.resume:
         # (the generators are put back below, behind the capture of the graph route: its rehearsal steps draw)
-        resumed = checkpoint.load_training_state(a.resume, system, opt, trusted=a.trusted, restore_rng=False)
+        try:
+            resumed = checkpoint.load_training_state(a.resume, system, opt, trusted=a.trusted, restore_rng=False)
+        except ValueError as e:
+            raise SystemExit(f"--resume: {e}")
         st = resumed["stream"]
+        if (resumed.get("schedule") is None) != (sched is None):
+            raise SystemExit("--resume: the checkpoint was written " + ("without" if sched is not None else "with") + " --lr_scheduler; "
+                             "continue it with the schedule it was written with")
+        if sched is not None:
+            try:
+                sched.load_state_dict(resumed["schedule"])
+            except ValueError as e:
+                raise SystemExit(f"--resume: {e}")
         if (st["seed"], st["batch"], st["total_steps"]) != (a.seed, a.batch, a.steps):
             raise SystemExit(f"--resume: the checkpoint was written with --seed {st['seed']} --batch {st['batch']} --steps {st['total_steps']}; "
                              "continue it with the same (the stream and the learning-rate schedule depend on them)")
@@ -176,6 +234,10 @@ def main(argv=None):
                 best.update(json.load(f))
         print(f"resumed {a.resume}: step {start}, epoch {epoch}, lr {resumed['lr']:.3e}", flush=True)
     bank, loss_fn, gt_valid = setup(epoch)
+    lr_by_epoch = {}
+    if sched is not None:
+        lr_by_epoch[epoch] = sched.apply(opt, epoch)
+        print(f"epoch {epoch}  lr {lr_by_epoch[epoch]:.6e}", flush=True)
     graphed = training.GraphedTrainStep(system, opt, a.batch, loss_fn, epoch=epoch, gt_valid=gt_valid) if a.route == "graph" else None
     if resumed is not None:
         if graphed is not None:
@@ -187,8 +249,11 @@ def main(argv=None):
         out = (torch.empty(a.batch, 8, device=dev), torch.empty(a.batch, 3, device=dev), torch.empty(a.batch, device=dev))
     t0 = time.time()
     loss = None
+    done = start
     for it in range(start, a.steps):
         e = epoch_first + bank.epoch_of(it - first, a.batch, world)
+        if a.num_epochs is not None and e >= a.num_epochs:
+            break
         if e != epoch:
             if a.ckpt_dir and rank == 0:
                 save_epoch(epoch, it)
@@ -201,12 +266,17 @@ def main(argv=None):
                 out = (graphed.rays, graphed.target, graphed.gt)
             elif graphed is not None:
                 graphed.set_epoch(epoch, loss_fn)
+            if sched is not None:
+                lr_by_epoch[epoch] = sched.apply(opt, epoch)
+                print(f"epoch {epoch}  lr {lr_by_epoch[epoch]:.6e}", flush=True)
         rays, rgbs, mask = bank.draw(it - first, a.batch, a.seed, rank, world, out=out)
         if graphed is not None:
             loss = graphed(rays, rgbs, mask)          # the step's own buffers: its copy_ of a tensor onto itself is a no-op
         else:
             loss = training.train_step(system, opt, rays, rgbs, mask, loss_fn, epoch=epoch, gt_valid=gt_valid if a.route == "static" else None)
-        opt.param_groups[0]["lr"] *= gamma
+        done = it + 1
+        if sched is None:
+            opt.param_groups[0]["lr"] *= gamma
         if val_bank is not None:
             # val_check_interval (train.py:585): every int(batches per epoch * fraction) batches of the epoch
             per_epoch = max(1, bank.n_rays // (a.batch * world))
@@ -216,7 +286,7 @@ def main(argv=None):
         if it % 1000 == 0 or it == a.steps - 1:
             print(f"step {it:6d}  epoch {epoch}  loss {loss.item():.4f}  [{time.time() - t0:.0f} s]", flush=True)
     if a.ckpt_dir and rank == 0:
-        save_epoch(epoch, a.steps, final=True)
+        save_epoch(epoch, done if a.num_epochs is not None else a.steps, final=True)
     arrs = {}
     for mname, mod in (("coarse", system.nerf_coarse), ("fine", system.nerf_fine)):
         for k, v in mod.state_dict().items():
@@ -224,7 +294,11 @@ def main(argv=None):
     arrs["meta"] = np.array(json.dumps(dict(steps=a.steps, batch=a.batch, lr=a.lr, root_dir=os.path.abspath(a.root_dir), img_wh=list(a.img_wh),
                                             frames=full.n_frames, route=a.route, loss=a.loss, seed=a.seed, epochs=epoch + 1,
                                             final_loss=None if loss is None else float(loss.item()),
-                                            trained_with="mirror_nerf_amd (scripts/train_blender.py), precision " + a.precision)))
+                                            trained_with="mirror_nerf_amd (scripts/train_blender.py), precision " + a.precision,
+                                            **({} if a.optimizer == "adam" else {"optimizer": a.optimizer}),
+                                            **({} if a.num_epochs is None else {"steps_run": done}),
+                                            **({} if sched is None else {"lr_scheduler": sched.state_dict()["options"],
+                                                                         "lr_by_epoch": {str(k): v for k, v in lr_by_epoch.items()}}))))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez_compressed(a.out, **arrs)
     print("wrote", a.out, f"{os.path.getsize(a.out) / 1e6:.1f} MB; ms/step {(time.time() - t0) / max(1, a.steps) * 1e3:.2f}")
