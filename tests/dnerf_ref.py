@@ -35,8 +35,8 @@ def embed(x, n_freqs):
 
 
 def _lin(sd, name, h):
-    w = torch.as_tensor(sd[name + ".weight"]).to(h.dtype)
-    b = torch.as_tensor(sd[name + ".bias"]).to(h.dtype)
+    w = torch.as_tensor(sd[name + ".weight"]).to(device=h.device, dtype=h.dtype)
+    b = torch.as_tensor(sd[name + ".bias"]).to(device=h.device, dtype=h.dtype)
     return h @ w.T + b
 
 
@@ -50,21 +50,30 @@ def _trunk(sd, prefix, first, enc):
     return h
 
 
-def field(sd, xyz, viewdirs, t, zero_canonical=True):
-    """-> (cat[rgb raw, alpha raw] (B,4), dx (B,3)) at time t (a float) for positions (B,3) and unit directions (B,3)."""
-    dt = xyz.dtype
+def deformation(sd, xyz, t):
+    """The deformation net: -> dx (B,3) of the positions (B,3) at time t (a float, rounded to float32 as the caller's is)."""
     enc = embed(xyz, 10)
-    if float(t) == 0.0 and zero_canonical:
-        dx = torch.zeros_like(xyz)
-    else:
-        te = embed(torch.full((xyz.shape[0], 1), float(t), dtype=torch.float32).to(dt), 10)
-        dx = _lin(sd, "_time_out", _trunk(sd, "_time", torch.cat([enc, te], -1), enc))
-        enc = embed(xyz + dx, 10)
+    te = embed(torch.full((xyz.shape[0], 1), float(t), dtype=torch.float32, device=xyz.device).to(xyz.dtype), 10)
+    return _lin(sd, "_time_out", _trunk(sd, "_time", torch.cat([enc, te], -1), enc))
+
+
+def canonical(sd, pts, viewdirs):
+    """The canonical NeRF: -> cat[rgb raw, alpha raw] (B,4) at the (moved) points (B,3) for unit directions (B,3)."""
+    enc = embed(pts, 10)
     h = _trunk(sd, "_occ.pts_linears", enc, enc)
     alpha = _lin(sd, "_occ.alpha_linear", h)
     feat = _lin(sd, "_occ.feature_linear", h)
     hv = torch.relu(_lin(sd, "_occ.views_linears.0", torch.cat([feat, embed(viewdirs, 4)], -1)))
-    return torch.cat([_lin(sd, "_occ.rgb_linear", hv), alpha], -1), dx
+    return torch.cat([_lin(sd, "_occ.rgb_linear", hv), alpha], -1)
+
+
+def field(sd, xyz, viewdirs, t, zero_canonical=True):
+    """-> (cat[rgb raw, alpha raw] (B,4), dx (B,3)) at time t (a float) for positions (B,3) and unit directions (B,3): the
+    canonical net at x + dx, one add in the inputs' dtype; at t = 0 with zero_canonical the deformation net is not asked."""
+    if float(t) == 0.0 and zero_canonical:
+        return canonical(sd, xyz, viewdirs), torch.zeros_like(xyz)
+    dx = deformation(sd, xyz, t)
+    return canonical(sd, xyz + dx, viewdirs), dx
 
 
 def composite(raw, z, rays_d, white_bkgd):

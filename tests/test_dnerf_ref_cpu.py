@@ -95,6 +95,38 @@ def test_restatement_matches_the_reference_module(tag):
         assert fx.meta["floor"][f"{key}_{tag}"] == pytest.approx(float(np.abs(a.astype(np.float64) - b).max()) / scale, rel=1e-12, abs=1e-300)
 
 
+@pytest.mark.parametrize("tag", ["t037", "t0"])
+def test_field_is_the_composition_of_its_two_networks(tag):
+    """field() = canonical() at x + deformation(): the two halves that the GPU tests hold the kernel's two stages to, composed by
+    hand, give the bits field() gives and with them the committed G27 values on the bars of the test above."""
+    fx = FX.Fixture("g27_dnerf_model")
+    sd = DR.make_state_dicts(fx.meta["seed"], 1)[0]
+    W.apply_tweaks(sd, fx.meta["tweaks"])
+    t = fx.meta["times"][tag]
+    xyz, view = torch.from_numpy(fx.inputs["xyz"]).double(), torch.from_numpy(fx.inputs["viewdirs"]).double()
+    dx = DR.deformation(sd, xyz, t)
+    assert dx.shape == xyz.shape and dx.dtype == torch.float64
+    if t == 0.0:
+        # the canonical frame: the deformation net is not asked, though it would answer
+        raw, want_dx = DR.canonical(sd, xyz, view), torch.zeros_like(xyz)
+        assert float(dx.abs().max()) > 0.01
+        moved, moved_dx = DR.field(sd, xyz, view, t, zero_canonical=False)
+        assert torch.equal(moved_dx, dx) and torch.equal(moved, DR.canonical(sd, xyz + dx, view))
+    else:
+        raw, want_dx = DR.canonical(sd, xyz + dx, view), dx
+    got_raw, got_dx = DR.field(sd, xyz, view, t)
+    assert torch.equal(got_raw, raw) and torch.equal(got_dx, want_dx)
+    want_raw = fx.outputs[f"raw64_{tag}"]
+    assert np.abs(raw.numpy() - want_raw).max() <= 1e-10 * max(1.0, np.abs(want_raw).max())
+    assert np.abs(want_dx.numpy() - fx.outputs[f"dx64_{tag}"]).max() <= 1e-12
+    # float32 in, float32 out: the restatement's own fp32 run is what the kernel's bars are taken from
+    raw32, dx32 = DR.field(sd, xyz.float(), view.float(), t)
+    assert raw32.dtype == torch.float32 and dx32.dtype == torch.float32
+    floor = fx.meta["floor"]
+    scale = max(1.0, float(np.abs(want_raw[:, 3]).max()))
+    assert np.abs(raw32.numpy()[:, 3] - want_raw[:, 3]).max() <= 4.0 * floor[f"alpha_{tag}"] * scale
+
+
 def object_state_dicts(meta):
     sds = DR.make_state_dicts(meta["obj_seed"], len(meta["obj_tweaks"]))
     for sd, tw, c in zip(sds, meta["obj_tweaks"], meta["obj_checksum"]):
