@@ -270,6 +270,42 @@ int mnrf_object_merge_indexed(const float* obj_rgb, const float* obj_depth, cons
                               const int32_t* count, int64_t capacity, float scale, float pose_scale0, float near, float* rgb,
                               float* depth, float* mask, int32_t* n_used, void* stream);
 
+/* ---- Several placed objects at one level: culled in one pass, merged in one pass.  csrc/mnrf_objects.hip.
+ *
+ * THE RULE, per ray of the level: for k = 0 .. n_objects-1 in list order, the single-object rule of mnrf_object_merge for
+ * object k is applied to the ray's CURRENT (rgb, depth, mask) -- current: as left by the scene and by the objects 0 .. k-1.
+ * That is, by definition, the chain of n_objects single-object applications.  The rule writes depth = d, so the nearest
+ * opaque object wins; an exact tie in depth goes to the LATER object of the list (`d > depth` is false); and a current depth
+ * `<= near` hides nothing (eval.py:275-281), whichever object or scene left it. */
+#define MNRF_OBJECTS_MAX 8
+
+/* mnrf_object_cull for n_objects (1..MNRF_OBJECTS_MAX) objects on the same rays (n_rays,8), in two launches in all.  Per
+ * object, HOST arrays of n_objects rows: posed (0 / 1) and poses (12 floats a row, read where posed), scales, translations
+ * (3 a row): the ray move, as mnrf_object_rays; unbounded (0 / 1): 1 = the object has no bounds, every ray is kept and its
+ * row is what mnrf_object_rays writes (box_lo, box_hi, res, bits of that object are not read); box_lo, box_hi (3 a row),
+ * res (Rx, Ry, Rz a row), bits (a HOST array of n_objects DEVICE pointers, null = the whole box is one set cell): the bounds,
+ * as mnrf_object_cull.  Outputs, per object exactly what mnrf_object_cull writes (the same device functions decide):
+ * out_rays (n_objects,n_rays,8), index (n_objects,n_rays) int32 -- the kept rays of object k compacted in source order in
+ * rows 0 .. counts[k]-1 of plane k, rows from counts[k] on not defined -- counts (n_objects) int32, and slot
+ * (n_objects,n_rays) int32: slot[k][r] = the row of ray r in object k's list, or -1.  No atomic decides an order.  rays and
+ * out_rays are aligned to 16 bytes and distinct. */
+int mnrf_objects_cull(const float* rays, int64_t n_rays, int n_objects, MNRF_HOST const int* posed, MNRF_HOST const float* poses,
+                      MNRF_HOST const float* scales, MNRF_HOST const float* translations, MNRF_HOST const int* unbounded,
+                      MNRF_HOST const float* box_lo, MNRF_HOST const float* box_hi, MNRF_HOST const int* res,
+                      const uint32_t* const* bits, float* out_rays, int32_t* index, int32_t* slot, int32_t* counts, void* stream);
+
+/* THE RULE above on the n_rays rays of a level, in one launch.  obj_rgb, obj_depth, obj_opacity: HOST arrays of n_objects
+ * DEVICE pointers, the maps of object k rendered on the rows of its out_rays plane (a null entry, in all three: the object
+ * was not rendered and is skipped); slot, counts: of mnrf_objects_cull; row s = slot[k][r] of object k's maps is merged
+ * into ray r where 0 <= s < min(counts[k], capacity) (counts is read on the device; a given map of object k holds at
+ * least that many rows).  scales, pose_scale0: HOST arrays of n_objects floats; near; rgb, depth, mask: as mnrf_object_merge.
+ * n_used (n_objects int32, device, caller zeroes it, null = skip): element k receives the number of rays that took object k
+ * when its turn came -- a ray that a later, nearer object takes afterwards counts for both. */
+int mnrf_objects_merge(const float* const* obj_rgb, const float* const* obj_depth, const float* const* obj_opacity, int n_objects,
+                       const int32_t* slot, const int32_t* counts, int64_t n_rays, int64_t capacity, MNRF_HOST const float* scales,
+                       MNRF_HOST const float* pose_scale0, float near, float* rgb, float* depth, float* mask, int32_t* n_used,
+                       void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

@@ -4,8 +4,8 @@
 // whose object-frame segment meets a set cell; mnrf_object_merge_indexed merges the object's maps of those rays back into
 // the level's rows.  All three are memory-bound passes (about 32 B per ray in, at most 36 B out).
 //
-// The cull decision is evaluated in float64 on the fp32 object-frame ray that mnrf_object_rays writes (mnrf_object.h
-// move_ray, the same device function): against cells of extent c the margins below are 2^-12 c, far above the float64 rounding of
+// The cull decision (mnrf_object.h keep_ray, shared with mnrf_objects.hip) is evaluated in float64 on the fp32 object-frame
+// ray that mnrf_object_rays writes (mnrf_object.h move_ray, the same device function): against cells of extent c the margins below are 2^-12 c, far above the float64 rounding of
 // the expressions and far below the one cell the rule allows (include/mnrf.h).
 // Compiled with -ffp-contract=off and IEEE division, as the rest of the library.
 #include <hip/hip_runtime.h>
@@ -63,98 +63,9 @@ __global__ __launch_bounds__(256) void occupancy_bits_kernel(OccArgs A) {
 
 // ------------------------------------------------------------------------------------------------ the cull
 struct CullArgs {
-    const float* rays; long long n; mnrf_object::Move move;
-    double lo[3], cell[3]; int R[3]; const uint32_t* bits; int words;
+    const float* rays; long long n; mnrf_object::Move move; mnrf_object::Bounds bounds;
     float* out_rays; int* index; int* count;
 };
-
-constexpr double H = 0.5 + 1.0 / 64.0;        // half-width, in cells, of the neighbourhood looked at around a march sample
-constexpr double MARGIN = 1.0 / 4096.0;       // growth of a cell, in cell extents, in the exact test
-
-// Does the segment {o + d z : z in [zn, zf]} meet the closed box [a0, a1] grown by e?  Slabs; a NaN never says no.
-__device__ inline bool segment_meets_box(const double* o, const double* d, double zn, double zf, const double* a0,
-                                         const double* a1, const double* e) {
-    double t0 = zn, t1 = zf;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double b0 = a0[a] - e[a], b1 = a1[a] + e[a];
-        if (d[a] == 0.0) {
-            if (o[a] < b0 || o[a] > b1) return false;
-        } else {
-            const double ta = (b0 - o[a]) / d[a], tb = (b1 - o[a]) / d[a];
-            t0 = fmax(t0, fmin(ta, tb));
-            t1 = fmin(t1, fmax(ta, tb));
-        }
-    }
-    return !(t0 > t1);
-}
-
-// The rule of include/mnrf.h on one object-frame ray q.  The segment is clipped to the box (grown by H cells), walked in at
-// most max(R) + 3 samples no further apart than one cell on any axis; around each sample the set cells within H cells are
-// tested exactly.  A cell the segment meets lies within half a cell of the nearest sample on every axis, so it is looked at.
-__device__ inline bool keep_ray(const CullArgs& A, const float* q) {
-    bool finite = true;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) finite = finite && (fabsf(q[c]) <= 3.4028234663852886e38f);   // false for inf and NaN
-    if (!finite) return true;
-    const double o[3] = {q[0], q[1], q[2]}, d[3] = {q[3], q[4], q[5]};
-    const double zn = q[6], zf = q[7];
-    if (zf < zn) return false;                                         // an empty segment meets nothing
-    double e[3], blo[3], bhi[3], grow[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        e[a] = A.cell[a] * MARGIN + fabs(o[a]) * 0x1p-40;
-        blo[a] = A.lo[a];
-        bhi[a] = A.lo[a] + A.cell[a] * A.R[a];
-        grow[a] = A.cell[a] * H;
-    }
-    if (!A.bits) return segment_meets_box(o, d, zn, zf, blo, bhi, e);  // the whole box is one set cell
-    // clip to the grown box
-    double t0 = zn, t1 = zf, dt = 1.7976931348623157e308;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double b0 = blo[a] - grow[a], b1 = bhi[a] + grow[a];
-        if (d[a] == 0.0) {
-            if (o[a] < b0 || o[a] > b1) return false;
-        } else {
-            const double ta = (b0 - o[a]) / d[a], tb = (b1 - o[a]) / d[a];
-            t0 = fmax(t0, fmin(ta, tb));
-            t1 = fmin(t1, fmax(ta, tb));
-            dt = fmin(dt, A.cell[a] / fabs(d[a]));
-        }
-    }
-    if (t0 > t1) return false;
-    // (t1 - t0) / dt <= R + 2 H on the axis that gave dt, so n <= max(R) + 2: the trip count is bounded by Rx + Ry + Rz + 3
-    const int cap = A.R[0] + A.R[1] + A.R[2] + 2;
-    const double steps = ceil((t1 - t0) / dt);
-    const int n = steps < (double)cap ? (int)steps : cap;             // (a zero direction: dt is huge, n = 0, one sample)
-    const double step = n > 0 ? (t1 - t0) / n : 0.0;
-    for (int s = 0; s <= n; ++s) {
-        const double t = t0 + step * s;
-        int c0[3], c1[3];
-        bool any = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double u = (o[a] + d[a] * t - A.lo[a]) / A.cell[a];
-            const double f0 = fmax(floor(u - H), 0.0), f1 = fmin(floor(u + H), (double)(A.R[a] - 1));
-            any = any && f0 <= f1;
-            c0[a] = (int)f0;
-            c1[a] = (int)f1;
-        }
-        if (!any) continue;
-        for (int k = c0[2]; k <= c1[2]; ++k)
-            for (int j = c0[1]; j <= c1[1]; ++j) {
-                const uint32_t* row = A.bits + ((long long)k * A.R[1] + j) * A.words;
-                for (int i = c0[0]; i <= c1[0]; ++i) {
-                    if (!((row[i >> 5] >> (i & 31)) & 1u)) continue;
-                    const double a0[3] = {A.lo[0] + A.cell[0] * i, A.lo[1] + A.cell[1] * j, A.lo[2] + A.cell[2] * k};
-                    const double a1[3] = {A.lo[0] + A.cell[0] * (i + 1), A.lo[1] + A.cell[1] * (j + 1), A.lo[2] + A.cell[2] * (k + 1)};
-                    if (segment_meets_box(o, d, zn, zf, a0, a1, e)) return true;
-                }
-            }
-    }
-    return false;
-}
 
 // Pass 1, one thread per ray over the whole chip: the decision, as 0 / 1 in index[i].
 __global__ __launch_bounds__(256) void cull_mark_kernel(CullArgs A) {
@@ -162,7 +73,7 @@ __global__ __launch_bounds__(256) void cull_mark_kernel(CullArgs A) {
     if (i >= A.n) return;
     float q[8];
     mnrf_object::move_ray(A.move, A.rays + i * 8, q);
-    A.index[i] = keep_ray(A, q) ? 1 : 0;
+    A.index[i] = mnrf_object::keep_ray(A.bounds, q) ? 1 : 0;
 }
 
 // Pass 2: one workgroup walks the marks in order (wave ballots, a scan over the 16 waves: reflect_compact_kernel's scheme), so
@@ -248,14 +159,7 @@ extern "C" int mnrf_object_cull(const float* rays, int64_t n_rays, const float* 
     A.rays = rays;
     A.n = (long long)n_rays;
     A.move = mnrf_object::make_move(pose, scale, tx, ty, tz);
-    const int R[3] = {bits ? Rx : 1, bits ? Ry : 1, bits ? Rz : 1};      // without bits the whole box is one set cell
-    for (int a = 0; a < 3; ++a) {
-        A.lo[a] = (double)box_lo[a];
-        A.cell[a] = ((double)box_hi[a] - (double)box_lo[a]) / R[a];
-        A.R[a] = R[a];
-    }
-    A.bits = bits;
-    A.words = (R[0] + 31) / 32;
+    A.bounds = mnrf_object::make_bounds(box_lo, box_hi, Rx, Ry, Rz, bits);
     A.out_rays = out_rays;
     A.index = index;
     A.count = count;

@@ -1,0 +1,173 @@
+"""Several placed objects in one scene: `batched_inference(..., placed_objects=[PlacedObject(...), ...])`.
+
+app_reflect_newly_placed_objects of the reference places exactly one object; the single-object keywords of batched_inference
+(system_obj= / render_kwargs_test_d_nerf=, new_object=, object_bounds=) follow it.  A PlacedObject carries what those keywords
+carry for ONE object -- its field, its placement, optionally its bounds and, for a D-NeRF object, its own time -- and a list of
+1..MAX_OBJECTS of them is rendered at every recursion level by one rule:
+
+    for k = 0 .. K-1 in list order, the single-object merge of object k is applied to the ray's current (rgb, depth, mask),
+    current meaning as left by the scene and by the objects 0 .. k-1.
+
+That is the chain of K single-object applications, by definition.  The merge writes depth = d, so the nearest opaque object
+wins; an exact tie in depth goes to the later object of the list; a current depth <= near hides nothing, as in the reference's
+own rule (eval.py:275-281).  The device passes are mnrf_objects_cull (all K objects' bounds against a level's rays in two
+launches, ONE read of the K counts) and mnrf_objects_merge (one launch); per object they evaluate the device functions of the
+single-object kernels, so the result is that chain bit for bit.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+__all__ = ["PlacedObject", "MAX_OBJECTS", "cull_objects", "merge_objects"]
+
+MAX_OBJECTS = 8      # MNRF_OBJECTS_MAX
+
+SINGLE_OBJECT_KEYWORDS = ("system_obj", "render_kwargs_test_d_nerf", "new_object", "object_bounds", "object_region")
+
+
+class PlacedObject:
+    """One object of `placed_objects=`.
+
+    field: a nerf_pl `system_obj` (.models and .embeddings, load_object_system) or a `render_kwargs_test_d_nerf` dict
+    (dnerf.load_dnerf_object); the kind is taken from the type.
+    placement: what `new_object=` takes, dict(pose_align=None | 3x4 | 4x4, scale=, translation=); None: the args.root_dir preset
+    of the call (recursion.resolve_new_object, with its refusals).
+    bounds: None (every ray of a level renders the object), an ObjectBounds, or "auto" with region=(lo, hi) and bounds_res
+    cells per axis (recursion.resolve_object_bounds: estimated once and kept on a nerf_pl object, per call at the object's
+    time for a D-NeRF object).
+    time: a D-NeRF object's own time; None: the call's frame_time=, which is then required."""
+
+    def __init__(self, field, placement, bounds=None, region=None, bounds_res=64, time=None):
+        from .object_bounds import ObjectBounds
+        from .recursion import resolve_new_object
+        if isinstance(field, dict):
+            if field.get("network_fn") is None:
+                raise TypeError("PlacedObject: a dict field is a render_kwargs_test_d_nerf (dnerf.load_dnerf_object): it has no network_fn")
+            self.kind = "d_nerf"
+        elif hasattr(field, "models") and hasattr(field, "embeddings"):
+            self.kind = "nerf_pl"
+        else:
+            raise TypeError("PlacedObject: field must be a nerf_pl system_obj (.models and .embeddings, load_object_system) or a "
+                            f"render_kwargs_test_d_nerf dict (dnerf.load_dnerf_object), not {type(field).__name__}")
+        self.field = field
+        if placement is not None:
+            resolve_new_object(None, placement)          # its refusals, now and not at the first frame
+        self.placement = placement
+        if bounds is None:
+            if region is not None:
+                raise ValueError("PlacedObject: region= is the region bounds='auto' looks for the object in: pass bounds='auto'")
+        elif isinstance(bounds, str) and bounds == "auto":
+            if region is None or len(region) != 2:
+                raise ValueError("PlacedObject: bounds='auto' needs region=(lo, hi): the box of the object's frame to look for it in")
+        elif not isinstance(bounds, ObjectBounds):
+            raise ValueError(f"PlacedObject: bounds must be None, an ObjectBounds or 'auto', not {bounds!r}")
+        self.bounds, self.region, self.bounds_res = bounds, region, bounds_res
+        if time is not None:
+            if self.kind != "d_nerf":
+                raise ValueError("PlacedObject: time= is a D-NeRF object's time; a nerf_pl object does not move")
+            time = float(time)
+        self.time = time
+
+    def __repr__(self):
+        return f"PlacedObject({self.kind}, placement={self.placement!r}, bounds={self.bounds!r}, time={self.time!r})"
+
+    def resolve(self, args, frame_time, device):
+        """What one call needs of this object: dict(kind, field, xform, bounds, time)."""
+        from .recursion import resolve_new_object, resolve_object_bounds
+        time = None
+        if self.kind == "d_nerf":
+            time = self.time if self.time is not None else frame_time
+            if time is None:
+                raise ValueError("placed_objects: a D-NeRF object without time= needs frame_time= (the object's time in [0, 1])")
+            time = float(time)
+        kw = dict(object_bounds=self.bounds, object_region=self.region, object_bounds_res=self.bounds_res, system_obj=self.field)
+        bounds = resolve_object_bounds(kw, True, self.field if self.kind == "d_nerf" else None, time, device)
+        return dict(kind=self.kind, field=self.field, xform=resolve_new_object(args, self.placement), bounds=bounds, time=time)
+
+
+def refuse(args, models, kwargs):
+    """The refusals of `placed_objects=`, each with its reason; the conditions of the single-object path that do not name an
+    object hold here too."""
+    placed = kwargs["placed_objects"]
+    given = [k for k in SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
+    if given:
+        raise ValueError(f"placed_objects= carries every object's field, placement and bounds: it cannot be combined with "
+                         f"{', '.join(k + '=' for k in given)} (the single-object keywords)")
+    if not getattr(args, "app_reflect_newly_placed_objects", False):
+        raise ValueError("placed_objects= lists the objects of app_reflect_newly_placed_objects: the application is not on")
+    if isinstance(placed, PlacedObject) or not isinstance(placed, (list, tuple)):
+        raise TypeError(f"placed_objects must be a list of PlacedObject, not {type(placed).__name__}")
+    if not 1 <= len(placed) <= MAX_OBJECTS:
+        raise ValueError(f"placed_objects holds 1..{MAX_OBJECTS} objects (MNRF_OBJECTS_MAX), not {len(placed)}")
+    for k, obj in enumerate(placed):
+        if not isinstance(obj, PlacedObject):
+            raise TypeError(f"placed_objects[{k}] must be a PlacedObject, not {type(obj).__name__}")
+        if obj.kind == "d_nerf" and obj.time is None and kwargs.get("frame_time") is None:
+            raise ValueError(f"placed_objects[{k}] is a D-NeRF object without time=: it needs frame_time= (the object's time in "
+                             "[0, 1], eval.py:1130, 1154)")
+    for other in ("app_place_new_mirror", "app_reflection_substitution", "app_control_mirror_roughness"):
+        if getattr(args, other, False):
+            raise ValueError(f"app_reflect_newly_placed_objects cannot be combined with {other} (one application at a time)")
+    if not ("fine" in models and kwargs.get("_N_importance", 1) > 0 and not getattr(args, "only_one_field", False)
+            and getattr(models["fine"], "predict_mirror_mask", False)):
+        raise ValueError("app_reflect_newly_placed_objects needs a fine mirror mask (N_importance > 0, not only_one_field, "
+                         "predict_mirror_mask=True): the reference clears mirror_mask_fine where the object is seen "
+                         "(eval.py:291)")
+    if getattr(args, "near", None) is None:
+        raise ValueError("app_reflect_newly_placed_objects needs args.near: the occlusion test compares the depth with it "
+                         "(eval.py:169-171, 275-281)")
+
+
+def cull_objects(rays, placed):
+    """mnrf_objects_cull on one level's rays (N, 8) for the resolved objects `placed` (PlacedObject.resolve) ->
+    (out_rays (K, N, 8), index (K, N) int32, slot (K, N) int32, counts (K,) int32 on the device): per object what
+    ObjectBounds.cull returns -- for an object without bounds every ray, in order -- and slot, the inverse of index (-1: the
+    ray is not in the object's list)."""
+    K, N, dev = len(placed), rays.shape[0], rays.device
+    posed, poses, scales, trans = (ctypes.c_int * K)(), (ctypes.c_float * (12 * K))(), (ctypes.c_float * K)(), (ctypes.c_float * (3 * K))()
+    unbounded, lo, hi, res = (ctypes.c_int * K)(), (ctypes.c_float * (3 * K))(), (ctypes.c_float * (3 * K))(), (ctypes.c_int * (3 * K))()
+    bits = (ctypes.c_void_p * K)()
+    for k, o in enumerate(placed):
+        x, b = o["xform"], o["bounds"]
+        posed[k] = x["pose"] is not None
+        if x["pose"] is not None:
+            poses[12 * k:12 * k + 12] = x["pose"]
+        scales[k] = x["scale"]
+        trans[3 * k:3 * k + 3] = x["translation"]
+        unbounded[k] = b is None
+        res[3 * k:3 * k + 3] = (1, 1, 1)
+        if b is not None:
+            if b.bits is not None and b.bits.device != dev:
+                raise ValueError(f"ObjectBounds: the bits live on {b.bits.device}, the rays on {dev} (use .to(device))")
+            lo[3 * k:3 * k + 3], hi[3 * k:3 * k + 3], res[3 * k:3 * k + 3] = b.lo, b.hi, b.res
+            bits[k] = b.bits.data_ptr() if b.bits is not None else None
+    out = torch.empty(K, N, 8, dtype=torch.float32, device=dev)
+    index = torch.empty(K, N, dtype=torch.int32, device=dev)
+    slot = torch.empty(K, N, dtype=torch.int32, device=dev)
+    counts = torch.zeros(K, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_objects_cull(p(rays), N, K, posed, poses, scales, trans, unbounded, lo, hi, res, bits, p(out), p(index),
+                                            p(slot), p(counts), _lib.stream()), "mnrf_objects_cull")
+    return out, index, slot, counts
+
+
+def merge_objects(maps, placed, slot, counts, capacity, near, rgb, depth, mask, n_used):
+    """mnrf_objects_merge: maps[k] = (rgb, depth, opacity) of object k rendered on its kept rows, or None (not rendered), into
+    the level's rgb, depth, mask (None: no mirror head) in place; n_used: (K,) int32 on the device or None."""
+    K, N = len(placed), rgb.shape[0]
+    tables = [(ctypes.c_void_p * K)() for _ in range(3)]
+    hold = []
+    for k, m in enumerate(maps):
+        if m is None:
+            continue
+        for table, t in zip(tables, m):
+            t = t.contiguous()
+            hold.append(t)
+            table[k] = t.data_ptr()
+    scales = (ctypes.c_float * K)(*[o["xform"]["scale"] for o in placed])
+    ps0 = (ctypes.c_float * K)(*[o["xform"]["pose_scale0"] for o in placed])
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_objects_merge(tables[0], tables[1], tables[2], K, p(slot), p(counts), N, capacity, scales, ps0, float(near),
+                                             p(rgb), p(depth), p(mask), p(n_used), _lib.stream()), "mnrf_objects_merge")

@@ -14,7 +14,7 @@ Python here is the recursion driver only: mask thresholding, reflected-ray const
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
 mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
-mnrf_object_merge_indexed).  One 4-byte device->host read per level decides
+mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge).  One 4-byte device->host read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
@@ -166,6 +166,9 @@ def _refuse_apps(args, models, kwargs):
     """The application flags batched_inference cannot honour, refused up front with the reason."""
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
+    if kwargs.get("placed_objects") is not None:      # the list carries the kinds: args.obj_model_type is not consulted
+        from .placed_objects import refuse
+        return refuse(args, models, kwargs)
     if getattr(args, "app_reflect_newly_placed_objects", False):
         obj_type = getattr(args, "obj_model_type", "d_nerf")                   # eval.py:108: the reference's default
         if obj_type == "d_nerf":
@@ -324,6 +327,31 @@ def resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, device):
         except AttributeError:      # (an object without a __dict__: estimated per call)
             pass
     return cached[1]
+
+
+def _merge_objects(r, rays_chunk, placed, near, n_used, renderers):
+    """The K-object rule on one level's maps, in place (placed_objects.py): for k = 0 .. K-1 in list order, _merge_object's
+    per-ray rule of object k on the ray's current maps.  ONE mnrf_objects_cull moves and culls the level's rays for every
+    object, ONE device->host read brings the K counts, every object with a non-zero count is rendered on its kept rows
+    (renderers[k]: rays -> dict; queued back to back, no read in between), ONE mnrf_objects_merge applies the chain.  placed:
+    the resolved objects (PlacedObject.resolve); n_used: (K,) int32 on the device or None."""
+    from .placed_objects import cull_objects, merge_objects
+    N = rays_chunk.shape[0]
+    if N == 0:
+        return
+    obj_rays, _, slot, counts = cull_objects(rays_chunk, placed)
+    host = counts.tolist()                                    # the one read of this chunk and level
+    maps = [None] * len(placed)
+    for k, M in enumerate(host):
+        if M > 0:
+            o = renderers[k](obj_rays[k, :M])
+            maps[k] = (o["rgb_fine"], o["depth_fine"], o["opacity_fine"])
+    if not any(m is not None for m in maps):
+        return
+    for key in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
+        if key in r and not r[key].is_contiguous():
+            r[key] = r[key].contiguous()
+    merge_objects(maps, placed, slot, counts, N, near, r["rgb_fine"], r["depth_fine"], r.get("mirror_mask_fine"), n_used)
 
 
 def _f(dev, *s):
@@ -717,18 +745,44 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     object_region=(lo, hi) and optionally object_bounds_res=64, see resolve_object_bounds): the object is rendered only along
     the rays whose segment, in the object's frame, can touch the bounds (mnrf_object_cull, mnrf_object_merge_indexed).  Those
     rays get bit for bit what they get without bounds; the others stay as the scene rendered them.  Costs one more 4-byte
-    device->host read per chunk and level."""
+    device->host read per chunk and level.
+
+    placed_objects=[PlacedObject(field, placement, bounds=, region=, bounds_res=, time=), ...] (placed_objects.py; 1..8
+    objects, nerf_pl and D-NeRF mixed, each with its own placement, bounds and -- a D-NeRF object -- time, None meaning
+    frame_time=) with args.app_reflect_newly_placed_objects: several objects, each seen in the mirrors.  It replaces the
+    single-object keywords (system_obj=, render_kwargs_test_d_nerf=, new_object=, object_bounds=, object_region= are refused
+    beside it) and args.obj_model_type is not consulted.  THE RULE, at every recursion level, the last included, ahead of the
+    hard clip: per ray, for k = 0 .. K-1 in list order, the single-object merge above of object k is applied to the ray's
+    current (rgb, depth, mask) -- current: as left by the scene and by the objects 0 .. k-1.  This is by definition the chain
+    of K single-object applications.  The merge writes depth = d, so the nearest opaque object wins; an exact tie in depth
+    goes to the LATER object of the list; a current depth <= near hides nothing, as in the reference's own rule
+    (eval.py:275-281).  x_surface and the normals are not edited.  One mnrf_objects_cull, one read of the K counts, the
+    renders of the objects with kept rays and one mnrf_objects_merge per chunk and level (_merge_objects).  object_used= is
+    then a device int32 tensor of K elements -- element k: the number of rays, over all levels, that took object k when its
+    turn came; a ray that a later, nearer object then takes counts for BOTH -- or of 1 element, which receives their sum.
+    _object_chain=True (tests, measurements): the same list through K successive single-object passes (_merge_object), the
+    launches of the single-object path; the result is the same bit for bit."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
     _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
     objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
-    obj_xform = resolve_new_object(args, kwargs.get("new_object")) if objects else None
-    obj_dnerf = kwargs.get("render_kwargs_test_d_nerf") if objects and getattr(args, "obj_model_type", "d_nerf") == "d_nerf" else None
-    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if objects and obj_dnerf is None else (None, None)
+    placed = kwargs.get("placed_objects")
+    single = objects and placed is None                                    # the single-object keywords
+    obj_xform = resolve_new_object(args, kwargs.get("new_object")) if single else None
+    obj_dnerf = kwargs.get("render_kwargs_test_d_nerf") if single and getattr(args, "obj_model_type", "d_nerf") == "d_nerf" else None
+    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if single and obj_dnerf is None else (None, None)
     frame_time = float(kwargs["frame_time"]) if obj_dnerf is not None else None
     obj_used = kwargs.get("object_used") if objects else None
-    obj_bounds = resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, rays.device)
+    obj_bounds = resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, rays.device) if placed is None else None
+    used_k, object_chain = None, bool(kwargs.get("_object_chain", False))
+    if placed is not None:
+        call_time = kwargs.get("frame_time")
+        placed = [o.resolve(args, None if call_time is None else float(call_time), rays.device) for o in placed]
+        if obj_used is not None:
+            if obj_used.numel() not in (1, len(placed)):
+                raise ValueError(f"object_used holds {len(placed)} elements (one per placed object) or 1 (their total), not {obj_used.numel()}")
+            used_k = torch.zeros(len(placed), dtype=torch.int32, device=rays.device)
     if obj_used is not None:
         obj_used.zero_()
     place = bool(getattr(args, "app_place_new_mirror", False))
@@ -804,7 +858,13 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                         _rgb_depth_only=rgb_depth, _blended_level=blended)
         r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
         r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
-        if objects:                                                       # eval.py:173-291, ahead of the hard clip
+        if placed is not None and not object_chain:                       # the K-object rule, ahead of the hard clip
+            _merge_objects(r, rays_chunk, placed, args.near, used_k, placed_renderers)
+        elif placed is not None:                                          # the same list through the single-object launches
+            for k, o in enumerate(placed):
+                _merge_object(r, rays_chunk, o["xform"], args.near, None if used_k is None else used_k[k:k + 1],
+                              placed_renderers[k], o["bounds"])
+        elif objects:                                                     # eval.py:173-291, ahead of the hard clip
             _merge_object(r, rays_chunk, obj_xform, args.near, obj_used, render_object, obj_bounds)
         mask = None
         for key in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse"):
@@ -834,17 +894,28 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                     mirror_fraction[level] = (int(torch.count_nonzero(mask).item()) if any_mirror else 0) / rays_chunk.shape[0]
         return r, rays_chunk, level, mask, any_mirror, pending, counted
 
-    def render_object(obj_rays):
-        if obj_dnerf is not None:
+    def render_field(obj_rays, dnerf, time, field_models, field_embeddings):
+        if dnerf is not None:
             # eval.py:233-259: the time in column 8, the normalised directions behind it (a plain division); near and far are
             # the rays' own columns 6 and 7; samples, background and models come from the OBJECT's configuration
             d = obj_rays[:, 3:6]
-            batch = torch.cat([obj_rays, torch.full_like(obj_rays[:, :1], frame_time), d / torch.norm(d, dim=-1, keepdim=True)], -1)
-            o = render_rays_dnerf(batch, **dict(obj_dnerf, _frame_time=frame_time))
+            batch = torch.cat([obj_rays, torch.full_like(obj_rays[:, :1], time), d / torch.norm(d, dim=-1, keepdim=True)], -1)
+            o = render_rays_dnerf(batch, **dict(dnerf, _frame_time=time))
             return {"rgb_fine": o["rgb_map"], "depth_fine": o["depth_map"], "opacity_fine": o["acc_map"]}
         # eval.py:221-232: only colour, depth and opacity of this render are read -- the maps-only path
-        return render_rays(obj_models, obj_embeddings, obj_rays, N_samples, use_disp, 0, 0, N_importance, chunk, white_back,
+        return render_rays(field_models, field_embeddings, obj_rays, N_samples, use_disp, 0, 0, N_importance, chunk, white_back,
                            test_time=True, compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
+
+    def render_object(obj_rays):
+        return render_field(obj_rays, obj_dnerf, frame_time, obj_models, obj_embeddings)
+
+    def placed_renderer(o):
+        if o["kind"] == "d_nerf":
+            return lambda obj_rays: render_field(obj_rays, o["field"], o["time"], None, None)
+        field_models, field_embeddings = _object_system(o["field"])
+        return lambda obj_rays: render_field(obj_rays, None, None, field_models, field_embeddings)
+
+    placed_renderers = [placed_renderer(o) for o in placed] if placed is not None else None
 
     def recurse(rays_chunk, level):
         return stage_b(stage_a(rays_chunk, level))
@@ -978,10 +1049,15 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     from .mirror_nerf import check_guard, release_transient
     guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else []) + \
         (list(obj_models.values()) if obj_models is not None else [])      # (a D-NeRF object runs fp32 only: no guard)
+    for o in placed or ():
+        if o["kind"] == "nerf_pl":
+            guarded += [m for m in _object_system(o["field"])[0].values() if not any(m is g for g in guarded)]
     if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard(guarded):
         try:
             return batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk,
                                      **dict(kwargs, _guard_retry=True))
         finally:
             release_transient(guarded)      # (a range-only trip: this frame on fp32, the next one on split again)
+    if used_k is not None:
+        obj_used.copy_(used_k if obj_used.numel() == used_k.numel() else used_k.sum(dtype=torch.int32).view(1))
     return {k: torch.cat(v, 0) for k, v in results.items()}

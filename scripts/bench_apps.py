@@ -24,6 +24,18 @@ app_off + kept_fraction x (unculled - app_off).  The random-init object is opaqu
 unculled frame: outside the box the object is simply absent.  Nothing is asserted on the times.
 
     python scripts/bench_apps.py --obj_bounds [--reps 3]
+
+--objects K [K ...] runs the several-objects leg INSTEAD (batched_inference(placed_objects=), on the same workload at
+max_recursive_level 1): for each K, K copies of the object (--objects_kind nerf_pl: the object leg's; d_nerf: the D-NeRF leg's)
+under the office preset, each bounded by its own cube of the object's frame that about 10 % of the PRIMARY rays hit (cubes
+around the points that K pixels spread over the middle row look at, sized by bisection with mnrf_object_cull).  Routes: `fused`
+(one mnrf_objects_cull, one read of the K counts, one mnrf_objects_merge per chunk and level), `chain` (_object_chain=True: K
+successive single-object passes, the launches of the single-object path) and, for K = 1, `legacy` (the single-object keywords).
+One warm-up frame per route, then --reps rounds (default 7 for this leg) that alternate the routes frame by frame; the host
+clock around a frame that ends in a synchronise; median and spread (max - min over the median) per route.  Also reported: the
+kept rays per object and level, and the device->host reads of kept-ray counts per frame.  Nothing is asserted on the times.
+
+    python scripts/bench_apps.py --objects 1 2 4 [--objects_kind nerf_pl] [--reps 7]
 """
 import argparse
 import json
@@ -178,14 +190,141 @@ def bounds_leg(a, models, emb, rays, dev, base_args):
     return res
 
 
+def nerf_pl_object(dev, emb):
+    """The object of fixture g26_object_office_l2 as system_obj: seed 7, density head x 1000 with the fixture's biases."""
+    from types import SimpleNamespace
+    obj_models = {}
+    for name, sd, bias in zip(("coarse", "fine"), SY.make_state_dict(7, 2, predict_normal=False, predict_mirror_mask=False), (6.18, 44.94)):
+        SY.apply_tweaks(sd, [["sigma.weight", "mul", 1000.0], ["sigma.bias", "set", bias]])
+        m = M.MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=False, predict_mirror_mask=False)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        obj_models[name] = m.to(dev).eval()
+    return SimpleNamespace(models=obj_models, embeddings=emb)
+
+
+def objects_leg(a, models, emb, rays, dev, base_args):
+    """The --objects leg (module docstring) -> the result dict."""
+    from types import SimpleNamespace
+    from mirror_nerf_amd import ObjectBounds, PlacedObject
+    from mirror_nerf_amd import placed_objects as PO
+    reps = a.reps
+    kind = a.objects_kind
+    field = nerf_pl_object(dev, emb) if kind == "nerf_pl" else dnerf_object(dev)
+    on_args = dict(base_args, app_reflect_newly_placed_objects=True, obj_model_type=kind, root_dir="office", near=0.05)
+    xform = REC.resolve_new_object(SimpleNamespace(root_dir="office"))
+    placement = dict(pose_align=None, scale=xform["scale"], translation=xform["translation"])
+    n_primary = rays.shape[0]
+    time_kw = dict(frame_time=0.37) if kind == "d_nerf" else {}
+
+    def frame(**kw):
+        out = M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=on_args, trace_secondary_rays=True,
+                                  to_cpu=False, **time_kw, **kw)
+        torch.cuda.synchronize()
+        return out
+
+    def timed(**kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frame(**kw)
+        return (time.perf_counter() - t0) * 1e3
+
+    def cube_for(col, target=0.1):
+        """A cube around the point the pixel (H / 2, col) looks at, in the object's frame, that `target` of the primary rays hit."""
+        ray = rays[(H // 2) * W + col].double().cpu()
+        o = ray[:3] * xform["scale"] + torch.tensor(xform["translation"], dtype=torch.float64)
+        c = (o + ray[3:6] * 0.5 * (ray[6] + ray[7])).tolist()
+        cube = lambda h: ObjectBounds([v - h for v in c], [v + h for v in c])  # noqa: E731
+        share = lambda h: int(cube(h).cull(rays, xform)[2].item()) / n_primary  # noqa: E731
+        lo_h, hi_h = 1e-4, 64.0
+        for _ in range(40):
+            mid = (lo_h * hi_h) ** 0.5
+            lo_h, hi_h = (mid, hi_h) if share(mid) < target else (lo_h, mid)
+        return cube(hi_h), round(share(hi_h), 4)
+
+    def counted(K, **kw):
+        """One unpipelined frame -> (kept rays [object][level], rays per level, reads of kept-ray counts)."""
+        kept, level_rays, level, reads = [[0, 0] for _ in range(K)], [0, 0], [0], [0]
+        scene, cull_k, cull_1 = REC.render_rays, PO.cull_objects, ObjectBounds.cull
+        turn = [0]
+
+        def count_scene(m_, e_, r, *x, **k):
+            if m_ is models:
+                level[0] = 1 if k.get("_rgb_depth_only") else 0
+                level_rays[level[0]] += int(r.shape[0])
+                turn[0] = 0
+            return scene(m_, e_, r, *x, **k)
+
+        def count_k(r, placed):
+            out = cull_k(r, placed)
+            reads[0] += 1
+            for k, c in enumerate(out[3].tolist()):
+                kept[k][level[0]] += c
+            return out
+
+        def count_1(self, r, xf):
+            out = cull_1(self, r, xf)
+            reads[0] += 1
+            kept[turn[0] % K][level[0]] += int(out[2].item())
+            turn[0] += 1
+            return out
+        REC.render_rays, PO.cull_objects, ObjectBounds.cull = count_scene, count_k, count_1
+        os.environ["MNRF_EVAL_PIPELINE"] = "0"
+        try:
+            frame(**kw)
+        finally:
+            REC.render_rays, PO.cull_objects, ObjectBounds.cull = scene, cull_k, cull_1
+            os.environ.pop("MNRF_EVAL_PIPELINE")
+        return kept, level_rays, reads[0]
+
+    res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "
+                       f"all-mirror random-init pair (bench.py config 2), max_recursive_level 1; K copies of the {kind} object of the "
+                       "object legs under the office preset, each in its own cube hit by about 10 % of the primary rays",
+           "protocol": f"one warm-up frame per route, then {reps} rounds alternating the routes frame by frame; host clock around a frame "
+                       "that ends in a synchronise; median, spread = (max - min) / median of a route's frames",
+           "object_kind": kind}
+    for K in a.objects:
+        cols = [W * (j + 1) // (K + 1) for j in range(K)]
+        cubes = [cube_for(c) for c in cols]
+        placed = [PlacedObject(field, placement, bounds=b) for b, _ in cubes]
+        used = torch.zeros(K, dtype=torch.int32, device=dev)
+        routes = {"fused": dict(placed_objects=placed, object_used=used), "chain": dict(placed_objects=placed, object_used=used, _object_chain=True)}
+        if K == 1:
+            one = {"system_obj": field} if kind == "nerf_pl" else {"render_kwargs_test_d_nerf": field}
+            routes["legacy"] = dict(one, object_bounds=cubes[0][0], object_used=used)
+        times = {name: [] for name in routes}
+        for kw in routes.values():
+            frame(**kw)
+        for _ in range(reps):
+            for name, kw in routes.items():
+                times[name].append(timed(**kw))
+        entry = {"pixel_columns": cols, "primary_rays_hit": [s_ for _, s_ in cubes], "box_half_size": [round((b.hi[0] - b.lo[0]) / 2, 5) for b, _ in cubes]}
+        for name, kw in routes.items():
+            kept, level_rays, reads = counted(K, **kw)
+            frame(**kw)
+            ms = statistics.median(times[name])
+            entry[name] = {"ms_per_frame": round(ms, 2), "ms_reps": [round(t, 2) for t in times[name]],
+                           "spread": round((max(times[name]) - min(times[name])) / ms, 4), "rays_per_level": level_rays,
+                           "kept_rays_per_object_and_level": kept,
+                           "kept_share_per_level": [round(sum(k[lv] for k in kept) / max(K * level_rays[lv], 1), 4) for lv in range(2)],
+                           "count_reads_per_frame": reads, "rays_that_took_each_object": used.tolist()}
+        entry["fused_over_chain"] = round(entry["fused"]["ms_per_frame"] / entry["chain"]["ms_per_frame"], 4)
+        if K == 1:
+            entry["fused_over_legacy"] = round(entry["fused"]["ms_per_frame"] / entry["legacy"]["ms_per_frame"], 4)
+        res[f"K{K}"] = entry
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=None, help="timed frames per route (default 3; 7 for --objects)")
+    ap.add_argument("--objects", type=int, nargs="+", default=None, metavar="K", help="run the several-objects leg instead, for each K (1..8)")
+    ap.add_argument("--objects_kind", type=str, default="nerf_pl", choices=("nerf_pl", "d_nerf"))
     ap.add_argument("--levels", type=int, nargs="+", default=[2, 50])
     ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
     ap.add_argument("--no_dnerf", action="store_true", help="skip the leg with a D-NeRF object")
     ap.add_argument("--obj_bounds", action="store_true", help="run the object-bounds leg instead of the others")
     a = ap.parse_args()
+    a.reps = a.reps or (7 if a.objects else 3)
     dev = "cuda:0"
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
     emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
@@ -237,6 +376,9 @@ def main():
     base_args = dict(ARGS)
     if a.obj_bounds:
         print(json.dumps(bounds_leg(a, models, emb, rays, dev, base_args)))
+        return
+    if a.objects:
+        print(json.dumps(objects_leg(a, models, emb, rays, dev, base_args)))
         return
     off, ms_off, t_off, traced_off = run(base_args)
     res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "

@@ -35,6 +35,18 @@ frame i at frame_time = i / n_frames (eval.py:1130, 1154): the object moves from
 the cells `auto` finds occupied inside --obj_region at --obj_bounds_res cells per axis (object_bounds.py): the rays that are
 kept get exactly what they get without the flag.
 
+Several objects: --app_reflect_newly_placed_objects --objects_json FILE, a JSON list of entries
+
+    {"ckpt_path": ..., "model_type": "nerf_pl" | "d_nerf", "pose_align": null | 3x4 | 4x4, "scale": 1.0, "translation": [0, 0, 0],
+     "bounds": null | [x0, y0, z0, x1, y1, z1] | "auto", "region": [x0, y0, z0, x1, y1, z1], "bounds_res": 64,
+     "time_offset": 0.0, "time_scale": 1.0}
+
+(ckpt_path and model_type are required; a relative ckpt_path is taken from the file's directory) places up to 8 objects, each
+with its own placement and bounds, through batched_inference(placed_objects=): per ray they are merged in list order by the
+single-object rule, so the nearest opaque object wins and a tie in depth goes to the later entry.  Frame i of n renders D-NeRF
+object j at time_offset + time_scale * i / n; a time outside [0, 1] is refused before the first frame.  The flag replaces
+--obj_ckpt_path and the --obj_* flags and is refused beside them.
+
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
 and the other scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
 frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
@@ -94,7 +106,16 @@ def get_opts(argv=None):
                     help="x0 y0 z0 x1 y1 z1 of the region `--obj_bounds auto` looks for the object in.  The default is the extent of the "
                          "Blender-synthetic scenes such objects are trained in (cameras at radius 4, near 2, far 6): a guess, override it")
     ap.add_argument("--obj_bounds_res", type=int, default=64, help="cells per axis of the estimated bounds")
+    ap.add_argument("--objects_json", type=str, default=None,
+                    help="several placed objects: a JSON list of {ckpt_path, model_type, pose_align, scale, translation, bounds, region, "
+                         "bounds_res, time_offset, time_scale}; replaces --obj_ckpt_path and the --obj_* flags")
     args = ap.parse_args(argv)
+    if args.objects_json is not None:
+        given = sorted({a.split("=")[0] for a in (sys.argv[1:] if argv is None else argv) if str(a).startswith("--obj_")})
+        if given:
+            ap.error(f"--objects_json carries every object's checkpoint, kind and bounds: it cannot be combined with {', '.join(given)}")
+        if not args.app_reflect_newly_placed_objects:
+            ap.error("--objects_json lists the objects of --app_reflect_newly_placed_objects")
     if args.obj_bounds is not None:
         if not args.app_reflect_newly_placed_objects:
             ap.error("--obj_bounds bounds the object of --app_reflect_newly_placed_objects")
@@ -135,6 +156,84 @@ def load_object(args, device):
     return {"system_obj": load_object_system(args.obj_ckpt_path, device, args.N_importance, trusted=args.trusted)}
 
 
+OBJECT_KEYS = {"ckpt_path": None, "model_type": None, "pose_align": None, "scale": 1.0, "translation": (0.0, 0.0, 0.0), "bounds": None,
+               "region": (-1.5, -1.5, -1.5, 1.5, 1.5, 1.5), "bounds_res": 64, "time_offset": 0.0, "time_scale": 1.0}
+
+
+def read_objects_json(path):
+    """--objects_json FILE -> the list of entries, every key present (OBJECT_KEYS holds the defaults), refused with the reason
+    when the file is not what the flag describes."""
+    import json
+    with open(path) as f:
+        entries = json.load(f)
+    if not isinstance(entries, list) or not 1 <= len(entries) <= 8:
+        raise SystemExit(f"[Error] {path}: --objects_json takes a list of 1..8 objects")
+    out = []
+    for j, e in enumerate(entries):
+        if not isinstance(e, dict):
+            raise SystemExit(f"[Error] {path}: object {j} is not a JSON object")
+        unknown, missing = sorted(set(e) - set(OBJECT_KEYS)), [k for k in ("ckpt_path", "model_type") if e.get(k) is None]
+        if unknown or missing:
+            raise SystemExit(f"[Error] {path}: object {j}: unknown keys {unknown}, missing keys {missing} (known: {sorted(OBJECT_KEYS)})")
+        e = dict(OBJECT_KEYS, **e)
+        if e["model_type"] not in ("nerf_pl", "d_nerf"):
+            raise SystemExit(f"[Error] {path}: object {j}: model_type must be 'nerf_pl' or 'd_nerf', not {e['model_type']!r}")
+        b = e["bounds"]
+        if not (b is None or b == "auto" or (isinstance(b, list) and len(b) == 6)):
+            raise SystemExit(f"[Error] {path}: object {j}: bounds must be null, [x0, y0, z0, x1, y1, z1] or \"auto\", not {b!r}")
+        if len(e["region"]) != 6:
+            raise SystemExit(f"[Error] {path}: object {j}: region holds six numbers (x0 y0 z0 x1 y1 z1)")
+        if not os.path.isabs(e["ckpt_path"]):
+            e["ckpt_path"] = os.path.join(os.path.dirname(os.path.abspath(path)), e["ckpt_path"])
+        out.append(e)
+    return out
+
+
+def object_time(entry, i, n_frames):
+    return float(entry["time_offset"]) + float(entry["time_scale"]) * i / n_frames
+
+
+def check_object_times(entries, n_frames):
+    """A D-NeRF object's time of every frame lies in [0, 1], or nothing is rendered."""
+    for j, e in enumerate(entries):
+        if e["model_type"] != "d_nerf":
+            continue
+        for i in range(n_frames):
+            t = object_time(e, i, n_frames)
+            if not 0.0 <= t <= 1.0:
+                raise SystemExit(f"[Error] --objects_json: object {j} would be rendered at time {t:.4f} in frame {i} of {n_frames} "
+                                 f"(time_offset {e['time_offset']} + time_scale {e['time_scale']} * i / n): outside [0, 1]")
+
+
+def load_placed(entries, args, device):
+    """The fields of --objects_json, loaded once: [(entry, field)]."""
+    from mirror_nerf_amd.dnerf import load_dnerf_object
+    from mirror_nerf_amd.recursion import load_object_system
+    fields = []
+    for j, e in enumerate(entries):
+        print(f"[info] Load object {j} ({e['model_type']}) from ckpt:", e["ckpt_path"])
+        if e["model_type"] == "d_nerf":
+            fields.append((e, load_dnerf_object(e["ckpt_path"], device, trusted=args.trusted)))
+        else:
+            fields.append((e, load_object_system(e["ckpt_path"], device, args.N_importance, trusted=args.trusted)))
+    return fields
+
+
+def placed_objects(fields, i, n_frames):
+    """The `placed_objects=` list of frame i: every object with its placement and bounds, a D-NeRF object at its time."""
+    from mirror_nerf_amd import ObjectBounds, PlacedObject
+    out = []
+    for e, field in fields:
+        b, region = e["bounds"], None
+        if isinstance(b, list):
+            b = ObjectBounds(b[:3], b[3:])
+        elif b == "auto":
+            region = (tuple(e["region"][:3]), tuple(e["region"][3:]))
+        out.append(PlacedObject(field, dict(pose_align=e["pose_align"], scale=e["scale"], translation=e["translation"]), bounds=b, region=region,
+                                bounds_res=e["bounds_res"], time=object_time(e, i, n_frames) if e["model_type"] == "d_nerf" else None))
+    return out
+
+
 _BOUNDS = {}      # id(the nerf_pl object) -> its bounds: estimated once; a D-NeRF object is estimated per frame
 
 
@@ -165,10 +264,13 @@ def object_bounds(args, obj, frame_time=None):
     return b
 
 
-def render(system, rays, args, obj=None, frame_time=None):
-    """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object."""
+def render(system, rays, args, obj=None, frame_time=None, placed=None):
+    """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object;
+    placed: the frame's list of PlacedObject (--objects_json), in place of obj."""
     import mirror_nerf_amd as M
     extra = dict(obj or {})
+    if placed is not None:
+        extra = {"placed_objects": placed}
     if "render_kwargs_test_d_nerf" in extra:
         extra["frame_time"] = frame_time
     bounds = object_bounds(args, obj, frame_time)
@@ -238,8 +340,12 @@ def main(argv=None):
         else:
             bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
         n_frames, frame_of = bank.n_frames, bank.frame
+    entries = read_objects_json(args.objects_json) if args.objects_json is not None else None
+    if entries is not None:
+        check_object_times(entries, n_frames)
     system = load_system(args, dev)
-    system_obj = load_object(args, dev)
+    system_obj = load_object(args, dev) if entries is None else None
+    fields = load_placed(entries, args, dev) if entries is not None else None
 
     out = args.out_dir
     dirs = {"rgb": out, "mirror_mask": os.path.join(out, "mirror_mask"), "depth": os.path.join(out, "depth"),
@@ -265,7 +371,8 @@ def main(argv=None):
     with ThreadPoolExecutor(max_workers=max(1, min(16, args.workers))) as pool:
         for i in range(n_frames):
             sample = frame_of(i)
-            results = render(system, sample["rays"], args, system_obj, frame_time=i / n_frames)      # eval.py:1130
+            results = render(system, sample["rays"], args, system_obj, frame_time=i / n_frames,      # eval.py:1130
+                             placed=placed_objects(fields, i, n_frames) if fields is not None else None)
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
