@@ -109,3 +109,44 @@ def cases():
     for c in (3, 4):
         out.append((f"stack2_c{c}", np.stack([make_source(hw, c, "noise", seed=100 + c), make_source(hw, c, "ramp", seed=200 + c)]), wh))
     return out
+
+
+# ----------------------------------------------------------------------------- the cases of fixture g22_resample_edges
+# The launch geometry of csrc/mnrf_resample.hip: TPB threads along the output x, rows on gridDim.y up to ROWS_MAX and strided
+# beyond.  Every shape of cases() fits one x-block and one sweep of rows; these are the smallest that do not:
+#   (3, 90) -> (300, 3)     the pass along x alone, upscaling: a second x-block, ragged (300 = 256 + 44)
+#   (9, 300) -> (300, 4)    the pass along y alone at 300 columns: ox >= 256 in the y pass
+#   (5, 700) -> (260, 3)    both passes, downscaling; a ragged second block in both, the buffer between them 260 wide
+#   (7, 1100) -> (520, 5)   both passes, three x-blocks
+# and a stack of EDGE_STACK_FRAMES frames of (24, 10) -> (7, 23): the pass along x runs over frames * 24 = 72000 rows and the
+# pass along y over frames * 23 = 69000, both past ROWS_MAX, so the stride over rows runs in each.
+TPB = 256
+ROWS_MAX = 65535
+EDGE_SHAPES = (((3, 90), (300, 3)), ((9, 300), (300, 4)), ((5, 700), (260, 3)), ((7, 1100), (520, 5)))
+EDGE_STACK_SHAPE = ((24, 10), (7, 23))
+EDGE_STACK_FRAMES = 3000
+EDGE_STACK = f"stack{EDGE_STACK_FRAMES}_c4"
+
+
+def past_one_x_block(dst_w):
+    """A second x-block, and a last one that is not full."""
+    return dst_w > TPB and dst_w % TPB != 0
+
+
+def rows_strided(frames, src_h, dst_h):
+    """Both passes sweep their rows more than once: the pass along x has the source's rows, the pass along y the target's."""
+    return frames * src_h > ROWS_MAX and frames * dst_h > ROWS_MAX
+
+
+def edge_cases():
+    """(name, source (F, H, W, C), (w, h)) of every case of the fixture: RGB and RGBA noise, an RGBA ramp (alpha 0 / 255 / mixed in thirds,
+    so the unpremultiply's branches also run past column 256), and the stack, hashed as a whole so that no two frames agree."""
+    out = []
+    for k, (hw, wh) in enumerate(EDGE_SHAPES):
+        assert past_one_x_block(wh[0])
+        for c, kind in ((3, "noise"), (4, "noise"), (4, "ramp")):
+            out.append((f"{hw[0]}x{hw[1]}_to_{wh[0]}x{wh[1]}_c{c}_{kind}", make_source(hw, c, kind, seed=300 + 10 * k + c)[None], wh))
+    (h, w), wh = EDGE_STACK_SHAPE
+    assert rows_strided(EDGE_STACK_FRAMES, h, wh[1])
+    out.append((EDGE_STACK, make_source((EDGE_STACK_FRAMES * h, w), 4, "noise", seed=400).reshape(EDGE_STACK_FRAMES, h, w, 4), wh))
+    return out

@@ -5,7 +5,13 @@ operation (the kernels are compiled without contraction and with correctly round
 values inside [0, 256), and min / max do not depend on the order of reduction.
 
 Shapes: 1 x 1; 23 x 37 (odd: 3-byte rows never align to a dword; fewer pixels than one block of 256 threads x 4 pixels; not a
-multiple of a wave); 67 x 130 (several blocks and a tail)."""
+multiple of a wave); 67 x 130 (several blocks and a tail).  Those fit every grid uncapped (26 blocks at the most).  Past the caps:
+n = 1 400 003 (3 n / 1024 = 4102 blocks wanted: frame_finish_kernel's cap of 4096 and frame_extrema_kernel's of 1024 are both
+reached, so the flat three-channel loops and the reduction stride, with n and 3 n no multiples of 4 and a storage offset of 1;
+a second frame of that size has its extremes only where a thread's second or later value lies); n = 4 200 003 (n / 1024 = 4102:
+the per-pixel loops of frame_finish_kernel -- mirror mask, depth_image, store_pixels -- and of depth_colormap_kernel sweep
+twice, the latter over a stack of two frames of different ranges, whose own extremes come from a capped extrema launch with
+one stats block per frame).  Each of these tests asserts that reach from its n."""
 import importlib.util
 import json
 import os
@@ -50,13 +56,13 @@ def _to_device(maps, offset=0):
 
 
 def _extrema(dev_maps, running=None):
-    """The six extremes of the stats block after one extrema launch, as float32 numpy."""
+    """The six extremes of the stats block after one extrema launch, as float32 numpy (x_surface may be absent: a null map)."""
     from mirror_nerf_amd import _lib
     L = _lib.lib()
     stats = torch.zeros(L.mnrf_frame_stats_floats(), dtype=torch.float32, device=DEV)
     n = dev_maps["depth"].shape[0]
     _lib.check(L.mnrf_frame_extrema(dev_maps["depth"].data_ptr(), dev_maps["depth_reflect"].data_ptr(),
-                                    dev_maps["x_surface"].data_ptr(), n, stats.data_ptr(),
+                                    dev_maps["x_surface"].data_ptr() if "x_surface" in dev_maps else None, n, stats.data_ptr(),
                                     None if running is None else running.data_ptr(), _lib.stream()), "mnrf_frame_extrema")
     s = stats.cpu().numpy()
     assert not s[8:].view(np.uint32).any()       # the reduction's state is left zero for the next launch
@@ -105,6 +111,113 @@ CASES = [  # (H, W, storage offset, seeded_maps keywords)
 def test_images_and_extrema_equal_numpy(H, W, offset, kw):
     maps = FR.seeded_maps(H * W, seed=H * 1000 + W + offset, **kw)
     _check_frame(maps, _table(), offset)
+
+
+# ----------------------------------------------------------------------------- past the caps of the grids
+# blocks_for(items, 4 per thread, cap) of csrc/mnrf_frames.hip: a block covers 256 * 4 = 1024 items of a loop's first sweep.
+FINISH_CAP, EXTREMA_CAP = 4096, 1024
+N_FLAT = 1_400_003           # 3 n floats: the flat loops of frame_finish_kernel sweep twice
+N_PIXEL = 4_200_003          # n pixels: its per-pixel loops, and depth_colormap_kernel's, sweep twice
+
+
+def _blocks(items):
+    return -(-items // 1024)
+
+
+def test_flat_loops_past_the_grid_caps():
+    """rgb, the normals and x_surface on the second sweep of a grid capped at 4096 blocks, the extrema launch at its cap of
+    1024; n is no multiple of 4 and the maps start 4 bytes past a 16-byte boundary, so the tails and the scalar loads run."""
+    n = N_FLAT
+    assert _blocks(3 * n) > FINISH_CAP and _blocks(3 * n) > EXTREMA_CAP and n % 4 != 0 and (3 * n) % 4 != 0
+    _check_frame(FR.seeded_maps(n, seed=41, nonfinite="all"), _table(), 1)
+
+
+def test_extremes_that_only_the_later_sweeps_see():
+    """The extrema launch has 1024 * 256 threads and each takes one value per sweep: the minimum and the maximum of both
+    depths and of x_surface are put at flat positions from 1024 * 256 on, where only a thread's second or later value finds
+    them -- one of them in the last three elements of its map."""
+    n = N_FLAT
+    first_sweep = EXTREMA_CAP * 256
+    assert _blocks(n) > EXTREMA_CAP and _blocks(3 * n) > FINISH_CAP
+    maps = FR.seeded_maps(n, seed=42, nonfinite="none")
+    places = {"depth": (n - 2, first_sweep + 37_856), "depth_reflect": (first_sweep, n - 1),
+              "x_surface": (3 * n - 1, first_sweep + 3 * 4096 * 256 + 5)}          # (minimum, maximum), flat
+    for k, (lo, hi) in places.items():
+        flat = maps[k].reshape(-1)
+        assert np.shares_memory(flat, maps[k])                                       # a view: the edit lands in the map
+        flat[lo], flat[hi] = flat.min() - np.float32(1.5), flat.max() + np.float32(2.5)
+    for k, (lo, hi) in places.items():
+        flat = maps[k].reshape(-1)
+        assert min(lo, hi) >= first_sweep and max(lo, hi) < flat.size
+        assert int(np.argmin(flat)) == lo and int(np.argmax(flat)) == hi
+        assert (flat == flat[lo]).sum() == 1 and (flat == flat[hi]).sum() == 1
+    assert any(p >= maps[k].size - 3 for k, pair in places.items() for p in pair)
+    assert (_want_extrema(maps) == [maps[k].reshape(-1)[p] for k in places for p in places[k]]).all()
+    _check_frame(maps, _table())
+
+
+@pytest.fixture(scope="module")
+def pixel_frames():
+    """Two frames of N_PIXEL pixels with the maps the per-pixel images need (and rgb, without which nothing is emitted): the
+    second is the first reversed, its depth squared and its reflected depth shifted, so the frames' ranges differ.  NaN only:
+    with an infinity the range overflows and every pixel gets the same colour."""
+    n = N_PIXEL
+    assert _blocks(n) > FINISH_CAP and n % 4 != 0
+    first = {k: v for k, v in FR.seeded_maps(n, seed=43, nonfinite="nan").items() if k in ("rgb", "mirror_mask", "depth", "depth_reflect")}
+    second = {k: np.ascontiguousarray(v[::-1]) for k, v in first.items() if k != "rgb"}
+    second["depth"] = (second["depth"] * second["depth"] * np.float32(0.125)).astype(np.float32)      # not a rescaling: another image
+    second["depth_reflect"] = (second["depth_reflect"] + np.float32(1.5)).astype(np.float32)
+    return first, second
+
+
+def test_per_pixel_loops_past_the_grid_cap(pixel_frames):
+    """mirror_mask, depth and depth_reflect of frame_finish_kernel on their second sweep (4 pixels per thread, 4096 blocks)."""
+    from mirror_nerf_amd import frames
+    maps, _ = pixel_frames
+    n, T = N_PIXEL, _table(6)
+    assert _blocks(n) > FINISH_CAP
+    dev = _to_device(maps)
+    stems = ["mirror_mask", "depth", "depth_reflect"]
+    got = frames.finish_frame(_results(dev), "fine", table=T, want=stems)
+    want = FR.frame_images(_results(maps), T)
+    assert set(got) == {"mirror_mask_fine", "depth_fine", "depth_reflect_fine"} and set(got) | {"rgb_fine"} == set(want)
+    for k in got:
+        g = got[k].cpu().numpy()
+        assert g.dtype == np.uint8 and g.shape == want[k].shape == (n, 3)
+        bad = np.flatnonzero((g != want[k]).any(axis=1))
+        assert bad.size == 0, (k, bad.size, bad[:5], g[bad[:5]], want[k][bad[:5]])
+        assert len(np.unique(g[:, 0])) > 16                    # an image, not one colour
+    ex = _extrema(dev)                                         # without x_surface; asserts the reduction's state is zero again
+    want_ex = np.array([*FR.depth_extrema(maps["depth"]), *FR.depth_extrema(maps["depth_reflect"])], np.float32)
+    assert (_bits(ex[:4]) == _bits(want_ex)).all() and np.isnan(ex[4:6]).all()
+    for k in dev:
+        assert dev[k].cpu().numpy().tobytes() == maps[k].tobytes(), k
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["depth", "depth_reflect"])
+@pytest.mark.parametrize("own", [False, True], ids=["given_extremes", "own_extremes"])
+def test_depth_stack_past_the_grid_cap(pixel_frames, own, masked):
+    """depth_colormap_kernel on its second sweep over a stack of two frames of different ranges: with the frames' own
+    extremes (the extrema launch at its cap, one stats block per frame) and with a given pair that clips both frames."""
+    from mirror_nerf_amd import frames
+    n, T = N_PIXEL, _table(7)
+    assert _blocks(n) > FINISH_CAP and _blocks(n) > EXTREMA_CAP
+    key = "depth_reflect" if masked else "depth"
+    stack = torch.from_numpy(np.stack([m[key] for m in pixel_frames])).to(DEV)
+    masks = torch.from_numpy(np.stack([m["mirror_mask"] for m in pixel_frames])).to(DEV) if masked else None
+    pair = (None, None) if own else ((1.0, 7.5) if masked else (2.5, 5.0))
+    if own:
+        ranges = [FR.depth_extrema(m[key]) for m in pixel_frames]
+        assert ranges[0][0] != ranges[1][0] or ranges[0][1] != ranges[1][1]
+    ex = None if own else torch.tensor(pair, dtype=torch.float32, device=DEV)
+    got = frames.colormap_depth(stack, ex, masks, table=T)
+    assert tuple(got.shape) == (2, n, 3) and got.dtype == torch.uint8
+    got = got.cpu().numpy()
+    for f, m in enumerate(pixel_frames):
+        want = FR.depth_reflect_image(m[key], m["mirror_mask"], T, *pair) if masked else FR.depth_image(m[key], T, *pair)
+        bad = np.flatnonzero((got[f] != want).any(axis=1))
+        assert bad.size == 0, (f, bad.size, bad[:5], got[f][bad[:5]], want[bad[:5]])
+    assert (got[0] != got[1][::-1]).any()
 
 
 def test_default_table_is_jet():

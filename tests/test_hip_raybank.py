@@ -4,7 +4,11 @@ Everything is compared exactly: gathered rays against mnrf_generate_rays of the 
 bit), colours and masks against the same float32 expressions in torch on the CPU (IEEE division, multiply, subtract, add; no
 contraction on either side), drawn indices against the integer restatement tests/raybank_ref.py.  The one tolerance is fixture
 G12's own 1e-6 on rays captured from the reference.  Shapes: odd, non-square frames (37 x 53, 5 x 7), N not a power of two,
-batches that divide neither N nor the 256-thread block."""
+batches that divide neither N nor the 256-thread block.  Those banks have 105 and 5883 rays (half = 4 and 7).  The 32-bit range of
+the stream is reached with banks that select the two frames of a small base bank tens of thousands of times: N = 2^32 - 1 (the
+largest accepted; half = 16, slots and `start` above 2^31), N = 2^31 (the domain is 2 N and `x >= N` a uint32 comparison with
+0x80000000), N = 2^31 + 65536 (bit 31 set on both sides of it), and with plain banks of N = 65536 (N is the domain: no walk),
+65537 (half = 9, the longest walks) and 1, 2, 3 (the bit count raised to 2).  Each asserts its N and its half."""
 import ctypes
 import os
 import subprocess
@@ -185,6 +189,120 @@ def test_frame_selection():
     for bad in ([], [4], [-1], "all"):
         with pytest.raises(ValueError):
             b.select(bad)
+
+
+# ----------------------------------------------------------------------------- the 32-bit range of the shuffled stream
+# Banks whose n_rays sits at the edges of the permutation's domain, made by selecting the frames of a small base bank again and
+# again (a slot costs 4 bytes).  (id, base (F, H, W, C), selection, N, half):
+EDGE_BANKS = [
+    ("N=2^32-1", (2, 255, 257, 4), [0, 1] * 32768 + [1], 2 ** 32 - 1, 16),   # the largest N accepted: the domain 2^32 holds one value more
+    ("N=2^31", (2, 256, 256, 4), [0, 1] * 16384, 2 ** 31, 16),               # N - 1 has 31 bits, the domain is 2^32 = 2 N: every other value
+    #                                                                          walks, and the walk ends on a uint32 comparison with 0x80000000
+    ("N=2^31+65536", (2, 256, 256, 4), [0, 1] * 16384 + [0], 2 ** 31 + 65536, 16),      # x >= N with bit 31 set on both sides
+    ("N=65536", (1, 256, 256, 3), None, 65536, 8),                           # N is the Feistel domain: never walks
+    ("N=65537", (1, 1, 65537, 3), None, 65537, 9),                           # one past it: the domain is 4 N - 4, long walks
+    ("N=1", (1, 1, 1, 3), None, 1, 1),                                       # bits < 2 is raised to 2; every draw is ray 0
+    ("N=2", (1, 1, 2, 3), None, 2, 1),
+    ("N=3", (1, 1, 3, 3), None, 3, 1),
+]
+EDGE_B = 1000
+
+
+def _edge_base(F, H, W, C, seed):
+    from mirror_nerf_amd.data import RayBank
+    rng = np.random.default_rng(seed)
+    images = rng.integers(0, 256, (F, H, W, C), dtype=np.uint8)
+    masks = rng.integers(-1, 2, (F, H, W)).astype(np.int8)
+    return RayBank(_poses(F, seed), images, masks, 0.5 * W / np.tan(0.5 * 0.6911112), NEAR, FAR, DEV)
+
+
+@pytest.fixture(scope="module", params=EDGE_BANKS, ids=[e[0] for e in EDGE_BANKS])
+def edge_bank(request):
+    """(bank, base bank, every row of the base bank, N, whether the bank is a selection)"""
+    _, shape, selection, N, half = request.param
+    base = _edge_base(*shape, seed=len(selection or []) + shape[1])
+    b = base if selection is None else base.select(selection)
+    assert b.n_rays == N and R.half_bits(N) == half and N < 2 ** 32          # the reach of the case
+    return b, base, base.gather(torch.arange(base.n_rays, device=DEV)), N, selection is not None
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype == torch.float32 and torch.equal(a.reshape(-1).view(torch.int32), b.reshape(-1).view(torch.int32))
+
+
+def test_stream_at_the_edges_of_its_32_bit_range(edge_bank):
+    """The drawn indices are the restatement's at step 0, at the step that straddles the end of epoch 0, several epochs on at a
+    position above 2^32 (also reached through the device step word), at one above 2^34 and for rank 2 of 3; the drawn rows are the gather of those
+    indices and, through the frame list, the base bank's pixels."""
+    b, base, base_rows, N, selected = edge_bank
+    B, hw = EDGE_B, b.H * b.W
+    straddle, far, deep = N // B, (3 * N + 2 ** 32) // B + 7, 2 ** 34 // B + 1
+    assert N % B != 0 and (straddle * B) // N == 0 and (straddle * B + B - 1) // N >= 1      # the batch crosses into epoch 1
+    assert far * B > 2 ** 32 and (far * B) // N >= 3 and ((far * 3 + 2) * B) // N >= 3
+    assert (deep * B) // N >= 4 and (N > 3 or (deep * B) // N >= 2 ** 32)       # small banks: the epoch has a high word
+    word = torch.tensor([far - 5], dtype=torch.int64, device=DEV)
+    ids = torch.tensor(b.frame_ids, dtype=torch.int64, device=DEV)
+    for seed in (0, 2 ** 40 + 12345):
+        draws = [(s, 0, 1, None) for s in (0, straddle, far, deep)] + [(5, 0, 1, word), (0, 2, 3, None), (far, 2, 3, None)]
+        for step, rank, world, step_dev in draws:
+            tag = (seed, step, rank, world, step_dev is not None)
+            rays, rgbs, mask, idx = b.draw(step, B, seed, rank=rank, world=world, step_dev=step_dev, return_indices=True)
+            want = R.draw_indices(N, far if step_dev is not None else step, B, seed, rank, world)
+            assert idx.dtype == torch.int64 and np.array_equal(idx.cpu().numpy(), want), tag
+            assert int(idx.min()) >= 0 and int(idx.max()) < N
+            rows = (rays, rgbs, mask)
+            assert not any(t.isnan().any() for t in rows), tag
+            for got, ref in zip(rows, b.gather(idx)):
+                assert _same_bits(got, ref), tag
+            pixels = ids[idx // hw] * hw + idx % hw                          # slots past 2^31 are pixels of the base frames
+            assert selected or torch.equal(pixels, idx)
+            for got, ref in zip(rows, base_rows):
+                assert _same_bits(got, ref[pixels]), tag
+        if N == 2 ** 32 - 1:
+            assert int(idx.max()) >= 2 ** 31                                 # half of the bank lies there: bit 31 is in use
+    if N == 1:
+        assert not idx.any()
+    if selected:
+        assert set(b.frame_ids) == {0, 1} and len(set((ids[idx // hw]).tolist())) == 2      # both base frames were drawn from
+
+
+def test_last_slot_of_an_edge_bank_is_its_base_frame(edge_bank):
+    """frame(last slot): the rows start + 0 ... start + hw - 1 with start = (slots - 1) hw, above 2^31 in the large banks."""
+    b, base, _, N, _ = edge_bank
+    last = b.n_frames - 1
+    if N > 2 ** 31:
+        assert last * b.H * b.W >= 2 ** 31
+    got, want = b.frame(last), base.frame(b.frame_ids[last])
+    assert set(got) == {"rays", "rgbs", "mirror_mask", "valid_mask"} and got["valid_mask"].dtype == torch.bool
+    for k in got:
+        assert (torch.equal(got[k], want[k]) if k == "valid_mask" else _same_bits(got[k], want[k])), k
+
+
+def test_gather_addresses_the_whole_64_bit_index():
+    """Explicit indices around 2^31 and 2^32 on the bank of 2^32 - 1 rays: the rows inside are the base bank's, N, 2^32 and -1
+    give NaN.  One slot more makes N >= 2^32: a draw is refused, a gather above 2^32 still finds its pixel."""
+    _, shape, selection, N, _ = EDGE_BANKS[0]
+    base = _edge_base(*shape, seed=3)
+    rows = base.gather(torch.arange(base.n_rays, device=DEV))
+    hw = base.H * base.W
+
+    def check(bank, indices, inside):
+        got = bank.gather(torch.tensor(indices, dtype=torch.int64, device=DEV))
+        for k, (g, ok) in enumerate(zip(indices, inside)):
+            for t, ref in zip(got, rows):
+                if ok:
+                    assert _same_bits(t[k], ref[bank.frame_ids[g // hw] * hw + g % hw]), g
+                else:
+                    assert t[k].isnan().all(), g
+
+    b = base.select(selection)
+    assert b.n_rays == N == 2 ** 32 - 1
+    check(b, [0, 2 ** 31 - 1, 2 ** 31, N - 1, N, 2 ** 32, -1], [True, True, True, True, False, False, False])
+    more = base.select(selection + [0])
+    assert more.n_rays == 65538 * hw >= 2 ** 32
+    with pytest.raises(RuntimeError, match=r"below 2\^32"):
+        more.draw(0, EDGE_B, 0, rank=0, world=1)
+    check(more, [2 ** 32, 2 ** 32 + 12345, more.n_rays - 1, more.n_rays], [True, True, True, False])
 
 
 def test_captured_draw_advances_with_a_device_step_word(bank):

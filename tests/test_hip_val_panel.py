@@ -2,7 +2,10 @@
 numpy restatement of visualize_val_image(..., add_text=False) that tests/test_validation_cpu.py holds to the reference's own
 capture.  Tolerance ZERO: every tile is the reference's chain of single fp32 operations.  Shapes: 6x8 (less than a wave of
 4-pixel threads), 5x13 (65 pixels: one past 64, and no multiple of 4, so the tail and the unaligned rows run), 37x29 (1073
-pixels: past one 256-thread workgroup of 4-pixel threads, a multiple of nothing)."""
+pixels: past one 256-thread workgroup of 4-pixel threads, a multiple of nothing).  Those need 4 blocks at the most.  Past the
+grid caps: 283x311 (3 n / 1024 = 258 blocks wanted, panel_extrema_kernel has 256: it strides, and the last ticket is taken
+under a capped grid) and 1031x1019 (n / 1024 = 1026 blocks wanted, panel_write_kernel has 1024: it strides; n = 1 mod 4).  Both
+tests assert that reach from H and W."""
 import json
 import os
 
@@ -33,11 +36,47 @@ def _run(H, W, batch, res):
     return stack, names
 
 
+EXTREMA_CAP, WRITE_CAP = 256, 1024          # the grid caps of panel_extrema_kernel and panel_write_kernel
+
+
+def _blocks(items):
+    """Blocks of 256 threads x 4 items that a loop's first sweep would need."""
+    return -(-items // 1024)
+
+
 @pytest.mark.parametrize("variant", VR.VARIANTS)
 @pytest.mark.parametrize("H,W", SHAPES, ids=[f"{h}x{w}" for h, w in SHAPES])
 def test_val_panel_is_the_restatement_exactly(H, W, variant):
+    _check_panel(H, W, variant, *VR.seeded_case(H, W, 100 + H, variant))
+
+
+@pytest.mark.parametrize("variant", ["all", "nan_global", "depth_extremes_last"])
+def test_val_panel_past_the_extrema_cap(variant):
+    """283 x 311: the launch is sized for 3 n values at 4 per thread and wants 258 blocks; panel_extrema_kernel has 256 and
+    strides.  Its 65536 threads take one value per sweep, so a global tile is swept five times and a depth tile (n = 88013
+    values) twice, and the last-ticket reduction runs under the capped grid.  The NaN of nan_global sits in the last pixel and
+    the extremes of depth_extremes_last in the last element: both are seen in the last sweep only."""
+    H, W = 283, 311
+    assert _blocks(3 * H * W) > EXTREMA_CAP and H * W - 1 >= EXTREMA_CAP * 256
+    _check_panel(H, W, variant, *VR.seeded_case(H, W, 100 + H, variant))
+
+
+def test_val_panel_past_the_write_cap():
+    """1031 x 1019: n / 1024 = 1026 blocks wanted, panel_write_kernel has 1024 and strides (and n = 1 mod 4: the tail runs
+    there).  A reduced set of maps, still with a tile of each kind."""
+    from mirror_nerf_amd import _lib, frames
+    H, W = 1031, 1019
+    assert _blocks(H * W) > WRITE_CAP and (H * W) % 4 != 0
+    batch, res = VR.seeded_case(H, W, 100 + H, "all")
+    res = {k: res[k] for k in ("rgb_fine", "depth_fine", "depth_coarse_reflect", "surface_normal_fine", "x_surface_fine")}
+    kinds = [kind for _, kind, _ in frames.val_panel_tiles(batch, res)]
+    assert set(kinds) == {_lib.MNRF_PANEL_COPY, _lib.MNRF_PANEL_MASK, _lib.MNRF_PANEL_NORMAL, _lib.MNRF_PANEL_GLOBAL,
+                          _lib.MNRF_PANEL_DEPTH} and len(kinds) == 7
+    _check_panel(H, W, "all", batch, res)
+
+
+def _check_panel(H, W, variant, batch, res):
     from mirror_nerf_amd.frames import jet_table
-    batch, res = VR.seeded_case(H, W, 100 + H, variant)
     want, want_names = VR.val_panel((W, H), batch, res, jet_table())
     stack, names = _run(H, W, batch, res)
     assert names == want_names

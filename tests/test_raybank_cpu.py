@@ -1,5 +1,7 @@
 """The ray bank without a GPU: the permutation of tests/raybank_ref.py (the integer restatement of csrc/mnrf_bank.hip's
-contract) is a bijection, differs between epochs and seeds and lands uniformly; `read_blender` reads a small Blender-format
+contract) is a bijection, differs between epochs and seeds and lands uniformly, and equals a scalar implementation in plain Python integers
+at the N where 32-bit arithmetic could slip (1, 2, 3, 65536, 65537, 2^31, 2^31 + 65536, 2^32 - 1: the banks
+tests/test_hip_raybank.py holds the kernel to), at epoch boundaries and at positions above 2^32; `read_blender` reads a small Blender-format
 directory built here with PIL; the C entry points refuse bad arguments before any launch."""
 import ctypes
 import json
@@ -61,6 +63,55 @@ def test_landing_counts_are_uniform():
 
     assert chi2(R.ROUNDS) < 1.5
     assert chi2(2) > 10          # the check sees a weak network
+
+
+# --------------------------------------------------------------------------- the restatement against plain Python integers
+def _mix32(x):
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def _scalar_stream(p, n, seed):
+    """One stream position in Python integers, from the contract in the header comment of csrc/mnrf_bank.hip: nothing is shared
+    with tests/raybank_ref.py and nothing depends on how numpy's uint64 wraps, shifts or divides."""
+    epoch, i = divmod(p, n)
+    half = (max(2, (n - 1).bit_length()) + 1) // 2
+    mask = (1 << half) - 1
+    keys = []
+    for r in range(6):
+        k = _mix32(((seed & 0xFFFFFFFF) + 0x9E3779B9 * (r + 1)) & 0xFFFFFFFF)
+        k = _mix32(k ^ ((seed >> 32) & 0xFFFFFFFF))
+        keys.append(_mix32(_mix32(k ^ (epoch & 0xFFFFFFFF)) ^ ((epoch >> 32) & 0xFFFFFFFF)))
+    x, passes = i, 0
+    while True:
+        L, R_ = x >> half, x & mask
+        for k in keys:
+            L, R_ = R_, L ^ (_mix32(R_ ^ k) & mask)
+        x, passes = (L << half) | R_, passes + 1
+        assert x < 4 ** half and passes <= 64
+        if x < n:
+            return x
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 65536, 65537, 2 ** 31, 2 ** 31 + 65536, 2 ** 32 - 1])
+def test_stream_equals_plain_python_integers_at_the_edges_of_its_range(n):
+    """The N of tests/test_hip_raybank.py's edge banks: 40 positions at each of the start, the end of epoch 0 (both sides), an
+    epoch boundary above 2^32, a position whose epoch has a high word (small n) and the top of a 60-bit step count."""
+    over = -(-(2 ** 32 + 12345) // n) * n                         # the first epoch boundary above 2^32 + 12345
+    starts = [0, max(n - 20, 0), over - 20, 7 * over + n // 3, (2 ** 60 // n) * n - 20]
+    p = sorted({s + k for s in starts for k in range(40)})
+    assert len(p) >= 100 and any(a // n != b // n for a, b in zip(p, p[1:])) and p[-1] > 2 ** 32 and p[-1] < 2 ** 64
+    assert any(a > 2 ** 32 and a // n != (a + 1) // n for a in p[:-1])      # an epoch boundary above 2^32
+    for seed in (0, 2 ** 40 + 12345, 2 ** 64 - 1):
+        got = R.stream(np.array(p, np.uint64), n, seed)
+        want = [_scalar_stream(q, n, seed) for q in p]
+        assert got.dtype == np.int64 and got.tolist() == want, (n, seed)
+        assert 0 <= min(want) and max(want) < n
+    if n >= 2 ** 31:
+        assert max(want) >= 2 ** 30
 
 
 # --------------------------------------------------------------------------- the loader

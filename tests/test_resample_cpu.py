@@ -1,6 +1,11 @@
 """The device resize without a GPU: `data.lanczos_taps`, fed through the numpy restatement of tests/resample_ref.py (what
 csrc/mnrf_resample.hip is written from), reproduces Pillow's own LANCZOS resize (fixture G22) with tolerance zero; the C entry
-points refuse bad arguments with a message before any launch."""
+points refuse bad arguments with a message before any launch.
+
+Shapes: those of `RR.cases()`, each inside one 256-wide x-block of the device kernels, and those of `RR.edge_cases()` (fixture
+g22_resample_edges), which tests/test_hip_resample.py runs on the device past that block and past 65535 rows: outputs 300, 260
+and 520 wide, and a 3000-frame stack of which the fixture keeps Pillow's CRC-32.  Here they anchor the restatement to Pillow
+at those shapes."""
 import ctypes
 import os
 import zlib
@@ -12,6 +17,7 @@ from tests import resample_ref as RR
 from tests.golden.fixtures import Fixture
 
 CASES = RR.cases()
+EDGE_CASES = RR.edge_cases()
 
 
 @pytest.fixture(scope="module")
@@ -32,6 +38,39 @@ def test_taps_reproduce_pillow(g22, name, src, wh):
     want = g22.outputs[name]
     assert got.shape == want.shape == (src.shape[0], wh[1], wh[0], src.shape[3])
     assert np.array_equal(got, want), int(np.abs(got.astype(int) - want.astype(int)).max())
+
+
+@pytest.fixture(scope="module")
+def g22_edges():
+    return Fixture("g22_resample_edges")
+
+
+def test_edge_sources_are_the_fixture_s(g22_edges):
+    """The stack's output is kept as a checksum only; every other case has its bytes."""
+    assert {n for n, _, _ in EDGE_CASES} == set(g22_edges.outputs) | {RR.EDGE_STACK} == set(g22_edges.meta["source_crc32"])
+    assert set(g22_edges.meta["output_crc32"]) == {RR.EDGE_STACK}
+    for name, src, _ in EDGE_CASES:
+        assert zlib.crc32(src.tobytes()) == g22_edges.meta["source_crc32"][name], name
+    stack = dict((n, s) for n, s, _ in EDGE_CASES)[RR.EDGE_STACK]
+    assert len({zlib.crc32(f.tobytes()) for f in stack}) == stack.shape[0]        # no two frames agree
+
+
+@pytest.mark.parametrize("name,src,wh", EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
+def test_taps_reproduce_pillow_past_one_launch_tile(g22_edges, name, src, wh):
+    from mirror_nerf_amd.data import lanczos_taps
+    F, sh, sw, C = src.shape
+    if name == RR.EDGE_STACK:
+        assert RR.rows_strided(F, sh, wh[1]) and sw != wh[0]
+    else:
+        assert RR.past_one_x_block(wh[0])
+    got = RR.resample(src, wh, lanczos_taps)
+    assert got.dtype == np.uint8 and got.shape == (F, wh[1], wh[0], C)
+    if name == RR.EDGE_STACK:
+        assert zlib.crc32(got.tobytes()) == g22_edges.meta["output_crc32"][name]
+    else:
+        want = g22_edges.outputs[name]
+        assert got.shape == want.shape
+        assert np.array_equal(got, want), int(np.abs(got.astype(int) - want.astype(int)).max())
 
 
 def test_same_size_is_a_copy_without_the_alpha_round_trip(g22):
