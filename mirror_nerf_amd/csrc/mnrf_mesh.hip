@@ -284,8 +284,8 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const int32_t* tri, long 
                                                        int32_t* counts) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tri) return;
-    const int a = tri[t * 3];
-    if (a < 0 || a >= n_vert) return;
+    const int a = tri[t * 3 + 0], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
+    if (a < 0 || b < 0 || c < 0 || a >= n_vert || b >= n_vert || c >= n_vert) return;      // (refused, as cc_hook_kernel refuses it)
     const int l = labels[a];
     if (l < 0 || l >= n_vert) return;
     atomicAdd(&counts[l], 1);

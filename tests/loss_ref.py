@@ -307,3 +307,159 @@ def grad_parts(key, got, want):
     yield key, got, want
     if key.startswith("mirror_mask_") and np.asarray(want).shape[0] > len(MASK_EDGES):
         yield key + "[6:]", np.asarray(got)[len(MASK_EDGES):], np.asarray(want)[len(MASK_EDGES):]
+
+
+# ------------------------------------------------------------------------------------------------------------------ PSNR and MSE
+# metrics.mse / metrics.psnr (mse_partial_kernel + mse_finish_kernel of csrc/mnrf_loss.hip), for tests/test_hip_psnr_fp64.py and, on
+# the CPU, tests/test_loss_ref_cpu.py.  The reference is the float64 mean of (float64(a) - float64(b))^2 over the selected elements
+# and -10 log10 of it.  The bar is derived from the kernel's float32 summation, not measured:
+#
+#   every term (a - b)^2 carries 3 roundings (the subtraction, doubled by the square, and the square's own);
+#   a thread adds its q = ceil(n / (blocks * 256)) terms serially, the first onto an exact 0: q - 1 roundings;
+#   block_sum: six shuffle levels and the four wave sums added onto an exact 0: 6 + 3 = 9;
+#   mse_finish_kernel adds the `blocks` partials serially onto an exact 0: blocks - 1;  the division: 1.
+#
+# All terms are non-negative, so to first order the relative error of the sum is at most the largest number of roundings any one
+# term passes through, times 2^-24: (3 + (q - 1) + 9 + (blocks - 1) + 1) * 2^-24 with blocks = min(1024, ceil(n / 256)).  The PSNR
+# adds the derivative of -10 log10, 10 / ln 10, times that, and 2 ulp of the PSNR value for log10f.
+MSE_TPB, MSE_MAX_BLOCKS = 256, 1024
+MSE_SWEEP = MSE_TPB * MSE_MAX_BLOCKS          # 262 144 elements per pass of the grid-stride loop
+U32 = 2.0 ** -24
+
+
+def mse_geometry(n):
+    """(blocks, q): the launch of mnrf_mse_psnr for n elements and the number of terms its busiest thread adds."""
+    blocks = min(MSE_MAX_BLOCKS, max(1, -(-n // MSE_TPB)))
+    return blocks, -(-n // (blocks * MSE_TPB))
+
+
+def mse_bar(n):
+    """The relative bar of the MSE (and of the count) for n elements."""
+    blocks, q = mse_geometry(n)
+    return (3 + max(q - 1, 0) + 9 + (blocks - 1) + 1) * U32
+
+
+def psnr_bar(n, psnr):
+    """The absolute bar of the PSNR in dB around the float64 value `psnr`."""
+    return 10.0 / np.log(10.0) * mse_bar(n) + 2.0 * float(np.spacing(np.float32(abs(psnr))))
+
+
+def mse_selection(n, mask, per_mask):
+    """(n,) bool: element i is selected when there is no mask or mask[i // per_mask] is set."""
+    if mask is None:
+        return np.ones(n, dtype=bool)
+    return np.asarray(mask).reshape(-1).astype(bool)[np.arange(n) // per_mask]
+
+
+def mse_fp64(a, b, sel):
+    """(mse, psnr, count) in float64 over the selected elements; an empty selection is (nan, nan, 0)."""
+    d = np.asarray(a, np.float32).reshape(-1).astype(np.float64)[sel] - np.asarray(b, np.float32).reshape(-1).astype(np.float64)[sel]
+    if d.size == 0:
+        return float("nan"), float("nan"), 0
+    m = float((d * d).mean())
+    with np.errstate(divide="ignore"):
+        return m, float(-10.0 * np.log10(m)), int(d.size)
+
+
+def _block_sum_f32(v):
+    """block_sum of csrc/mnrf_loss.hip on a (blocks, 256) float32 array: per wave of 64 the shuffle-down tree (lane 0 holds
+    the sum), then the four wave sums added in order onto 0."""
+    v = v.reshape(v.shape[0], MSE_TPB // 64, 64).copy()
+    for o in (32, 16, 8, 4, 2, 1):
+        v[..., :o] = v[..., :o] + v[..., o:2 * o]
+    r = np.zeros(v.shape[0], dtype=np.float32)
+    for w in range(MSE_TPB // 64):
+        r = r + v[:, w, 0]
+    return r
+
+
+def mse_emulate(a, b, sel):
+    """The kernels' own order in float32 numpy: (partials (blocks, 2) float32, out (3,) float32 = [mse, psnr, count]).  The MSE
+    and the count are what the kernel computes bit for bit (IEEE float32 adds, multiplies and one division, nothing contracted);
+    the PSNR goes through numpy's log10 and may differ from log10f in the last place."""
+    a, b = np.asarray(a, np.float32).reshape(-1), np.asarray(b, np.float32).reshape(-1)
+    n = a.size
+    blocks, q = mse_geometry(n)
+    d = a - b
+    pad = max(q, 1) * blocks * MSE_TPB
+    term, one = np.zeros(pad, np.float32), np.zeros(pad, np.float32)
+    term[:n] = np.where(sel, d * d, np.float32(0))
+    one[:n] = sel
+    term, one = term.reshape(-1, blocks, MSE_TPB), one.reshape(-1, blocks, MSE_TPB)
+    s, c = np.zeros((blocks, MSE_TPB), np.float32), np.zeros((blocks, MSE_TPB), np.float32)
+    for j in range(term.shape[0]):      # thread (block, t) visits i = block * 256 + t + j * blocks * 256; a skipped term adds an exact 0
+        s, c = s + term[j], c + one[j]
+    partials = np.stack([_block_sum_f32(s), _block_sum_f32(c)], 1)
+    ts, tc = np.float32(0), np.float32(0)
+    for k in range(blocks):
+        ts, tc = ts + partials[k, 0], tc + partials[k, 1]
+    with np.errstate(all="ignore"):
+        m = np.float32(ts / tc)
+        out = np.array([m, np.float32(-10) * np.log10(m), tc], dtype=np.float32)
+    return partials, out
+
+
+PSNR_SIZES = (1, 63, 64, 65, 255, 256, 257, MSE_SWEEP - 1, MSE_SWEEP, MSE_SWEEP + 1, 3 * MSE_SWEEP + 5, 2 ** 24 + 257)
+PSNR_MASK_N = 3 * MSE_SWEEP + 6          # 786 438 = 3 * 262 146: three full passes and a tail, whole pixels of 3 channels
+# name -> (n, per_mask or None, kind of mask, kind of images)
+PSNR_CASES = {f"size_{n}": (n, None, None, "noise") for n in PSNR_SIZES}
+PSNR_CASES.update({
+    "mask_element": (PSNR_MASK_N, 1, "random", "noise"),
+    "mask_pixel3": (PSNR_MASK_N, 3, "random", "noise"),
+    "mask_pixel4": (PSNR_MASK_N + 2, 4, "random", "noise"),        # 786 440 = 4 * 196 610 = 5 * 157 288
+    "mask_pixel5": (PSNR_MASK_N + 2, 5, "random", "noise"),
+    "mask_all_true": (PSNR_MASK_N, 3, "all", "noise"),
+    "mask_late_passes": (PSNR_MASK_N, 1, "late", "noise"),
+    "mask_last_only": (PSNR_MASK_N, 1, "last", "noise"),
+    "mask_none_selected": (PSNR_MASK_N, 3, "none", "noise"),
+    "identical": (MSE_SWEEP + 1, None, None, "identical"),
+    "one_element_2^-20": (1000, None, None, "one"),
+    "scale_255": (MSE_SWEEP + 1, None, None, "255"),
+})
+_PSNR_BUILT = {}
+
+
+def psnr_case(name):
+    """-> dict(a, b (n,) float32, mask (n // per,) uint8 or None, per, sel (n,) bool, ref = mse_fp64(...)): seeded, built once,
+    left unchanged."""
+    c = _PSNR_BUILT.get(name)
+    if c is None:
+        n, per, mkind, ikind = PSNR_CASES[name]
+        rs = np.random.RandomState(list(PSNR_CASES).index(name) + 100)
+        b = rs.uniform(0, 1, n).astype(np.float32)
+        if ikind == "identical":
+            a = b.copy()
+        elif ikind == "one":
+            b[:] = np.round(b * 256) / 256
+            b[n // 2] = 0.5
+            a = b.copy()
+            a[n // 2] = np.float32(0.5 + 2.0 ** -20)
+        else:
+            a = np.clip(b + rs.normal(0, 0.05, n), 0, 1).astype(np.float32)
+            if ikind == "255":
+                a, b = a * np.float32(255), b * np.float32(255)
+        mask = None
+        if mkind is not None:
+            m = n // per
+            mask = {"random": lambda: rs.uniform(size=m) < 0.5, "all": lambda: np.ones(m, bool), "none": lambda: np.zeros(m, bool),
+                    "late": lambda: (rs.uniform(size=m) < 0.5) & (np.arange(m) >= MSE_SWEEP) & (np.arange(m) < 3 * MSE_SWEEP),
+                    "last": lambda: np.arange(m) == m - 1}[mkind]().astype(np.uint8)
+        sel = mse_selection(n, mask, per or 1)
+        c = _PSNR_BUILT[name] = dict(a=a, b=b, mask=mask, per=per or 1, sel=sel, ref=mse_fp64(a, b, sel))
+        if n > 2 ** 24:      # (the one large case is not kept: 200 MB)
+            del _PSNR_BUILT[name]
+    return c
+
+
+def psnr_errors(c, out):
+    """c: a psnr_case; out = [mse, psnr, count] as float32 -> (mse error / bar, psnr error / bar, count error / bar) against the
+    float64 reference of the case, each a fraction of its derived bar; the caller asserts <= 1.  NaN must meet NaN, 0 must meet
+    0, +inf +inf."""
+    n = c["a"].size
+    m, p, cnt = c["ref"]
+    gm, gp, gc = (float(x) for x in out)
+    if cnt == 0:
+        return (0.0 if np.isnan(gm) else np.inf, 0.0 if np.isnan(gp) else np.inf, 0.0 if gc == 0.0 else np.inf)
+    if m == 0.0:
+        return (0.0 if gm == 0.0 else np.inf, 0.0 if gp == np.inf else np.inf, abs(gc - cnt) / cnt / mse_bar(n))
+    return (abs(gm - m) / m / mse_bar(n), abs(gp - p) / psnr_bar(n, p), abs(gc - cnt) / cnt / mse_bar(n))

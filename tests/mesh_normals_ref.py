@@ -1,6 +1,7 @@
 """Plain numpy restatements for the tests of the colouring along the vertex normals (mirror_nerf_amd.mesh.vertex_normals,
 normal_rays, rgb_to_uint8): float64 throughout, sums in the order of the triangle array (np.add.at).  Nothing is shared
-with csrc/mnrf_mesh.hip, whose sums are 64-bit fixed point and free of any order.
+with csrc/mnrf_mesh.hip, whose sums are 64-bit fixed point and free of any order.  `height_field_mesh` and `fan_mesh` build
+the large meshes of the tests: more triangles than one sweep of the maximum kernel, and 100 000 triangles on one vertex.
 """
 import numpy as np
 
@@ -21,6 +22,39 @@ def vertex_normals(vertices, triangles, dtype=np.float32):
     bad = ~(np.isfinite(length) & (length > 0))
     out[bad] = (0.0, 0.0, 1.0)
     return out.astype(dtype)
+
+
+def cross_products(vertices, triangles):
+    """(T, 3) float64: (v_b - v_a) x (v_c - v_a) of every triangle, from the float32 vertices."""
+    v = np.asarray(vertices, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        return np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+
+
+def height_field_mesh(n, seed=0):
+    """An n x n grid of unit spacing with seeded heights in [0, 0.3): (vertices (n^2, 3) float32, triangles (2 (n - 1)^2, 3)
+    int32), two triangles per square in row order, wound so that the normals point to +z.  The last two triangles are
+    (n^2 - n - 2, n^2 - 1, n^2 - n - 1) and (n^2 - n - 2, n^2 - 2, n^2 - 1): the corner vertex n^2 - 1 belongs to them and to
+    no other."""
+    rs = np.random.RandomState(seed)
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    v = np.stack([i, j, rs.uniform(0, 0.3, (n, n))], -1).reshape(-1, 3).astype(np.float32)
+    a = (i[:-1, :-1] * n + j[:-1, :-1]).reshape(-1)
+    lower = np.stack([a, a + n, a + n + 1], 1)          # (i, j), (i + 1, j), (i + 1, j + 1)
+    upper = np.stack([a, a + n + 1, a + 1], 1)          # (i, j), (i + 1, j + 1), (i, j + 1)
+    t = np.stack([upper, lower], 1).reshape(-1, 3).astype(np.int32)
+    return v, t
+
+
+def fan_mesh(n_triangles, radius=1.0, height=0.25):
+    """A closed fan: hub 0 at (0, 0, height), n_triangles rim vertices on the circle of `radius` in z = 0, triangle k =
+    (0, 1 + k, 1 + (k + 1) % n): every triangle holds the hub, all are congruent up to float32 rounding of the rim."""
+    k = np.arange(n_triangles)
+    ang = 2.0 * np.pi * k / n_triangles
+    v = np.concatenate([[[0.0, 0.0, height]], np.stack([radius * np.cos(ang), radius * np.sin(ang), 0 * ang], 1)], 0).astype(np.float32)
+    t = np.stack([0 * k, 1 + k, 1 + (k + 1) % n_triangles], 1).astype(np.int32)
+    return v, t
 
 
 def normal_rays_torch(vertices, normals, near, far, near_t=1.0):

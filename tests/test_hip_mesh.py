@@ -2,7 +2,10 @@
 construction, the density grid against the reference's volume (fixture G20, tests/golden/make_golden_mesh.py), marching
 cubes against the cell-loop restatement of tests/mesh_ref.py, manifold properties of closed surfaces, the largest
 component against a numpy union-find, the colour fusion against a float64 restatement and the reference's opacities,
-and the whole chain down to a PLY file.
+and the whole chain down to a PLY file.  Sections 8 to 10 take the kernels to the edges of their launch geometry: blocks
+filled to the 768 vertices the count kernel packs, more than 65 535 blocks, strides of 70 001 points, non-finite
+densities; components of renumbered meshes, of strips a million triangles long and of triangle arrays with indices out
+of range; the projection on images one pixel wide or high.  Every one of those cases asserts that it reaches its edge.
 
 Bars.  sigma: the project's 1e-4 * max(1, max|sigma_ref|) (tests/test_hip_parity.py), raised to 4 x the fixture's own
 fp32-vs-fp64 difference if that is larger (FX.tolerance's rule); the inside mask must agree wherever the reference is
@@ -400,3 +403,337 @@ def test_extract_mesh_script(tmp_path):
     from mirror_nerf_amd import mesh
     v, t, c = mesh.read_ply(out)
     assert len(t) > 20000 and t.max() < len(v) and c is None
+
+
+# ----------------------------------------------------------------------------------------------- 8. marching cubes at its edges
+MC_BLOCK = 256        # points per block of the marching-cubes kernels
+GUARD = 16
+
+
+def _mc_block_counts(vol, thr):
+    """mnrf_mc_count alone: the (blocks, 2) int32 [vertices, triangles] per block, written inside a buffer of sentinels."""
+    from mirror_nerf_amd import _lib
+    L = _lib.lib()
+    dv = torch.from_numpy(np.ascontiguousarray(vol, dtype=np.float32)).to(DEV)
+    nx, ny, nz = vol.shape
+    blocks = int(L.mnrf_mc_blocks(nx, ny, nz))
+    assert blocks == (vol.size + MC_BLOCK - 1) // MC_BLOCK
+    buf = torch.full((GUARD + blocks + GUARD, 2), -7, dtype=torch.int32, device=DEV)
+    with torch.cuda.device(DEV):
+        _lib.check(L.mnrf_mc_count(_lib.ptr(dv), nx, ny, nz, float(thr), _lib.ptr(buf[GUARD:GUARD + blocks]), _lib.stream()), "mnrf_mc_count")
+    got = buf.cpu().numpy()
+    assert (got[:GUARD] == -7).all() and (got[GUARD + blocks:] == -7).all()
+    return got[GUARD:GUARD + blocks]
+
+
+def _checker(shape):
+    I, J, K = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+    return ((I + J + K) % 2).astype(np.float32)
+
+
+def _profile_volume(shape, seed):
+    """A seeded smooth profile along the long axis plus a small dependence on the two short ones: crossings of all three
+    edge kinds, a few thousand of them."""
+    rs = np.random.RandomState(seed)
+    axis = int(np.argmax(shape))
+    s = np.arange(shape[axis], dtype=np.float64)
+    f = sum(rs.uniform(0.5, 1) * np.sin(s * 2 * np.pi / rs.uniform(40, 90) + rs.uniform(0, 6.28)) for _ in range(3))
+    grid = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+    a, b = [g for i, g in enumerate(grid) if i != axis]
+    return (f[tuple(slice(None) if i == axis else None for i in range(3))] + 0.21 * a - 0.13 * b).astype(np.float32)
+
+
+@pytest.mark.parametrize("name", sorted(VOLUMES) + ["checker_rows", "checker_planes"])
+def test_block_counts_match_restatement(name, table):
+    """What mc_count_kernel leaves per block -- vertices in the low half of one scanned word, triangles in the high half --
+    against numpy, block by block.  The checkerboards cross every grid edge: (3, 3, 600) keeps whole blocks inside one z-row,
+    where a block reaches the 768 vertices (3 a point) the packing is sized for; (9, 10, 31) has rows of 31 and planes of 310
+    points, so every block holds eight rows or more and most hold parts of two planes."""
+    if name.startswith("checker"):
+        shape = (3, 3, 600) if name == "checker_rows" else (9, 10, 31)
+        vol, thr = _checker(shape), 0.5
+    else:
+        make, thr = VOLUMES[name]
+        vol = make()
+    got = _mc_block_counts(vol, thr)
+    want = MR.block_counts(vol, thr, table, MC_BLOCK)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    if name == "checker_rows":
+        assert got[:, 0].max() == 3 * MC_BLOCK == 768 and (got[:, 0] == 768).sum() >= 2 and got[:, 1].max() >= 2 * MC_BLOCK
+    if name == "checker_planes":
+        first, last = np.arange(len(got)) * MC_BLOCK, np.minimum(np.arange(len(got)) * MC_BLOCK + MC_BLOCK, vol.size) - 1
+        rows = last // 31 - first // 31 + 1
+        assert len(got) == 11 and rows[:-1].min() >= 8 and (last // 310 != first // 310).sum() >= 6
+        assert got[:, 0].sum() == MR.crossed_edges(vol, thr) == 8 * 10 * 31 + 9 * 9 * 31 + 9 * 10 * 30
+    if name.startswith("checker"):      # and the whole mesh
+        _compare_with_restatement(vol, thr, table)
+
+
+def _far_corner_volume():
+    """257^3, negative everywhere but in a lens in the plane i = 255: 12 cells of radius along j and k, less than one along
+    i.  Only the planes i >= 254 lie past block 65 535 (65 536 * 256 points are 254.01 planes), so a closed surface that
+    keeps all its work there is one point thick."""
+    N = 257
+    vol = np.full((N, N, N), -1.0, dtype=np.float32)
+    i, J, K = np.meshgrid(np.arange(250, N), np.arange(N), np.arange(N), indexing="ij")
+    vol[250:] = 1.0 - np.sqrt(((i - 255.1) / 0.8) ** 2 + ((J - 236.3) / 12.0) ** 2 + ((K - 229.6) / 12.0) ** 2)
+    return vol
+
+
+def test_marching_cubes_past_65535_blocks(table):
+    """66 308 blocks (257^3 = 66 307 * 256 + 1 points); every active point lies in a block with an index above 65 535.
+    Against the cropped restatement (tests/test_mesh_cpu.py shows it equal to the uncropped one).  Measured next to an
+    MI355X: the whole test 0.43 s, most of it numpy over the 17 M points."""
+    from mirror_nerf_amd import _lib
+    vol, thr = _far_corner_volume(), 0.0
+    assert int(_lib.lib().mnrf_mc_blocks(*vol.shape)) == 66308 > 65535
+    # the reach: the lowest flat index of a point that owns a crossed edge or an active cell
+    ins = vol >= thr
+    owner = np.zeros(vol.shape, dtype=bool)
+    owner[:-1] |= ins[1:] != ins[:-1]
+    owner[:, :-1] |= ins[:, 1:] != ins[:, :-1]
+    owner[:, :, :-1] |= ins[:, :, 1:] != ins[:, :, :-1]
+    cases = MR.cell_cases(vol, thr)
+    owner[:-1, :-1, :-1] |= (cases != 0) & (cases != 255)
+    lowest = int(np.flatnonzero(owner.reshape(-1))[0])
+    assert lowest >= 65536 * MC_BLOCK and owner.sum() > 900
+    v, t = _mc(vol, thr)
+    rv, rt = MR.marching_cubes_cropped(vol, thr, table)
+    assert v.shape[0] == rv.shape[0] == MR.crossed_edges(vol, thr) and t.shape[0] == rt.shape[0] > 1000
+    vn, tn = v.cpu().numpy(), t.cpu().numpy()
+    gv, gt = MR.canonical(vn, tn)
+    wv, wt = MR.canonical(rv, rt)
+    ulp = np.spacing(np.float32(256.0))
+    assert float(np.abs(gv.astype(np.float64) - wv).max()) <= 2 * ulp and np.array_equal(gt, wt)
+    assert MR.is_closed_oriented(tn) and MR.euler_characteristic(len(vn), tn) == 2 and MR.signed_volume(vn, tn) > 0
+    assert vn[:, 0].min() > 254 and tn.min() == 0 and tn.max() == len(vn) - 1
+    v2, t2 = _mc(vol, thr)
+    assert torch.equal(v, v2) and torch.equal(t, t2)
+    bc = _mc_block_counts(vol, thr)
+    assert not bc[:65536].any() and bc[65536:, 0].sum() == len(vn) and bc[65536:, 1].sum() == len(tn)
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 70001), (70001, 2, 2)])
+def test_marching_cubes_long_strides(shape, table):
+    """One long axis: along z the row stride nz and the plane stride ny * nz are 70 001 and 140 002 points, far beyond a
+    block and beyond 65 535; along x the volume is 70 001 planes of four points, 64 planes a block."""
+    vol, thr = _profile_volume(shape, seed=sum(shape)), 0.0
+    if shape[2] > 2:
+        assert shape[2] > 65535 and shape[1] * shape[2] > 65535
+    else:
+        assert shape[0] > 65535 and shape[1] * shape[2] == 4
+    ins = vol >= thr
+    kinds = [(ins[1:] != ins[:-1]).sum(), (ins[:, 1:] != ins[:, :-1]).sum(), (ins[:, :, 1:] != ins[:, :, :-1]).sum()]
+    assert min(kinds) > 500, kinds
+    v, t = _compare_with_restatement(vol, thr, table)
+    assert t.shape[0] > 2000
+    assert np.array_equal(_mc_block_counts(vol, thr), MR.block_counts(vol, thr, table, MC_BLOCK))
+
+
+def test_marching_cubes_non_finite_densities(table):
+    """A handful of NaN (outside, as under >=) and +inf (inside) values next to the surface.  Positions next to them may be
+    NaN, so the topology is compared: the vertex count, every index in range, and the triangle array under the vertex
+    numbering the kernels document (crossed edges in the flat order of their lower end, +x, +y, +z within a point)."""
+    vol, thr = _smooth_random().copy(), 0.1
+    rs = np.random.RandomState(8)
+    ins = vol >= thr
+    edge = np.zeros(vol.shape, dtype=bool)       # interior points with a neighbour on the other side
+    edge[1:-1, 1:-1, 1:-1] = ((ins[1:-1, 1:-1, 1:-1] != ins[2:, 1:-1, 1:-1]) | (ins[1:-1, 1:-1, 1:-1] != ins[1:-1, 2:, 1:-1])
+                              | (ins[1:-1, 1:-1, 1:-1] != ins[1:-1, 1:-1, 2:]))
+    inside, outside = np.argwhere(edge & ins), np.argwhere(edge & ~ins)
+    for p in inside[rs.choice(len(inside), 4, replace=False)]:
+        vol[tuple(p)] = np.nan
+    for p in outside[rs.choice(len(outside), 4, replace=False)]:
+        vol[tuple(p)] = np.inf
+    assert np.isnan(vol).sum() == 4 and np.isposinf(vol).sum() == 4
+    v, t = _mc(vol, thr)
+    V = v.shape[0]
+    vn, tn = v.cpu().numpy(), t.cpu().numpy()
+    assert V == MR.crossed_edges(vol, thr) != MR.crossed_edges(_smooth_random(), thr)
+    assert tn.min() >= 0 and tn.max() < V and len(np.unique(tn)) == V
+    rv, rt, edges = MR.marching_cubes(vol, thr, table, return_edges=True)
+    rank = MR.flat_edge_rank(edges, vol.shape)
+    assert len(rv) == V and len(rt) == len(tn)
+    assert np.array_equal(MR.canonical_triangles(tn), MR.canonical_triangles(rank[rt]))
+    # the positions: NaN at the same vertices (there are some), elsewhere the usual 2 ulp
+    want = np.empty_like(rv)
+    want[rank] = rv
+    assert np.isnan(want).any() and np.array_equal(np.isnan(vn), np.isnan(want))
+    ok = ~np.isnan(want)
+    assert float(np.abs(vn[ok].astype(np.float64) - want[ok]).max()) <= 2 * np.spacing(np.float32(max(vol.shape) - 1))
+    v2, t2 = _mc(vol, thr)
+    assert v.cpu().numpy().tobytes() == v2.cpu().numpy().tobytes() and torch.equal(t, t2)
+
+
+# ----------------------------------------------------------------------------------------------- 9. components at their edges
+def _mean_edge_span(t):
+    t = np.asarray(t, dtype=np.int64)
+    return float(np.abs(t - np.roll(t, 1, 1)).mean())
+
+
+@pytest.mark.parametrize("name", ["torus", "two_spheres", "smooth_random", "g20"])
+def test_components_of_renumbered_meshes(name, g20):
+    """The hook rounds have only seen marching cubes' flat order, where neighbours have neighbouring numbers.  Here the same
+    meshes under a seeded random renumbering of the vertices, a shuffled triangle array and rotated corners."""
+    from mirror_nerf_amd import mesh
+    if name == "g20":
+        vol, thr = np.maximum(g20.outputs["sigma"], 0), g20.meta["threshold"]
+    else:
+        make, thr = VOLUMES[name]
+        vol = make()
+    v, t = _mc(vol, thr)
+    vn, tn = v.cpu().numpy(), t.cpu().numpy()
+    V = len(vn)
+    perm, rt = MR.renumber(V, tn, seed=len(name))
+    nv = np.empty_like(vn)
+    nv[perm] = vn
+    assert _mean_edge_span(rt) > V / 5 > 4 * _mean_edge_span(tn)      # neighbours are far apart now
+    dt, dv = torch.from_numpy(rt).to(DEV), torch.from_numpy(nv).to(DEV)
+    want = MR.union_find_labels(V, rt)
+    labels = mesh.component_labels(V, dt).cpu().numpy()
+    assert np.array_equal(labels, want)
+    assert len(np.unique(want)) == len(np.unique(MR.union_find_labels(V, tn)))
+    lv, lt, info = mesh.largest_component(dv, dt, return_info=True)
+    wv, wt, n_comp, largest = MR.largest_component(nv, rt)
+    assert info == {"n_components": n_comp, "largest_triangles": largest}
+    assert np.array_equal(lt.cpu().numpy(), wt) and np.array_equal(lv.cpu().numpy(), wv)
+
+
+STRIP = 1000000
+
+
+@pytest.mark.parametrize("numbering", ["ascending", "descending", "shuffled"])
+def test_components_of_a_long_strip(numbering):
+    """One strip of 1 000 000 triangles (V = 1 000 002 > 65 535): a chain as long as the mesh, under three numberings; the
+    one component carries label 0.  Every round costs a host synchronisation.  Measured on an MI355X for component_labels:
+    ascending 0.017 s (the first launch of the process), descending 0.002 s, shuffled 0.005 s; a tenth of the length took
+    0.005 / 0.001 / 0.001 s, so the strip is a million long and not the 70 000 that would do."""
+    import time
+    from mirror_nerf_amd import mesh
+    strip = MR.triangle_strip(STRIP)
+    V = STRIP + 2
+    assert V > 65535
+    tri = {"ascending": strip, "descending": (V - 1 - strip).astype(np.int32), "shuffled": MR.renumber(V, strip, 3)[1]}[numbering]
+    dt = torch.from_numpy(np.ascontiguousarray(tri)).to(DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    labels = mesh.component_labels(V, dt)
+    torch.cuda.synchronize()
+    print(f"component_labels, strip of {STRIP} triangles, {numbering}: {time.perf_counter() - t0:.3f} s")
+    assert labels.shape == (V,) and not bool(labels.any())
+    v = torch.arange(V, dtype=torch.float32, device=DEV)[:, None].repeat(1, 3).contiguous()
+    lv, lt, info = mesh.largest_component(v, dt, return_info=True)
+    assert info == {"n_components": 1, "largest_triangles": STRIP} and torch.equal(lv, v) and torch.equal(lt, dt)
+
+
+def test_components_of_two_interleaved_strips():
+    """Two strips of 35 001 triangles over the even and the odd vertices (V = 70 006): two labels, 0 and 1, and between the
+    two equal components the documented tie rule: the lowest label wins."""
+    from mirror_nerf_amd import mesh
+    T = 35001
+    V = 2 * (T + 2)
+    rs = np.random.RandomState(4)
+    tri = np.concatenate([MR.triangle_strip(T, 0, 2), MR.triangle_strip(T, 1, 2)])[rs.permutation(2 * T)]
+    assert V > 65535 and tri.max() == V - 1
+    dt = torch.from_numpy(np.ascontiguousarray(tri)).to(DEV)
+    labels = mesh.component_labels(V, dt).cpu().numpy()
+    assert np.array_equal(labels, np.arange(V) % 2) and np.array_equal(labels, MR.union_find_labels(V, tri))
+    v = torch.arange(V, dtype=torch.float32, device=DEV)[:, None].repeat(1, 3).contiguous()
+    lv, lt, info = mesh.largest_component(v, dt, return_info=True)
+    wv, wt, n_comp, largest = MR.largest_component(v.cpu().numpy(), tri)
+    assert info == {"n_components": 2, "largest_triangles": T} == {"n_components": n_comp, "largest_triangles": largest}
+    assert np.array_equal(lv.cpu().numpy()[:, 0], np.arange(0, V, 2)) and np.array_equal(lt.cpu().numpy(), wt)
+
+
+def test_component_kernels_refuse_indices_out_of_range():
+    """mnrf_cc_step and mnrf_cc_count on a triangle array in which rows hold -1, V, V + 5, 2^31 - 1 and -2^31 in every
+    column, at the start, across a block edge and at the end: those rows are skipped by both kernels, the other rows give
+    the labels and counts of the restatement on the valid rows alone, and nothing is written outside labels[0, V) and
+    counts[0, V).  The rows whose first index is good and whose second or third is not are what caught cc_count_kernel
+    looking at the first index only: it counted triangles the hook kernel had refused (167 for 165 under label 0)."""
+    from mirror_nerf_amd import _lib
+    L = _lib.lib()
+    rs = np.random.RandomState(6)
+    V, T = 300, 700
+    # four groups of vertices that never mix, so that there are several components
+    group = rs.randint(0, 4, T)
+    tri = (group[:, None] * 75 + rs.randint(0, 75, (T, 3))).astype(np.int64)
+    bad_values = [-1, V, V + 5, 2 ** 31 - 1, -2 ** 31]
+    bad_rows = [0, 1, 2, 254, 255, 256, 257, 258, 400, 401, 402, 403, T - 3, T - 2, T - 1]
+    for k, r in enumerate(bad_rows):
+        tri[r, k % 3] = bad_values[k % 5]
+    tri = tri.astype(np.int32)
+    valid = ((tri >= 0) & (tri < V)).all(1)
+    assert (~valid).sum() == len(bad_rows) and all(((tri[~valid] == b).any()) for b in bad_values)
+    assert all((~((tri[~valid][:, c] >= 0) & (tri[~valid][:, c] < V))).any() for c in range(3))      # every column holds a bad index
+    assert (((tri[~valid][:, 0] >= 0) & (tri[~valid][:, 0] < V))).any()      # and some bad rows start with a good one
+    want = MR.union_find_labels(V, tri[valid])
+    want_counts = np.bincount(want[tri[valid][:, 0]], minlength=V)
+    dt = torch.from_numpy(tri).to(DEV)
+    labels = torch.full((GUARD + V + GUARD,), -99, dtype=torch.int32, device=DEV)
+    counts = torch.full((GUARD + V + GUARD,), -99, dtype=torch.int32, device=DEV)
+    counts[GUARD:GUARD + V] = 0
+    changed = torch.zeros(1, dtype=torch.int32, device=DEV)
+    with torch.cuda.device(DEV):
+        lab, cnt = labels[GUARD:GUARD + V], counts[GUARD:GUARD + V]
+        _lib.check(L.mnrf_cc_init(_lib.ptr(lab), V, _lib.stream()), "mnrf_cc_init")
+        for _ in range(V + 2):
+            changed.zero_()
+            _lib.check(L.mnrf_cc_step(_lib.ptr(dt), T, _lib.ptr(lab), V, _lib.ptr(changed), _lib.stream()), "mnrf_cc_step")
+            if int(changed.item()) == 0:
+                break
+        else:
+            raise AssertionError("no fixed point")
+        _lib.check(L.mnrf_cc_count(_lib.ptr(dt), T, _lib.ptr(lab), V, _lib.ptr(cnt), _lib.stream()), "mnrf_cc_count")
+    got, got_counts = labels.cpu().numpy(), counts.cpu().numpy()
+    assert (got[:GUARD] == -99).all() and (got[GUARD + V:] == -99).all()
+    assert (got_counts[:GUARD] == -99).all() and (got_counts[GUARD + V:] == -99).all()
+    assert np.array_equal(got[GUARD:GUARD + V], want) and len(np.unique(want[tri[valid].reshape(-1)])) == 4
+    assert np.array_equal(got_counts[GUARD:GUARD + V], want_counts) and want_counts.sum() == valid.sum()
+
+
+# ----------------------------------------------------------------------------------------------- 10. colour projection at its edges
+@pytest.mark.parametrize("H,W,V", [(1, 53, 257), (37, 1, 257), (1, 1, 257), (37, 53, 65537)])
+def test_projection_on_one_pixel_axes_and_the_last_pixel(H, W, V):
+    """Images of one row, one column and one pixel; 257 and 65 537 vertices (one past a block, one past 65 536); vertex 0
+    reaches the last column and the last row by a few float32 steps and is clamped onto them (x1 = W, y1 = H are clamped
+    too), vertex 1 lies far outside the same corner, vertex 2 stops a few steps short of it.  The bars are those of
+    test_projection_and_sampling_match_float64."""
+    from mirror_nerf_amd import mesh
+    rs = np.random.RandomState(H * 1000 + W)
+    focal, near, z = 41.3, 0.05, -2.0
+    pose = np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)
+    f32 = float(np.float32(focal))
+    depth = -z + 1e-5
+    edge_x = ((W - 1) * depth + 0.5 * W * z) / f32             # projects onto column W - 1
+    edge_y = -((H - 1) * depth + 0.5 * H * z) / f32            # projects onto row H - 1
+    span = 1.4 * max(abs(edge_x), abs(edge_y), 0.1)
+    verts = np.stack([rs.uniform(-span, span, V), rs.uniform(-span, span, V), rs.uniform(-3.0, -1.0, V)], 1).astype(np.float32)
+
+    up = lambda x: np.nextafter(np.float32(x), np.float32(np.inf))      # noqa: E731
+    down = lambda x: np.nextafter(np.float32(x), np.float32(-np.inf))   # noqa: E731
+    xa, xb, ya, yb = np.float32(edge_x), np.float32(edge_x), np.float32(edge_y), np.float32(edge_y)
+    for _ in range(8):      # column grows with x, row grows as y falls
+        xa, xb, ya, yb = up(xa), down(xb), down(ya), up(yb)
+    verts[0] = [xa, ya, z]
+    verts[1] = [edge_x + 50.0, edge_y - 50.0, z]
+    verts[2] = [xb, yb, z]
+    image = rs.randint(0, 256, (H, W, 3)).astype(np.uint8)
+    wc, wd, pix, wr = MR.project_view(verts, image, pose, focal, near)
+    assert pix[0].tolist() == [W - 1, H - 1] and pix[1].tolist() == [W - 1, H - 1]
+    if W > 1:
+        assert W - 1 - 1e-3 < pix[2, 0] < W - 1
+    if H > 1:
+        assert H - 1 - 1e-3 < pix[2, 1] < H - 1
+    assert (pix[:, 0] == 0).sum() > V // 20 and (pix[:, 1] == 0).sum() > V // 20      # clipped on the other side too
+    colors, depth_, rays = mesh.project_view(torch.from_numpy(verts).to(DEV), torch.from_numpy(image).to(DEV), pose, focal, near)
+    assert colors.shape == (V, 3) and depth_.shape == (V,) and rays.shape == (V, 8)
+    got = colors.cpu().numpy()
+    assert (np.abs(got - wc) <= 1e-5 * np.maximum(1.0, np.abs(wc))).all()
+    assert np.array_equal(got[:2], np.tile(image[H - 1, W - 1].astype(np.float32), (2, 1)))
+    if H == 1 and W == 1:
+        assert np.array_equal(got, np.tile(image[0, 0].astype(np.float32), (V, 1)))
+    np.testing.assert_allclose(depth_.cpu().numpy(), wd, rtol=1e-12, atol=1e-12)
+    r = rays.cpu().numpy()
+    np.testing.assert_allclose(r[:, :7], wr[:, :7], rtol=0, atol=2e-6)
+    np.testing.assert_allclose(r[:, 7], wd, rtol=1e-7)

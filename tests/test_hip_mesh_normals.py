@@ -179,6 +179,107 @@ def test_vertex_normals_hand_made_and_degenerate():
         assert np.abs(got.astype(np.float64) - NR.vertex_normals(vv, t, dtype=np.float64)).max() <= BAR, scale
 
 
+# ----------------------------------------------------------------------------------------------- 1b. past one sweep of the maximum
+SWEEP = 1024 * 256      # triangles per pass of vn_max_kernel's grid-stride loop
+
+
+@pytest.fixture(scope="module")
+def field():
+    """The 400 x 400 height field (318 402 triangles), flat around its last corner: built once, copied by the tests."""
+    v, t = NR.height_field_mesh(400)
+    corner = len(v) - 1
+    v[[corner, corner - 1, corner - 400, corner - 401], 2] = 0.0
+    return v, t
+
+
+def _normals(v, t):
+    from mirror_nerf_amd import mesh
+    return mesh.vertex_normals(_dev(v, np.float32), _dev(t, np.int32))
+
+
+def _count_bits(T):
+    return int(3 * T).bit_length()      # 3 T < 2^count_bits, as mnrf_vertex_normals counts them
+
+
+def test_vertex_normals_maximum_in_the_second_sweep(field):
+    """The corner vertex of the last but one triangle (index 318 400 >= 262 144) is pulled out by 0.9 * 2^20 grid steps: that
+    triangle's cross product is 0.9 * 2^20 times the largest of all the others, and only the second pass of vn_max_kernel's
+    loop sees it.  With M < 2^20 and 3 T < 2^20 the fixed-point step is 2^-22, so a vertex with m triangles is at most
+    m * 2^-23 off on a sum of length >= m: 1.2e-7 and one float32 rounding, inside BAR at every vertex.
+    A maximum lost in the later pass would make the step 2^20 times finer; at this ratio the sums still fit 64 bits, so the
+    same mesh is run again with the corner 2^23 steps out, where a step taken from the first pass alone saturates the
+    conversion of that triangle: its three vertices are then checked (the others are 2^-18 coarse there, by design).
+    Measured on an MI355X: max |n - n_ref| 1.19e-7 over the 160 000 vertices."""
+    v, t = field[0].copy(), field[1]
+    T, corner = len(t), len(v) - 1
+    v[corner, 0] += np.float32(0.9 * 2 ** 20)
+    big = np.abs(NR.cross_products(v, t)).max(1)
+    k = int(np.argmax(big))
+    ratio = big[k] / np.delete(big, k).max()
+    assert k == T - 2 >= SWEEP and 0.85 * 2 ** 20 < ratio < 2 ** 20 and _count_bits(T) == 20 and big[k] < 2 ** 20
+    n = _normals(v, t)
+    want = NR.vertex_normals(v, t, dtype=np.float64)
+    err = float(np.abs(n.cpu().numpy().astype(np.float64) - want).max())
+    print(f"[second sweep] V = {len(v)}, T = {T}: max |n - n_ref| = {err:.3e} (bar {BAR:.0e})")
+    assert err <= BAR
+    # any order of the triangle array gives the same bits ...
+    rs = np.random.RandomState(5)
+    assert torch.equal(n, _normals(v, t[rs.permutation(T)]))
+    # ... also the one with the large triangle at index 0, in the first sweep: the later sweep was seen, not luck
+    first = np.concatenate([t[k:k + 1], t[:k], t[k + 1:]])
+    assert int(np.argmax(np.abs(NR.cross_products(v, first)).max(1))) == 0
+    assert torch.equal(n, _normals(v, first))
+    # the corner 2^23 steps out: the large triangle's vertices
+    v[corner, 0] = np.float32(399 + 2 ** 23)
+    big = np.abs(NR.cross_products(v, t)).max(1)
+    assert int(np.argmax(big)) == k and big[k] / np.delete(big, k).max() > 2 ** 23 > 2 ** (_count_bits(T) + 2)
+    far = _normals(v, t)
+    want = NR.vertex_normals(v, t, dtype=np.float64)
+    assert float(np.abs(far.cpu().numpy().astype(np.float64) - want)[t[k]].max()) <= BAR and want[t[k], 2].min() > 0.999999
+    assert torch.equal(far, _normals(v, first))
+
+
+def test_vertex_normals_fan_on_one_vertex():
+    """100 000 congruent triangles around one hub: every one of them adds a cross product close to the mesh's largest to the
+    hub's three accumulators -- the largest sum the bound |sum| < 2^62 has to hold (here 2^58.7), all of it on one address.
+    Measured on an MI355X: the hub is (0, 0, 1) exactly, the rim within 1.9e-8."""
+    T = 100000
+    v, t = NR.fan_mesh(T)
+    c = NR.cross_products(v, t)
+    big = np.abs(c).max(1)
+    assert np.bincount(t.reshape(-1))[0] == T and big.min() > 0.99 * big.max() and (c[:, 2] == big).all()
+    _, e = np.frexp(big.max())
+    steps = c[:, 2].sum() * 2.0 ** (62 - int(e) - _count_bits(T))      # the hub's z accumulator, in fixed-point steps
+    assert 2.0 ** 58 < steps < 2.0 ** 62
+    n = _normals(v, t)
+    want = NR.vertex_normals(v, t, dtype=np.float64)
+    got = n.cpu().numpy().astype(np.float64)
+    err_hub, err_rim = float(np.abs(got[0] - want[0]).max()), float(np.abs(got[1:] - want[1:]).max())
+    print(f"[fan] T = {T}: hub {got[0].tolist()}, |n - n_ref| hub {err_hub:.3e}, rim {err_rim:.3e} (bar {BAR:.0e})")
+    assert err_hub <= BAR and err_rim <= BAR and got[0, 2] > 0.999999
+    rs = np.random.RandomState(6)
+    assert torch.equal(n, _normals(v, t[rs.permutation(T)]))
+
+
+def test_vertex_normals_non_finite_corner_in_the_second_sweep(field):
+    """One more triangle at index 318 402 (second sweep) with a vertex at infinity: its three vertices get (0, 0, 1), every
+    other vertex is what the mesh without that triangle gives."""
+    v, t = field
+    V, T = len(v), len(t)
+    a = 200 * 400 + 200
+    v2 = np.concatenate([v, np.float32([[np.inf, 0.0, 0.0]])])
+    t2 = np.concatenate([t, np.int32([[a, a + 1, V]])])
+    assert len(t2) - 1 >= SWEEP and not np.isfinite(NR.cross_products(v2, t2)[-1]).all()
+    got = _normals(v2, t2).cpu().numpy()
+    assert np.array_equal(got[[a, a + 1, V]], np.tile(np.float32([0, 0, 1]), (3, 1)))
+    without = NR.vertex_normals(v2, t, dtype=np.float64)
+    others = np.ones(V + 1, dtype=bool)
+    others[[a, a + 1, V]] = False
+    assert float(np.abs(got.astype(np.float64) - without)[others].max()) <= BAR
+    assert np.abs(without[[a, a + 1]] - [0, 0, 1]).max() > 1e-3      # they had normals of their own
+    assert np.array_equal(NR.vertex_normals(v2, t2)[[a, a + 1, V]], np.tile(np.float32([0, 0, 1]), (3, 1)))      # as the restatement
+
+
 # ----------------------------------------------------------------------------------------------- 2. direction
 @pytest.mark.parametrize("exact_spacing", [False, True])
 @pytest.mark.parametrize("name", ["sphere", "torus"])

@@ -11,6 +11,8 @@
     costs, and no tensor needs a bar of its own: test_float32_floor_stays_under_a_quarter_of_the_bars asserts that every floor stays
     below a quarter of its bar, so a case added later that does not must be given 4x its measured floor here, by name, with the
     reason.
+  * the PSNR / MSE reduction: a float32 numpy emulation of the two kernels' order of summation (loss_ref.mse_emulate) against the
+    float64 mean on the cases of tests/test_hip_psnr_fp64.py, inside the bar derived from that order (loss_ref.mse_bar).
 """
 import json
 
@@ -140,6 +142,52 @@ def test_empty_selections_are_nan_with_zero_gradient():
         assert not g[k].any(), k
     g = R.case("empty_stage_pred_high")["ref"]["grads"]
     assert not g["rgb_coarse"].any() and not g["rgb_fine"].any()
+
+
+# ------------------------------------------------------------------------------------------------------------------ PSNR and MSE
+def test_psnr_bar_counts_the_roundings_of_the_kernel():
+    """The geometry the bar is built from, and the reach of the cases: below one wave, one block and one pass; two, four and 65
+    passes; masks whose selection starts in a later pass."""
+    assert R.mse_geometry(1) == (1, 1) and R.mse_geometry(256) == (1, 1) and R.mse_geometry(257) == (2, 1)
+    assert R.mse_geometry(R.MSE_SWEEP) == (1024, 1) and R.mse_geometry(R.MSE_SWEEP + 1) == (1024, 2)
+    assert R.mse_geometry(3 * R.MSE_SWEEP + 5) == (1024, 4) and R.mse_geometry(2 ** 24 + 257) == (1024, 65)
+    assert R.mse_bar(1) == 13 * 2.0 ** -24 and R.mse_bar(R.MSE_SWEEP + 1) == (3 + 1 + 9 + 1023 + 1) * 2.0 ** -24
+    assert float(np.float32(2 ** 24 + 257)) != 2 ** 24 + 257      # the count of the largest case is not a float32
+    late = R.psnr_case("mask_late_passes")
+    first = int(np.nonzero(late["sel"])[0][0])
+    assert R.MSE_SWEEP <= first and int(np.nonzero(late["sel"])[0][-1]) < 3 * R.MSE_SWEEP and late["ref"][2] > 100000
+    last = R.psnr_case("mask_last_only")
+    assert last["ref"][2] == 1 and last["sel"][-1] and last["sel"].size > 3 * R.MSE_SWEEP
+    for name, per in (("mask_pixel3", 3), ("mask_pixel4", 4), ("mask_pixel5", 5)):
+        c = R.psnr_case(name)
+        assert c["per"] == per and c["a"].size % per == 0 and c["mask"].size == c["a"].size // per and 0 < c["ref"][2] < c["a"].size
+    assert R.MSE_TPB % 3 and R.MSE_TPB % 5      # a pixel of 3 or 5 channels straddles block edges
+    one = R.psnr_case("one_element_2^-20")
+    assert one["ref"][0] == 2.0 ** -40 / 1000 and float(np.float32(one["ref"][0])) > 0
+
+
+@pytest.mark.parametrize("name", list(R.PSNR_CASES))
+def test_float32_emulation_of_the_mse_kernels_stays_inside_the_derived_bar(name):
+    """The kernels' order of summation in float32 numpy against the float64 mean: the derived bar is attainable by the
+    arithmetic it was derived for, without reference to the kernel.  Largest fractions of the bar over the cases: MSE 0.151
+    (size_255), PSNR 0.323 (size_1, numpy's log10), count 0.001 (2^24 + 257: the float32 count; exact in every other case)."""
+    c = R.psnr_case(name)
+    partials, out = R.mse_emulate(c["a"], c["b"], c["sel"])
+    blocks, _ = R.mse_geometry(c["a"].size)
+    assert partials.shape == (blocks, 2) and out.dtype == np.float32
+    fm, fp, fc = R.psnr_errors(c, out)
+    print(f"{name}: n = {c['a'].size}, mse {float(out[0]):.6e} (fp64 {c['ref'][0]:.6e}), errors as fractions of the bar: "
+          f"mse {fm:.3f}, psnr {fp:.3f}, count {fc:.3f}")
+    assert fm <= 1 and fp <= 1 and fc <= 1
+    if c["a"].size < 2 ** 24:
+        assert float(out[2]) == c["ref"][2]
+    if name == "mask_all_true":      # an all-true mask selects what no mask selects: the same bits
+        _, plain = R.mse_emulate(c["a"], c["b"], np.ones(c["a"].size, bool))
+        assert plain.tobytes() == out.tobytes()
+    if name == "identical":
+        assert float(out[0]) == 0.0 and float(out[1]) == np.inf
+    if name == "mask_none_selected":
+        assert np.isnan(out[0]) and np.isnan(out[1]) and float(out[2]) == 0.0
 
 
 @pytest.mark.parametrize("name", ["stage_invalid_ep0", "stage_invalid_ep2"])

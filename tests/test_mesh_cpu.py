@@ -1,6 +1,8 @@
 """Mesh extraction without a GPU: the new C-ABI entry points validate their arguments, the 256-case marching-cubes table
 read through mnrf_mc_table is exhaustively consistent (crossed edges, 2-manifold patches, matching faces = no cracks,
-outward winding), PLY files round-trip, and extract_mesh's index-to-world mapping restates the reference's three lines."""
+outward winding), PLY files round-trip, and extract_mesh's index-to-world mapping restates the reference's three lines.
+The restatements the GPU tests lean on are held to plainer ones here: the cropped marching cubes to the uncropped, the
+per-block counts to a loop over points, the union-find under renumbering and on long strips, the projection on one pixel."""
 import ctypes
 import itertools
 import os
@@ -213,6 +215,133 @@ def test_table_is_what_the_generator_derives(table):
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
     assert np.array_equal(np.array(gen.table(), dtype=np.int8), table)
+
+
+# ----------------------------------------------------------------------------------------------- the restatements themselves
+def _smooth(shape, seed):
+    rs = np.random.RandomState(seed)
+    X, Y, Z = np.meshgrid(*[np.linspace(-1, 1, n) for n in shape], indexing="ij")
+    f = np.zeros(shape)
+    for _ in range(5):
+        k = rs.uniform(2, 7, 3)
+        f += rs.uniform(0.5, 1) * np.sin(k[0] * X + k[1] * Y + k[2] * Z + rs.uniform(0, 6.28))
+    return f.astype(np.float32)
+
+
+def _blob(shape, centre, r):
+    I, J, K = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+    return (r - np.sqrt((I - centre[0]) ** 2 + (J - centre[1]) ** 2 + (K - centre[2]) ** 2)).astype(np.float32)
+
+
+@pytest.mark.parametrize("name", ["blob_inside", "cut_by_boundary"])
+def test_cropped_marching_cubes_is_the_uncropped_one(name, table):
+    """marching_cubes_cropped against marching_cubes where both can run: the same vertex bits, the same triangles, in the
+    same order (so also the same canonical mesh); the crop is a strict part of the volume in one case and touches three of
+    its faces in the other."""
+    if name == "blob_inside":
+        vol, thr = _blob((21, 19, 23), (13.3, 11.6, 15.2), 3.7), 0.0
+    else:
+        vol, thr = _blob((14, 15, 13), (11.5, 12.8, 1.2), 4.4), 0.0      # cut by the faces i = 13, j = 14 and k = 0
+    box = MR.crop_box(vol, thr)
+    v, t = MR.marching_cubes(vol, thr, table)
+    cv, ct = MR.marching_cubes_cropped(vol, thr, table)
+    assert len(t) > 100 and v.tobytes() == cv.tobytes() and np.array_equal(t, ct)
+    a, b = MR.canonical(v, t), MR.canonical(cv, ct)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    size = [hi - lo for lo, hi in box]
+    if name == "blob_inside":
+        assert all(lo > 0 and hi < n for (lo, hi), n in zip(box, vol.shape)) and np.prod(size) < vol.size / 3
+        assert MR.is_closed_oriented(ct) and MR.euler_characteristic(len(cv), ct) == 2
+    else:
+        assert box[0][1] == 14 and box[1][1] == 15 and box[2][0] == 0 and box[0][0] > 0 and not MR.is_closed_oriented(ct)
+    assert MR.marching_cubes_cropped(np.full((5, 6, 7), -1.0, np.float32), 0.0, table)[1].shape == (0, 3)
+
+
+def test_block_counts_restatement(table):
+    """block_counts against the cell loop: the per-block numbers add up to the restatement's mesh, block by block they are
+    what a plain loop over the points of the block gives, and a checkerboard fills a block inside one z-row to the 768
+    vertices csrc/mnrf_mesh.hip names as the most a block can hold."""
+    one = np.array([[[1, 0], [0, 0]], [[0, 0], [0, 0]]], np.float32)
+    assert MR.block_counts(one, 0.5, table).tolist() == [[3, 1]]
+    vol = _smooth((7, 9, 11), 3)
+    bc = MR.block_counts(vol, 0.1, table, block=64)
+    v, t = MR.marching_cubes(vol, 0.1, table)
+    assert bc.shape == ((7 * 9 * 11 + 63) // 64, 2) and bc[:, 0].sum() == len(v) == MR.crossed_edges(vol, 0.1) and bc[:, 1].sum() == len(t)
+    ins = vol >= np.float32(0.1)
+    cases = MR.cell_cases(vol, 0.1)
+    want = np.zeros_like(bc)
+    for p in range(vol.size):
+        i, j, k = np.unravel_index(p, vol.shape)
+        for a, (di, dj, dk) in enumerate(((1, 0, 0), (0, 1, 0), (0, 0, 1))):
+            if i + di < 7 and j + dj < 9 and k + dk < 11 and ins[i + di, j + dj, k + dk] != ins[i, j, k]:
+                want[p // 64, 0] += 1
+        if i < 6 and j < 8 and k < 10:
+            want[p // 64, 1] += int((table[cases[i, j, k]] >= 0).sum()) // 3
+    assert np.array_equal(bc, want)
+    I, J, K = np.meshgrid(np.arange(3), np.arange(3), np.arange(600), indexing="ij")
+    checker = ((I + J + K) % 2).astype(np.float32)
+    bc = MR.block_counts(checker, 0.5, table)
+    assert bc[:, 0].max() == 768 and bc[:, 0].sum() == MR.crossed_edges(checker, 0.5) and bc[:, 1].max() <= 5 * 256
+
+
+def test_union_find_on_renumbered_and_chain_meshes():
+    """union_find_labels is independent of the numbering: a renumbered mesh has the renumbered partition, each part labelled
+    with its smallest new number; strips are one component under any numbering; and 3 * 10^5 triangles stay cheap (measured
+    0.6 s for the shuffled strip here, printed)."""
+    import time
+    rs = np.random.RandomState(0)
+    # three components: two strips and a single triangle, glued by nothing; vertex 72 is unreferenced
+    t = np.concatenate([MR.triangle_strip(40), MR.triangle_strip(25, first=42), [[70, 69, 71]]]).astype(np.int32)
+    V = 73
+    base = MR.union_find_labels(V, t)
+    assert sorted(set(base.tolist())) == [0, 42, 69, 72]
+    for seed in range(3):
+        perm, rt = MR.renumber(V, t, seed)
+        got = MR.union_find_labels(V, rt)
+        for lab in set(base.tolist()):
+            members = perm[base == lab]
+            assert (got[members] == members.min()).all()
+        assert sorted(map(sorted, rt.tolist())) == sorted(map(sorted, perm[t].tolist()))      # the same triangles
+        w = np.arange(V * 3).reshape(V, 3)
+        nv = np.empty_like(w)
+        nv[perm] = w
+        lv, lt, n_comp, largest = MR.largest_component(nv, rt)
+        assert (n_comp, largest) == (3, 40) and sorted(lv[:, 0].tolist()) == list(range(0, 42 * 3, 3))
+    T = 300000
+    strip = MR.triangle_strip(T)
+    for name, tri in (("ascending", strip), ("descending", T + 1 - strip), ("shuffled", MR.renumber(T + 2, strip, 1)[1])):
+        t0 = time.perf_counter()
+        lab = MR.union_find_labels(T + 2, tri)
+        print(f"union_find_labels, strip of {T} triangles, {name}: {time.perf_counter() - t0:.2f} s")
+        assert not lab.any()
+    two = np.concatenate([MR.triangle_strip(500, 0, 2), MR.triangle_strip(500, 1, 2)])
+    lab = MR.union_find_labels(1004, two[rs.permutation(1000)])
+    assert np.array_equal(lab, np.arange(1004) % 2)
+    lv, lt, n_comp, largest = MR.largest_component(np.arange(1004)[:, None].repeat(3, 1), two)
+    assert (n_comp, largest) == (2, 500) and np.array_equal(lv[:, 0], np.arange(0, 1004, 2))      # the tie goes to label 0
+
+
+def test_project_view_restatement_on_one_pixel_axes():
+    """MR.project_view needs no special case for a one-pixel axis: np.clip(., 0, 0), floor and min(x0 + 1, W - 1) all land on
+    pixel 0, the weights multiply one pixel with itself.  A 1 x 1 image colours every vertex with its pixel; with H == 1 the
+    colour is the linear interpolation along the row alone."""
+    rs = np.random.RandomState(1)
+    verts = rs.uniform(-1, 1, (50, 3)).astype(np.float32)
+    verts[:, 2] -= 3.0
+    pose = np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)
+    img = rs.randint(0, 256, (1, 1, 3)).astype(np.uint8)
+    colors, depth, pix, _ = MR.project_view(verts, img, pose, 20.0, 0.05)
+    assert (pix == 0).all() and np.array_equal(colors, np.tile(img[0, 0].astype(np.float64), (50, 1))) and (depth > 0).all()
+    row = rs.randint(0, 256, (1, 9, 3)).astype(np.uint8)
+    colors, _, pix, _ = MR.project_view(verts, row, pose, 20.0, 0.05)
+    assert (pix[:, 1] == 0).all() and len(np.unique(pix[:, 0])) > 10
+    x0 = np.floor(pix[:, 0]).astype(int)
+    fx = (pix[:, 0].astype(np.float64) - x0)[:, None]
+    want = (1 - fx) * row[0, x0] + fx * row[0, np.minimum(x0 + 1, 8)]
+    np.testing.assert_allclose(colors, want, rtol=0, atol=1e-12)
+    col = np.ascontiguousarray(row.transpose(1, 0, 2))
+    colors_t, _, pix_t, _ = MR.project_view(verts[:, [1, 0, 2]] * np.float32([-1, 1, 1]), col, pose, 20.0, 0.05)
+    assert (pix_t[:, 0] == 0).all() and len(np.unique(pix_t[:, 1])) > 10
 
 
 # ----------------------------------------------------------------------------------------------- PLY

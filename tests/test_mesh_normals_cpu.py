@@ -80,6 +80,31 @@ def test_order_of_the_triangles_is_immaterial():
     assert np.abs(NR.vertex_normals(v, rot, dtype=np.float64) - want).max() <= 1e-15
 
 
+def test_large_mesh_builders():
+    """The meshes tests/test_hip_mesh_normals.py takes past one sweep of the maximum kernel (262 144 triangles): what their
+    doc strings promise, at full size, and the restatement's normals on them."""
+    n = 400
+    v, t = NR.height_field_mesh(n)
+    T = 2 * (n - 1) ** 2
+    assert v.shape == (n * n, 3) and t.shape == (T, 3) and T == 318402 and T > 262144
+    c = NR.cross_products(v, t)
+    assert (c[:, 2] == 1.0).all() and np.abs(c[:, :2]).max() < 0.3
+    corner = n * n - 1
+    assert np.array_equal(np.nonzero((t == corner).any(1))[0], [T - 2, T - 1])
+    assert t[T - 2].tolist() == [corner - n - 1, corner, corner - n] and t[T - 1].tolist() == [corner - n - 1, corner - 1, corner]
+    nrm = NR.vertex_normals(v, t, dtype=np.float64)
+    assert nrm[:, 2].min() > 0.9 and np.abs(np.linalg.norm(nrm, axis=1) - 1).max() < 1e-15
+    fv, ft = NR.fan_mesh(100000)
+    fc = NR.cross_products(fv, ft)
+    big = np.abs(fc).max(1)
+    assert (ft[:, 0] == 0).all() and np.bincount(ft.reshape(-1))[1:].tolist() == [2] * 100000
+    assert big.min() > 0.99 * big.max() and (fc[:, 2] == big).all()      # congruent triangles, the largest component is z
+    fn = NR.vertex_normals(fv, ft, dtype=np.float64)
+    np.testing.assert_allclose(fn[0], [0, 0, 1], atol=1e-9)
+    rim = fv[1:, :2].astype(np.float64)
+    assert ((fn[1:, :2] * rim).sum(1) > 0).all() and fn[1:, 2].min() > 0.9      # tilted outwards, as a cone's are
+
+
 # ----------------------------------------------------------------------------------------------- PLY
 def _expected_ply(v, t, c=None):
     """Today's layout without normals, byte for byte."""
