@@ -449,6 +449,18 @@ int mnrf_field_composite_fused_pn(float* packed, int64_t n_rays, const float* ra
                                   float* weights, float* opacity, float* rgb_map, float* depth, float* mirror_mask,
                                   float* surf_normal, float* x_surface, float* pred_normal, void* stream);
 
+/* ---- the fp32 -> (hi, lo) conversion of the forward-only split kernels --------------------------------------------------
+ * Those kernels form lo = f16(x - hi) with two mixed-precision FMAs under a round-toward-zero f16 mode (8 vector
+ * instructions per value pair); the long form (convert, subtract, convert: 11) stays compiled for comparison and gives the
+ * same bits.  mnrf_split_convert_long(on): on > 0 puts every later forward-only split launch of this process on the long
+ * form, 0 on the short one, a negative value changes nothing; returns the setting it found (initially the environment's
+ * MNRF_SPLIT_CONVERT_LONG, read once).  The training kernels always run the long form.
+ * mnrf_split2_probe runs the kernels' own conversion, under their mode setting, over n_pairs pairs (x[2i], x[2i+1]) and
+ * writes the packed hi and lo words of pair i to hi[i] and lo[i]; relu != 0 passes the values through the kernels' ReLU
+ * first, as the in-stream conversion does; long_form != 0 takes the long form. */
+int mnrf_split_convert_long(int on);
+int mnrf_split2_probe(const float* x, int64_t n_pairs, int relu, int long_form, uint32_t* hi, uint32_t* lo, void* stream);
+
 /* ---- training, round 3: operand planes (split arithmetic only) --------------------------------------------------------
  * The weight gradients dW = dY^T X contract over samples.  With MNRF_TRAIN_PLANES the training forward keeps the inputs X
  * of every Linear -- and mnrf_field_backward_planes the pre-activation gradients dY -- not as fp32 rows but as the hi/lo

@@ -114,6 +114,7 @@ void launch_split_fold(const float* const* params, float* const* packed, int n_i
 int launch_split_bwd(const FieldBwdArgs& A, hipStream_t s);
 // 48-samples-per-wave tuning of the forward-only split kernels (mnrf_field_split3.hip), MNRF_SPLIT48=1
 bool split48_enabled();
+bool split_convert_long();       // the forward-only split kernels run the long form of the fp32 -> (hi, lo) conversion (mnrf_split_convert_long)
 int launch_split48(const FieldArgs& A, bool sigma_only, hipStream_t s);
 int split48_ray_samples();      // samples of one workgroup of that tuning = samples per ray of the ray-fused fine pass (192)
 int launch_split_bwd2(const FieldBwd2Args& A, hipStream_t s);

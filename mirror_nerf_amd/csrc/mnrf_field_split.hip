@@ -21,14 +21,29 @@ constexpr int S = 2;
 constexpr int MIN_WAVES_PER_SIMD = 1;
 constexpr int CHUNK_PAIRS = 8;
 constexpr int RING_SLOTS = 4;
+constexpr bool CONV_SHORT = true;      // fp32 -> (hi, lo) in 8 vector instructions per value pair (mnrf_field_split_common.inc split2)
+#define MNRF_SPLIT_NO_GRAD             // forward only: launch_split() sends every grad launch to h2x
 #include "mnrf_field_split.inc"
+#undef MNRF_SPLIT_NO_GRAD
 }  // namespace h2
+// h2 with the conversion in its long form (forward only): see h3l in mnrf_field_split3.hip
+namespace h2l {
+constexpr int S = 2;
+constexpr int MIN_WAVES_PER_SIMD = 1;
+constexpr int CHUNK_PAIRS = 8;
+constexpr int RING_SLOTS = 4;
+constexpr bool CONV_SHORT = false;
+#define MNRF_SPLIT_NO_GRAD
+#include "mnrf_field_split.inc"
+#undef MNRF_SPLIT_NO_GRAD
+}  // namespace h2l
 // h2x: 32 KiB chunks (half the seams), 96 KiB ring of three slots
 namespace h2x {
 constexpr int S = 2;
 constexpr int MIN_WAVES_PER_SIMD = 1;
 constexpr int CHUNK_PAIRS = 16;
 constexpr int RING_SLOTS = 3;
+constexpr bool CONV_SHORT = false;     // the training kernels keep the long form of the conversion
 #include "mnrf_field_split.inc"
 #include "mnrf_field_split_bwd.inc"
 }  // namespace h2x
@@ -43,7 +58,7 @@ int launch_split(const FieldArgs& A, bool sigma_only, bool grad, hipStream_t s) 
     // default of the forward-only launches: 48 samples per wave (mnrf_field_split3.hip); geo_feat needs both halves of L8
     // in registers, which that tuning cannot afford
     if (!A.geo_feat && split48_enabled()) return launch_split48(A, sigma_only, s);
-    return h2::launch(A, sigma_only, grad, s);
+    return split_convert_long() ? h2l::launch(A, sigma_only, grad, s) : h2::launch(A, sigma_only, grad, s);
 }
 
 int launch_split_bwd(const FieldBwdArgs& A, hipStream_t s) { return h2x::launch_bwd(A, s); }

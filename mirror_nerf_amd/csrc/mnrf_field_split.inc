@@ -154,7 +154,9 @@ __device__ __forceinline__ float relu_(float x) {
 //   * half 2 of layer l converts half 1 of layer l into B operands 0..3 -- each one only after half 2 is done with the
 //     OLD operand of the same index (unit 4T'+4 on), since the new operands overwrite the layer's inputs in place;
 //   * half 1 of layer l+1 converts half 2 of layer l into B operands 4..7 during its T-steps 0..3, which read 0..3.
-// One task = two adjacent accumulator registers -> one 32-bit word of the hi and of the lo operand.  Tasks are numbered so
+// One task = two adjacent accumulator registers -> one 32-bit word of the hi and of the lo operand: 11 vector instructions in the
+// long form of split2, 8 in the short one (CONV_SHORT; its two-instruction asm statement is placed by the compiler inside the
+// sub-group's fenced region, behind the sub-group's first MFMAs like the rest of the task -- checked in the disassembly).  Tasks are numbered so
 // that the operands fill in T order: q = 4*S*Trel + 4*s + 2*(nb&1) + rp, nb = 2*Trel + ((q>>1)&1).
 constexpr int NTASKS = 16 * S;
 template <int ACT, bool WANT_MASK>
@@ -586,6 +588,7 @@ __device__ __forceinline__ void field_split_body(FieldArgs A) {
     constexpr long long JUMP_FROM_MIRB = BLENDED ? (long long)(FOLD_POS_DIR - (FOLD_POS_MIRB + FOLD_MIRB_PAIRS)) * PAIR_BYTES : 0;
     constexpr int JT = BLENDED ? 54 : -1;      // the unit of a 64-pair part that issues the last piece of the first chunk BEHIND the part
     constexpr bool FOLD = !SIGMA_ONLY && !GRAD;
+    conv_round_mode();
     float* const fz = (float*)(smem + LDS_FUSE);      // FUSE: [9][WG_SAMPLES]
     // Dynamic tile queue (S = 3, FieldArgs::tile_queue): the launch has one workgroup per CU; the first tile is the workgroup's
     // own id, every further one comes from the global counter -- requested at the START of the tile before, parked in LDS

@@ -126,13 +126,44 @@ __device__ __forceinline__ void fast_sincos(float a, float& sn, float& cs) {
 
 // ------------------------------------------------------------------ fp32 -> (hi, lo) f16 pairs
 // v_cvt_pkrtz_f16_f32 rounds toward zero, so lo = x - hi has the sign of x: |x - hi - lo| < 2^-20 |x|.
+//
+// CONV_SHORT (set by the includer; the forward-only tunings h2 and h3): lo in two instructions instead of five, 8 vector
+// instructions per value pair instead of 11 (two accumulator reads, two integer max, cvt_pkrtz, mixlo, mixhi, max3).  x - f32(hi)
+// is exact in fp32, so fma(-f32(hi), 1, x) is that same number; v_fma_mixlo_f16 / v_fma_mixhi_f16 take a half of hi as an f16
+// source (op_sel_hi says "f16", op_sel which half), form the fp32 FMA and write it as one f16 half, rounded by the wave's f16
+// rounding mode -- which conv_round_mode() sets to toward-zero at kernel entry: the bits of v_cvt_pkrtz_f16_f32, its saturation
+// at 65504 included (tests/test_hip_split_convert.py holds both forms against the definition and the kernels against each other).
+// The mode also governs v_cvt_f16_f32, v_cvt_pk_f16_f32, every *_f16 arithmetic instruction and all f64 arithmetic: the kernels
+// of these tunings contain none (DESIGN 4.1b; v_cvt_f32_f16 is exact, v_cvt_pkrtz and the MFMAs do not read the mode).
+// hipcc does not select the pair by itself (it turns the multiplication by -1 into a subtraction of a converted value), hence
+// inline assembly -- a plain, non-volatile statement with register operands, which the compiler schedules like any instruction
+// between the sched_barrier(0) fences of gemm_part_impl; it is no VALU to sched_group_barrier(0x002), whose groups hold the
+// task's six other instructions -- and with it the wait states the compiler no longer inserts: the ISA asks for 2 between a
+// VALU write of a register and an MFMA reading it as A / B, and for 1 between a write of one half of a register (mixhi) and a
+// VALU read of it.  The statement ends with mixhi, so both are owed by what follows it.  The words are B operands of a LATER
+// GEMM part: an in-stream job ends 12 to 16 units before its part does, L1's ends with the part, and a block conversion
+// (conv_half, split_b, acc_to_b) is followed by sat_flush's compare and ballot; then come the next part's bias reads, its
+// opening s_waitcnt and a unit's first MFMAs on other operands.  scripts/check_isa.py asserts on every build that no
+// instruction within two of a v_fma_mixhi_f16 names its destination.
+// The destination is early-clobber: mixlo writes it before mixhi has read hi and x1.
+__device__ __forceinline__ void conv_round_mode() {
+    // MODE.FP_ROUND[3:2] (f16 / f64 results) = 3, toward zero; [1:0] (fp32) stays.  Per wave, gone with the wave.
+    if constexpr (CONV_SHORT) __builtin_amdgcn_s_setreg(1 | (2 << 6) | ((2 - 1) << 11), 3);      // hwreg(HW_REG_MODE, 2, 2)
+}
 __device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigned& lo) {
     const auto h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    const float r0 = x0 - (float)h[0];
-    const float r1 = x1 - (float)h[1];
-    const auto l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
     hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
+    if constexpr (CONV_SHORT) {
+        asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, -%1, 1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+            : "=&v"(lo)
+            : "v"(hi), "v"(x0), "v"(x1));
+    } else {
+        const float r0 = x0 - (float)h[0];
+        const float r1 = x1 - (float)h[1];
+        const auto l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
+        lo = __builtin_bit_cast(unsigned, l);
+    }
 }
 
 // ------------------------------------------------------------------ range guard

@@ -12,7 +12,12 @@ activation-gradient and second-order kernels of both arithmetics):
   * the hand-placed reads and counted waits are present,
   * no scratch (spill) traffic at all in the forward kernels of the split arithmetic and inside the MFMA range of
     the fp32 forward kernels; the known phase-boundary spills of the gradient kernels are reported, and bounded,
-  * the weight-gradient GEMMs (mnrf_dw.o, mnrf_dwp.o) do not spill.
+  * the weight-gradient GEMMs (mnrf_dw.o, mnrf_dwp.o) do not spill,
+  * the forward-only split kernels (h2, h3) convert a value pair in the short form (mnrf_field_split_common.inc split2): the body
+    of a 256-wide trunk layer loop (the `#pragma unroll 1` loops of L2-L4 and L6-L8: 384 MFMAs per 16 samples of a wave) holds no
+    more non-MFMA vector instructions than the short form's count plus an allowance -- a compiler or source change that brings the
+    11-instruction form back adds 3 per pair, 288 per loop at 48 samples per wave -- and nothing within two instructions of a
+    v_fma_mixhi_f16 names its destination (the wait states inline assembly owes, see split2).
 """
 import os
 import re
@@ -41,6 +46,44 @@ def disassemble(obj):
         elif cur is not None and line.startswith("\t"):
             cur.append(line)
     return kernels
+
+
+def _address(line):
+    m = re.search(r"// ([0-9A-Fa-f]{8,}):", line)
+    return int(m.group(1), 16) if m else None
+
+
+def layer_loops(body, n_mfma):
+    """Non-MFMA vector instruction counts of the loops (a backward conditional branch and its target) that hold n_mfma MFMAs."""
+    addr = [_address(l) for l in body]
+    out = []
+    for i, l in enumerate(body):
+        m = re.match(r"\ts_cbranch_\w+ .*<[^>]*\+0x([0-9a-f]+)>", l)
+        if m and addr[i] is not None and addr[0] is not None:
+            target = addr[0] + int(m.group(1), 16)
+            if target < addr[i] and target in addr:
+                seg = body[addr.index(target):i + 1]
+                if sum("v_mfma" in x for x in seg) == n_mfma:
+                    out.append(sum(bool(re.match(r"\tv_(?!mfma)", x)) for x in seg))
+    return out
+
+
+def mixhi_near_readers(body):
+    """Instructions within two of a v_fma_mixhi_f16 that name its destination register."""
+    bad = []
+    for i, l in enumerate(body):
+        m = re.match(r"\tv_fma_mixhi_f16 v(\d+),", l)
+        if not m:
+            continue
+        r = int(m.group(1))
+        for nxt in body[i + 1:i + 3]:
+            ins = nxt.split("//")[0]
+            regs = {int(a) for a in re.findall(r"\bv(\d+)\b", ins)}
+            for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", ins):
+                regs |= set(range(int(a), int(b) + 1))
+            if r in regs:
+                bad.append(ins.strip())
+    return bad
 
 
 def check_object(name, mfma, rules):
@@ -73,6 +116,14 @@ def check_object(name, mfma, rules):
                 or scratch_all > rule["scratch_total_max"]:
             print("   ^^^ VIOLATION")
             ok = False
+        if "layer_valu_max" in rule:
+            loops = layer_loops(body, rule["layer_mfma"])
+            near = mixhi_near_readers(body)
+            print(f"   256-wide layer loops: {loops} non-MFMA vector instructions (bound {rule['layer_valu_max']}), "
+                  f"{sum('v_fma_mixhi_f16' in l for l in body)} v_fma_mixhi_f16, {len(near)} with a reader within two instructions")
+            if len(loops) != 2 or max(loops) > rule["layer_valu_max"] or near:
+                print("   ^^^ VIOLATION (conversion form)", near[:4])
+                ok = False
     return ok, n
 
 
@@ -89,7 +140,12 @@ def main():
     ok &= o and n5 >= 4
     fwd16 = dict(min_counted=100, counted_re=r"s_waitcnt lgkmcnt\([24]\)", scratch_inside_max=0, scratch_total_max=0)
     grad16 = dict(fwd16, scratch_inside_max=400, scratch_total_max=600)
+    # short conversion form, per 256-wide layer loop: 531 / 547 at 32 samples per wave (the long form: 723 / 739), 794 / 810 at 48
+    # (1082 / 1098); the bounds leave 20 for a compiler's change of mind and lie 170 and 270 below the long form
+    short32 = dict(layer_mfma=768, layer_valu_max=567)
+    short48 = dict(layer_mfma=1152, layer_valu_max=830)
     o, n2 = check_object("mnrf_field_split.o", "v_mfma_f32_16x16x32_f16", [
+        (r"4mnrf2h218field_split_kernel", dict(fwd16, **short32)),
         (r"field_split_kernel", fwd16),
         # the planes variants are the training default: the activation-gradient kernel keeps a handful of long-lived scalars in
         # scratch (9 reloads inside its streams since round 4; it was 161 while dL/dh8 was live through the colour branch, and that
@@ -103,19 +159,23 @@ def main():
     # 48-samples-per-wave tuning (S = 3, forward only): the sigma-only kernel must not spill; the full kernel's heads spill a
     # few B operands (safe: vmcnt waits only get stricter; reported and bounded)
     o, n4 = check_object("mnrf_field_split3.o", "v_mfma_f32_16x16x32_f16", [
-        (r"field_split_kernelILb1ELb0", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)")),        # one unit of read-ahead: the unit's wait is lgkmcnt(0)
+        # (h3l: the same five kernels with the long conversion form, kept for comparison -- every bound but the conversion's)
+        (r"4mnrf3h3l.*field_split_kernelILb0ELb0ELb0ELb1", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8)),
+        (r"4mnrf3h3l.*field_split_kernel_(rgb_depth|blended)", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8)),
+        (r"4mnrf3h3l.*field_split_kernel", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)")),
+        (r"field_split_kernelILb1ELb0", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", **short48)),        # one unit of read-ahead: the unit's wait is lgkmcnt(0)
         # the full kernel: ZERO scratch since round 3 (sample index and lane group recomputed from the execution-mask count),
         # also with the tile loop of the dynamic queue (every lane-derived value re-derived per tile through an opaque lane id).
         # Its ray-fused variant (FUSE): zero inside the network; the compositing wave at the end of a tile re-reads two
         # lane-derived values (the lane id behind __shfl_*) that hipcc hoists out of the tile loop: 2 stores per launch,
         # 5 loads per tile in one wave -- bounded
-        (r"field_split_kernelILb0ELb0ELb0ELb0", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)")),
-        (r"field_split_kernelILb0ELb0ELb0ELb1", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8)),
+        (r"field_split_kernelILb0ELb0ELb0ELb0", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", **short48)),
+        (r"field_split_kernelILb0ELb0ELb0ELb1", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8, **short48)),
         # its rgb / depth variant (the last reflection level): the same network without the mirror head, the same bound
-        (r"field_split_kernel_rgb_depth", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8)),
+        (r"field_split_kernel_rgb_depth", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8, **short48)),
         # its blended-level variant: the whole network (the mirror head in front of the colour branch), the same bound
-        (r"field_split_kernel_blended", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8))])
-    ok &= o and n4 >= 5
+        (r"field_split_kernel_blended", dict(fwd16, counted_re=r"s_waitcnt lgkmcnt\(0\)", scratch_total_max=8, **short48))])
+    ok &= o and n4 >= 10
     if n < 9 or n2 < 10:
         print(f"expected >= 9 fp32 and >= 10 split kernels, found {n} and {n2}")
     # weight-gradient GEMMs: no hand-placed scheme, but a spill there is a 2x slowdown nobody would notice
