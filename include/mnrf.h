@@ -306,6 +306,39 @@ int mnrf_objects_merge(const float* const* obj_rgb, const float* const* obj_dept
                        MNRF_HOST const float* pose_scale0, float near, float* rgb, float* depth, float* mask, int32_t* n_used,
                        void* stream);
 
+/* ---- Several new mirrors at one level, on any plane: batched_inference(new_mirrors=[...]).  csrc/mnrf_mirrors.hip.
+ *
+ * THE RULE, per ray (o, d) of rays (n_rays,8) and the n_mirrors (1..MNRF_MIRRORS_MAX) mirrors in list order.  Every mirror is
+ * tested against depth0, the ray's depth as it is BEFORE this call.  All arithmetic is single fp32 operations in the order written.
+ * Mirror k gives an intersection x and in-plane coordinates (u, w):
+ *   kind MNRF_MIRROR_AXIS  (axes[k], positions[k]; mnrf_place_mirror's very expressions, one shared device function):
+ *     t = (position - o_a) / d_a, u = t * d_b + o_b, w = t * d_2 + o_2, x_a = position, x_b = u, x_2 = w;
+ *   kind MNRF_MIRROR_FRAME (row k of frames: centre c, in-plane unit axes e_u, e_w; row k of normals: the unit normal n):
+ *     e = c - o, num = (n0*e0 + n1*e1) + n2*e2, den = (n0*d0 + n1*d1) + n2*d2, t = num / den, x_j = t * d_j + o_j, r = x - c,
+ *     u = (eu0*r0 + eu1*r1) + eu2*r2, w alike with e_w.
+ * Row k of rects is (r0, r1, r2, r3), in (u, w).  Shape MNRF_MIRROR_RECT: inside = !(u < r0 || w < r2 || u > r1 || w > r3);
+ * MNRF_MIRROR_ELLIPSE, inscribed in the rect: uc = (r0 + r1) * 0.5f, ru = (r1 - r0) * 0.5f, a = (u - uc) / ru, b alike for w,
+ * q = a*a + b*b, inside = !(q > 1.f).  A NaN coordinate counts as inside.  Then, as mnrf_place_mirror:
+ * dist = sqrtf(e0*e0 + e1*e1 + e2*e2) with e = o - x, s = sum((x - o) * d), blocked = dist > depth0 && depth0 > near,
+ * hit = inside && s > 0 && !blocked.  The winner is `best` of
+ *     best = -1;  for k = 0 .. n_mirrors-1:  if hit_k && (best < 0 || dist_k <= best_dist) { best = k; best_dist = dist_k; }
+ * -- the nearest hit, an exact tie to the LATER mirror, a NaN never replaces a winner.  Only where best >= 0:
+ * x_surface (n_rays,3) = x_best, depth (n_rays) = dist_best, normal (n_rays,3) = row best of normals, in place.  Unlike
+ * mnrf_place_mirror, the normal of a ray that is inside a mirror's shape but takes no mirror is KEPT.  mask (n_rays;
+ * thresholded) becomes `mask != 0 || best >= 0` in place; mask_bool (1 byte per ray, null = skip) receives the same; *any
+ * (int32, device, caller zeroes it, null = skip) is OR-ed with "any merged ray"; index (n_rays int32, null = skip) = best.
+ * kinds, shapes, axes (read where the kind is AXIS), positions (alike), frames (9 floats a row, read where the kind is FRAME),
+ * normals (3 a row), rects (4 a row): HOST arrays of n_mirrors rows; they travel in the kernel's argument block.  One launch. */
+#define MNRF_MIRRORS_MAX 8
+#define MNRF_MIRROR_AXIS 0
+#define MNRF_MIRROR_FRAME 1
+#define MNRF_MIRROR_RECT 0
+#define MNRF_MIRROR_ELLIPSE 1
+int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirrors, MNRF_HOST const int* kinds, MNRF_HOST const int* shapes,
+                       MNRF_HOST const int* axes, MNRF_HOST const float* positions, MNRF_HOST const float* frames,
+                       MNRF_HOST const float* normals, MNRF_HOST const float* rects, float near, float* depth, float* mask,
+                       float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any, int32_t* index, void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

@@ -6,6 +6,7 @@ rendering hot path behind the reference's own Python interfaces.
     from mirror_nerf_amd import DirectTemporalNeRF, render_rays_dnerf  # models/d_nerf: the animated object of run.sh MODE 4
     from mirror_nerf_amd import ObjectBounds, estimate_object_bounds    # where a placed object is: batched_inference(object_bounds=)
     from mirror_nerf_amd import PlacedObject                            # several objects: batched_inference(placed_objects=[...])
+    from mirror_nerf_amd import PlacedMirror                            # several mirrors on any plane: batched_inference(new_mirrors=[...])
     from mirror_nerf_amd import get_loss                                # losses.py:258 (TotalLoss, fused value + gradient)
     from mirror_nerf_amd import RayBank, read_blender                   # datasets/blender.py: training batches drawn on the device
     from mirror_nerf_amd import finish_frame, SplitExtrema, colormap_depth   # eval.py:743-978: the 8-bit images of a frame
@@ -20,6 +21,7 @@ from .recursion import NeRFSystem, batched_inference, render_rays_chunk_recursiv
 from .dnerf import DirectTemporalNeRF, load_dnerf_object, render_rays_dnerf  # noqa: F401
 from .object_bounds import ObjectBounds, estimate_object_bounds  # noqa: F401
 from .placed_objects import PlacedObject  # noqa: F401
+from .placed_mirrors import PlacedMirror  # noqa: F401
 from .losses import TotalLoss, get_loss  # noqa: F401
 from .data import RayBank, read_blender  # noqa: F401
 from . import frames  # noqa: F401
@@ -28,5 +30,5 @@ from .validation import validate, validation_step  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["Embedding", "MirrorNeRF", "render_rays", "sample_pdf", "NeRFSystem", "batched_inference",
-           "render_rays_chunk_recursively", "DirectTemporalNeRF", "load_dnerf_object", "render_rays_dnerf", "ObjectBounds", "estimate_object_bounds", "PlacedObject", "TotalLoss", "get_loss", "RayBank", "read_blender", "frames", "finish_frame", "SplitExtrema",
+           "render_rays_chunk_recursively", "DirectTemporalNeRF", "load_dnerf_object", "render_rays_dnerf", "ObjectBounds", "estimate_object_bounds", "PlacedObject", "PlacedMirror", "TotalLoss", "get_loss", "RayBank", "read_blender", "frames", "finish_frame", "SplitExtrema",
            "colormap_depth", "jet_table", "val_panel", "validation_step", "validate"]

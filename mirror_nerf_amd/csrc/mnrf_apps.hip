@@ -10,6 +10,7 @@
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
+#include "mnrf_mirror.h"
 #include "mnrf_object.h"
 
 namespace {
@@ -35,30 +36,18 @@ __global__ __launch_bounds__(256) void place_mirror_kernel(PlaceArgs A) {
         const float* r = A.rays + i * 8;
         const float o[3] = {r[0], r[1], r[2]};
         const float d[3] = {r[3], r[4], r[5]};
-        const int a = A.axis == MNRF_PLANE_Y ? 1 : 0;      // the plane's axis
-        const int b = 1 - a;                                // the rectangle's first coordinate (y for plane_x, x for plane_y)
-        // eval.py:391-398 / 435-442: (p - o_a) / d_a * d_b + o_b
-        const float t = (A.pos - o[a]) / d[a];
-        const float u = t * d[b] + o[b];
-        const float w = t * d[2] + o[2];
-        float x[3];
-        x[a] = A.pos;
-        x[b] = u;
-        x[2] = w;
-        const bool in_rect = !(u < A.rect[0] || w < A.rect[2] || u > A.rect[1] || w > A.rect[3]);   // eval.py:403-414 / 445-456
+        float x[3], u, w;
+        mnrf_mirror::axis_point(A.axis, A.pos, o, d, x, u, w);                                     // eval.py:391-398 / 435-442
+        const bool in_rect = mnrf_mirror::in_rect(u, w, A.rect);                                   // eval.py:403-414 / 445-456
         const float depth = A.depth[i];
         if (in_rect) {                                                                             // eval.py:458-460
             A.normal[i * 3 + 0] = A.nrm[0];
             A.normal[i * 3 + 1] = A.nrm[1];
             A.normal[i * 3 + 2] = A.nrm[2];
         }
-        // eval.py:461-463: torch.norm(o - x)
-        const float e0 = o[0] - x[0], e1 = o[1] - x[1], e2 = o[2] - x[2];
-        const float dist = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-        // eval.py:466-474: the intersection lies on the ray, not on its backward extension
-        const float s = (x[0] - o[0]) * d[0] + (x[1] - o[1]) * d[1] + (x[2] - o[2]) * d[2];
-        // eval.py:477-483 with eval.py:169-171: the foreground occludes it (depth of this level before any edit, the global near)
-        const bool blocked = dist > depth && depth > A.near;
+        const float dist = mnrf_mirror::distance(o, x);                                            // eval.py:461-463
+        const float s = mnrf_mirror::side(o, d, x);                                                // eval.py:466-474
+        const bool blocked = mnrf_mirror::blocked(dist, depth, A.near);                            // eval.py:477-483
         const bool hit = in_rect && s > 0.f && !blocked;
         merged = A.mask[i] != 0.f || hit;                                                          // eval.py:307, 490
         if (hit) {                                                                                 // eval.py:484-499

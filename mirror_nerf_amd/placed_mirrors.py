@@ -1,0 +1,169 @@
+"""Several new mirrors in one scene, on any plane: `batched_inference(..., new_mirrors=[PlacedMirror(...), ...])`.
+
+app_place_new_mirror of the reference places exactly one mirror on a plane x = c or y = c (`new_mirror=` follows it).  A
+PlacedMirror is either that axis-aligned mirror (`PlacedMirror.axis_aligned`, the keys of `new_mirror=`) or a mirror on any
+plane, given by a centre, a normal, an up direction and a size; its shape is the rectangle or the ellipse inscribed in it.  A
+list of 1..MAX_MIRRORS of them is applied at every recursion level below the last, right behind the threshold of the mirror
+mask, by one rule (include/mnrf.h mnrf_place_mirrors):
+
+    every mirror is tested against the level's depth as it is before any mirror of the call; per ray the nearest hit wins, an
+    exact tie goes to the later mirror of the list, and the winner alone writes the ray's x_surface, depth and normal.
+
+One deliberate difference from the single mirror: the reference writes the plane's normal to every ray inside the rectangle
+BEFORE its two filters (eval.py:458-460), so a second mirror behind the first would overwrite the normal of rays that hit the
+first.  Here the normal of a ray that is inside a shape but takes no mirror is kept.  The device pass is mnrf_place_mirrors,
+one launch for the whole list.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors"]
+
+MAX_MIRRORS = 8      # MNRF_MIRRORS_MAX
+SHAPES = ("rect", "ellipse")
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def _vec(v, n, what):
+    try:
+        a = np.asarray(v, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"PlacedMirror: {what} holds {n} numbers, not {v!r}") from None
+    if a.shape != (n,):
+        raise ValueError(f"PlacedMirror: {what} holds {n} numbers, not {v!r}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"PlacedMirror: {what} must be finite, not {v!r}")
+    return a
+
+
+class PlacedMirror:
+    """One mirror of `new_mirrors=`.
+
+    PlacedMirror(center, normal, up, size=(width, height), shape="rect" | "ellipse"): the plane through `center` with normal
+    `normal` (the side the mirror faces); `up` fixes the rotation about the normal -- the height runs along the part of `up` that
+    lies in the plane, the width along cross(that, normal).  The frame is built in float64 and rounded once to float32:
+        n = normal / |normal|,  e_w = normalize(up - (up . n) n),  e_u = normalize(cross(e_w, n)),
+        rect = (-width / 2, width / 2, -height / 2, height / 2) in (u, w).
+    The float64 frame stays in .frame64 (rows n, e_u, e_w).  Refused: a zero normal, an up parallel to the normal, a size that is
+    not positive, input that is not finite.
+
+    PlacedMirror.axis_aligned(axis, position, normal, rect, shape="rect"): the mirror of `new_mirror=`, on the plane
+    x = position (axis "x", rect = (y0, y1, z0, z1)) or y = position (axis "y", rect = (x0, x1, z0, z1)); `normal` is what is
+    written to the rays that take it, as given."""
+
+    def __init__(self, center, normal, up, size, shape="rect"):
+        if shape not in SHAPES:
+            raise ValueError(f"PlacedMirror: shape must be 'rect' or 'ellipse', not {shape!r}")
+        c, n, up, size = _vec(center, 3, "center"), _vec(normal, 3, "normal"), _vec(up, 3, "up"), _vec(size, 2, "size")
+        if not (size > 0.0).all():
+            raise ValueError(f"PlacedMirror: size = (width, height) must be positive, not {tuple(size)}")
+        length = np.linalg.norm(n)
+        if not length > 0.0:
+            raise ValueError("PlacedMirror: the normal is zero")
+        n = n / length
+        up = up / max(np.linalg.norm(up), np.finfo(np.float64).tiny)
+        e_w = up - np.dot(up, n) * n
+        length = np.linalg.norm(e_w)
+        if not length > 1e-8:
+            raise ValueError("PlacedMirror: up is parallel to the normal (or zero): it does not fix the mirror's rotation about it")
+        e_w = e_w / length
+        e_u = np.cross(e_w, n)
+        e_u = e_u / np.linalg.norm(e_u)
+        self.kind, self.shape = "frame", shape
+        self.frame64 = np.stack([n, e_u, e_w])
+        self.center = tuple(_f32(v) for v in c)
+        self.normal = tuple(_f32(v) for v in n)
+        self.e_u = tuple(_f32(v) for v in e_u)
+        self.e_w = tuple(_f32(v) for v in e_w)
+        self.rect = (_f32(-size[0] / 2), _f32(size[0] / 2), _f32(-size[1] / 2), _f32(size[1] / 2))
+        self.axis, self.position = None, None
+
+    @classmethod
+    def axis_aligned(cls, axis, position, normal, rect, shape="rect"):
+        if shape not in SHAPES:
+            raise ValueError(f"PlacedMirror: shape must be 'rect' or 'ellipse', not {shape!r}")
+        if axis not in ("x", "y"):
+            raise ValueError(f"PlacedMirror: axis must be 'x' or 'y', not {axis!r}")
+        n, rect = _vec(normal, 3, "normal"), _vec(rect, 4, "rect")
+        position = _vec([position], 1, "position")[0]
+        self = cls.__new__(cls)
+        self.kind, self.shape, self.frame64 = "axis", shape, None
+        self.axis, self.position = axis, _f32(position)
+        self.normal = tuple(_f32(v) for v in n)
+        self.rect = tuple(_f32(v) for v in rect)
+        self.center = self.e_u = self.e_w = (0.0, 0.0, 0.0)
+        return self
+
+    def as_dict(self):
+        """The mirror as the C entry point receives it (every number a float32 value)."""
+        return dict(kind=self.kind, shape=self.shape, axis=self.axis, position=self.position, center=self.center, normal=self.normal,
+                    e_u=self.e_u, e_w=self.e_w, rect=self.rect)
+
+    def __repr__(self):
+        if self.kind == "axis":
+            return f"PlacedMirror.axis_aligned({self.axis!r}, {self.position}, normal={self.normal}, rect={self.rect}, shape={self.shape!r})"
+        return f"PlacedMirror(center={self.center}, normal={self.normal}, e_u={self.e_u}, e_w={self.e_w}, rect={self.rect}, shape={self.shape!r})"
+
+
+def refuse(args, models, kwargs):
+    """The refusals of `new_mirrors=`, each with its reason.  What the list is allowed beside -- placed_objects= and
+    app_reflection_substitution -- keeps its own refusals (recursion._refuse_apps goes on with them)."""
+    mirrors = kwargs["new_mirrors"]
+    if isinstance(mirrors, PlacedMirror) or not isinstance(mirrors, (list, tuple)):
+        raise TypeError(f"new_mirrors must be a list of PlacedMirror, not {type(mirrors).__name__}")
+    if not 1 <= len(mirrors) <= MAX_MIRRORS:
+        raise ValueError(f"new_mirrors holds 1..{MAX_MIRRORS} mirrors (MNRF_MIRRORS_MAX), not {len(mirrors)}")
+    for k, m in enumerate(mirrors):
+        if not isinstance(m, PlacedMirror):
+            raise TypeError(f"new_mirrors[{k}] must be a PlacedMirror, not {type(m).__name__}")
+    if getattr(args, "app_place_new_mirror", False) or kwargs.get("new_mirror") is not None:
+        raise ValueError("new_mirrors= carries every mirror of the call: it cannot be combined with app_place_new_mirror or new_mirror= "
+                         "(the single mirror; PlacedMirror.axis_aligned takes its keys)")
+    from .placed_objects import SINGLE_OBJECT_KEYWORDS
+    given = [k for k in SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
+    if given or (getattr(args, "app_reflect_newly_placed_objects", False) and kwargs.get("placed_objects") is None):
+        raise ValueError("new_mirrors= is combined with objects through placed_objects=[PlacedObject(...), ...], not with the "
+                         f"single-object keywords ({', '.join(k + '=' for k in given) or 'app_reflect_newly_placed_objects without placed_objects='})")
+    if getattr(args, "app_control_mirror_roughness", False):
+        raise ValueError("app_control_mirror_roughness cannot be combined with new_mirrors= (one application at a time, except "
+                         "placed mirrors with placed objects or substitution)")
+    if not any(getattr(m, "predict_mirror_mask", False) for m in models.values()):
+        raise ValueError("new_mirrors= needs a mirror-mask head (predict_mirror_mask=True): the new mirror is merged into the "
+                         "predicted mirror mask, and substitution replaces what the mask marks")
+    if getattr(args, "near", None) is None:
+        raise ValueError("new_mirrors= needs args.near: the foreground test compares the depth with it (eval.py:169-171)")
+
+
+def pack(mirrors):
+    """The host arrays of mnrf_place_mirrors for a list of PlacedMirror: (K, kinds, shapes, axes, positions, frames, normals, rects)."""
+    K = len(mirrors)
+    kinds, shapes, axes = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_int * K)()
+    positions, frames = (ctypes.c_float * K)(), (ctypes.c_float * (9 * K))()
+    normals, rects = (ctypes.c_float * (3 * K))(), (ctypes.c_float * (4 * K))()
+    for k, m in enumerate(mirrors):
+        kinds[k] = _lib.MNRF_MIRROR_AXIS if m.kind == "axis" else _lib.MNRF_MIRROR_FRAME
+        shapes[k] = _lib.MNRF_MIRROR_ELLIPSE if m.shape == "ellipse" else _lib.MNRF_MIRROR_RECT
+        axes[k] = _lib.MNRF_PLANE_Y if m.axis == "y" else _lib.MNRF_PLANE_X
+        positions[k] = m.position if m.position is not None else 0.0
+        frames[9 * k:9 * k + 9] = m.center + m.e_u + m.e_w
+        normals[3 * k:3 * k + 3] = m.normal
+        rects[4 * k:4 * k + 4] = m.rect
+    return K, kinds, shapes, axes, positions, frames, normals, rects
+
+
+def place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool=None, flag=None, index=None):
+    """mnrf_place_mirrors on one level's rays (N, 8) and maps, in place.  packed: pack(mirrors); mask_bool: (N,) torch.bool or
+    None; flag: device int32 of one element, OR-ed with "any merged ray", or None; index: (N,) int32 or None."""
+    p = _lib.ptr
+    K, kinds, shapes, axes, positions, frames, normals, rects = packed
+    _lib.check(_lib.lib().mnrf_place_mirrors(
+        p(rays), rays.shape[0], K, kinds, shapes, axes, positions, frames, normals, rects, float(near), p(depth), p(mask), p(normal),
+        p(x_surface), ctypes.c_void_p(mask_bool.data_ptr()) if mask_bool is not None else None, p(flag), p(index), _lib.stream()),
+        "mnrf_place_mirrors")
+

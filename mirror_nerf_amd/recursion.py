@@ -14,7 +14,8 @@ Python here is the recursion driver only: mask thresholding, reflected-ray const
 order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask,
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
 mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
-mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge).  One 4-byte device->host read per level decides
+mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge; several mirrors on any
+plane, new_mirrors=: mnrf_place_mirrors).  One 4-byte device->host read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
@@ -166,6 +167,10 @@ def _refuse_apps(args, models, kwargs):
     """The application flags batched_inference cannot honour, refused up front with the reason."""
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
+    multi = kwargs.get("new_mirrors") is not None
+    if multi:                                         # its own refusals; what it is allowed beside keeps its own, below
+        from .placed_mirrors import refuse as refuse_mirrors
+        refuse_mirrors(args, models, kwargs)
     if kwargs.get("placed_objects") is not None:      # the list carries the kinds: args.obj_model_type is not consulted
         from .placed_objects import refuse
         return refuse(args, models, kwargs)
@@ -233,6 +238,27 @@ def _place_mirror(r, rays_chunk, sel, plane, near, flag):
         p(rays_chunk), N, _lib.MNRF_PLANE_Y if plane["axis"] == "y" else _lib.MNRF_PLANE_X, plane["position"], nx, ny, nz, u0, u1, w0, w1, float(near),
         p(depth), p(mask), p(normal), p(r[f"x_surface_{sel}"]), ctypes.c_void_p(merged.data_ptr()), p(flag), _lib.stream()),
         "mnrf_place_mirror")
+    r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
+    if "depth_fine" in r:
+        r["depth_fine"] = depth
+    elif "depth_coarse" in r:
+        r["depth_coarse"] = depth
+    return mask
+
+
+def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index):
+    """The K-mirror rule on one level's maps, in place (placed_mirrors.py, mnrf_place_mirrors): _place_mirror's edits of the
+    result dict for the mirrors `packed` (placed_mirrors.pack); index: (N,) int32 that receives the mirror each ray took, or
+    None."""
+    from .placed_mirrors import place_mirrors
+    N = rays_chunk.shape[0]
+    for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
+        if k in r and not r[k].is_contiguous():
+            r[k] = r[k].contiguous()
+    mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
+    mask, depth, normal = r[mkey], r[f"depth_{sel}"], _pick_normal(r, sel)
+    merged = torch.empty(N, dtype=torch.bool, device=rays_chunk.device)
+    place_mirrors(rays_chunk, packed, near, depth, mask, normal, r[f"x_surface_{sel}"], merged, flag, index)
     r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
     if "depth_fine" in r:
         r["depth_fine"] = depth
@@ -761,7 +787,18 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     then a device int32 tensor of K elements -- element k: the number of rays, over all levels, that took object k when its
     turn came; a ray that a later, nearer object then takes counts for BOTH -- or of 1 element, which receives their sum.
     _object_chain=True (tests, measurements): the same list through K successive single-object passes (_merge_object), the
-    launches of the single-object path; the result is the same bit for bit."""
+    launches of the single-object path; the result is the same bit for bit.
+
+    new_mirrors=[PlacedMirror(center, normal, up, size, shape=) | PlacedMirror.axis_aligned(axis, position, normal, rect, shape=),
+    ...] (placed_mirrors.py; 1..8 mirrors, on any plane, rectangular or elliptic) with args.near: like app_place_new_mirror it
+    implies tracing and takes the un-blended route; at every level below the last, right behind the threshold (where the single
+    mirror is merged), ONE mnrf_place_mirrors applies THE RULE of include/mnrf.h: every mirror is tested against the level's
+    depth as it is before any mirror of the call, per ray the nearest hit wins (an exact tie goes to the later mirror) and writes
+    x_surface, depth and normal; the normal of a ray inside a shape that takes no mirror is KEPT (the single mirror overwrites
+    it, eval.py:458-460: that is why mirrors cannot be chained).  Allowed beside placed_objects= (the objects are merged first,
+    the mirrors see the resulting depth) and beside app_reflection_substitution; refused beside app_place_new_mirror /
+    new_mirror=, the single-object keywords and roughness.  The result gains new_mirror_index: int32 per ray of the call's own
+    rays, the mirror the ray took at level 0, -1 for none."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
@@ -788,6 +825,10 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
     plane = resolve_new_mirror(args, kwargs.get("new_mirror")) if place else None
+    multi = kwargs.get("new_mirrors") is not None                          # several mirrors on any plane (placed_mirrors.py)
+    if multi:
+        from .placed_mirrors import pack
+        mirrors_packed = pack(kwargs["new_mirrors"])
     xform = resolve_substitution(args) if subst else None
     system_sub = kwargs.get("system_substitution") if subst else None
     trace_flag = kwargs.get("trace_secondary_rays", False)
@@ -846,7 +887,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # pixels never takes the slower route for more than the chunks it takes to notice a change.
         # `blended_level=True` / `False` forces the choice (tests, measurements).
         can_blend = bool(level < args.max_recursive_level and trace_flag and test_time and blend_mode is not False
-                         and not (rough or place or subst or objects))
+                         and not (rough or place or subst or objects or multi))
         evidence = mirror_fraction.get(level)
         blended = can_blend and (blend_mode is True or (evidence is not None and evidence >= BLENDED_BREAK_EVEN))
         count_it = can_blend and blend_mode is not True
@@ -874,10 +915,14 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # in place (eval.py:303-307); at the last level nothing branches on "any mirror pixel": no host read, so the next
         # chunk's launches queue behind this pass without a stream sync.  A new mirror (eval.py:311-320) makes every level
         # below the last one trace; it is merged into the mask right behind the threshold, and its flag is the one read.
-        last = level >= args.max_recursive_level or not (trace_flag or place)
+        last = level >= args.max_recursive_level or not (trace_flag or place or multi)
         edit = None
         if place and not last:
             edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
+        if multi and level == 0:          # the mirror each of the call's own rays took; -1 where the list is not applied
+            r["new_mirror_index"] = torch.full((rays_chunk.shape[0],), -1, dtype=torch.int32, device=rays_chunk.device)
+        if multi and not last:
+            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index") if level == 0 else None)  # noqa: E731
         pending, any_mirror, counted = None, False, None
         if mask is not None:
             if host_flags is not None and not last and rays_chunk.shape[0]:
@@ -930,7 +975,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         N = rays_chunk.shape[0]
         dev = rays_chunk.device
         only_in = not (level < 1)                                         # eval.py:159
-        trace = bool(mask is not None and any_mirror and (trace_flag or place))     # eval.py:311-320, 503-504
+        trace = bool(mask is not None and any_mirror and (trace_flag or place or multi))     # eval.py:311-320, 503-504
         if level >= args.max_recursive_level:
             trace = False
         if not trace or N == 0:

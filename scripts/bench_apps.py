@@ -36,6 +36,17 @@ clock around a frame that ends in a synchronise; median and spread (max - min ov
 kept rays per object and level, and the device->host reads of kept-ray counts per frame.  Nothing is asserted on the times.
 
     python scripts/bench_apps.py --objects 1 2 4 [--objects_kind nerf_pl] [--reps 7]
+
+--mirrors K [K ...] runs the several-mirrors leg INSTEAD (batched_inference(new_mirrors=), on the same workload at
+max_recursive_level 1; args.near = 1e9, so that the scene -- opaque right in front of the camera -- hides no mirror and every
+ray inside the rectangle takes one): for each K, K copies of the default plane_x preset (the plane x = -1, its rectangle and
+normal) as PlacedMirror.axis_aligned, copy k moved by 0.05 k along -normal, so the first one wins wherever it is hit and every
+frame traces the same rays; beside them `legacy`, the unchanged single-mirror route (app_place_new_mirror with new_mirror= the
+preset).  One warm-up frame per route, then --reps rounds (default 7) that alternate the routes frame by frame; the host clock
+around a frame that ends in a synchronise; median and spread (max - min over the median) per route, and the rays that took each
+mirror.  The edit is one elementwise launch per chunk and level in a frame of field passes: nothing is asserted on the times.
+
+    python scripts/bench_apps.py --mirrors 1 2 4 8 [--reps 7] > profiles/mirrors_bench.json
 """
 import argparse
 import json
@@ -314,17 +325,66 @@ def objects_leg(a, models, emb, rays, dev, base_args):
     return res
 
 
+def mirrors_leg(a, models, emb, rays, dev, base_args):
+    """The --mirrors leg (module docstring) -> the result dict."""
+    from types import SimpleNamespace
+    from mirror_nerf_amd import PlacedMirror
+    reps = a.reps
+    args = dict(base_args, max_recursive_level=1, plane_pos="plane_x", root_dir="synthetic", near=1e9)
+    plane = REC.resolve_new_mirror(SimpleNamespace(**args))
+
+    def frame(frame_args, **kw):
+        out = M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=frame_args, trace_secondary_rays=True,
+                                  to_cpu=False, **kw)
+        torch.cuda.synchronize()
+        return out
+
+    def timed(frame_args, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frame(frame_args, **kw)
+        return (time.perf_counter() - t0) * 1e3
+
+    routes = {"legacy": (dict(args, app_place_new_mirror=True), dict(new_mirror=plane))}
+    for K in a.mirrors:
+        copies = [PlacedMirror.axis_aligned(plane["axis"], plane["position"] - 0.05 * k * plane["normal"][0], plane["normal"], plane["rect"])
+                  for k in range(K)]
+        routes[f"K{K}"] = (args, dict(new_mirrors=copies))
+    res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "
+                       "all-mirror random-init pair (bench.py config 2), max_recursive_level 1, near 1e9 (nothing hides a mirror); K copies of the default plane_x "
+                       "preset, copy k moved 0.05 k behind the first",
+           "protocol": f"one warm-up frame per route, then {reps} rounds alternating the routes frame by frame; host clock around a frame "
+                       "that ends in a synchronise; median, spread = (max - min) / median of a route's frames"}
+    times = {name: [] for name in routes}
+    outs = {name: frame(fa, **kw) for name, (fa, kw) in routes.items()}
+    for _ in range(reps):
+        for name, (fa, kw) in routes.items():
+            times[name].append(timed(fa, **kw))
+    for name in routes:
+        ms = statistics.median(times[name])
+        res[name] = {"ms_per_frame": round(ms, 2), "ms_reps": [round(t, 2) for t in times[name]],
+                     "spread": round((max(times[name]) - min(times[name])) / ms, 4),
+                     "merged_mirror_rays_level0": int(outs[name]["mirror_mask_fine"].sum().item())}
+        if name != "legacy":
+            idx = outs[name]["new_mirror_index"]
+            res[name]["rays_that_took_each_mirror"] = torch.bincount(idx[idx >= 0].long(), minlength=int(name[1:])).tolist()
+            res[name]["over_legacy"] = round(ms / statistics.median(times["legacy"]), 4)
+            res[name]["depth_equals_legacy"] = bool(torch.equal(outs[name]["depth_fine"], outs["legacy"]["depth_fine"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=None, help="timed frames per route (default 3; 7 for --objects)")
     ap.add_argument("--objects", type=int, nargs="+", default=None, metavar="K", help="run the several-objects leg instead, for each K (1..8)")
     ap.add_argument("--objects_kind", type=str, default="nerf_pl", choices=("nerf_pl", "d_nerf"))
+    ap.add_argument("--mirrors", type=int, nargs="+", default=None, metavar="K", help="run the several-mirrors leg instead, for each K (1..8)")
     ap.add_argument("--levels", type=int, nargs="+", default=[2, 50])
     ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
     ap.add_argument("--no_dnerf", action="store_true", help="skip the leg with a D-NeRF object")
     ap.add_argument("--obj_bounds", action="store_true", help="run the object-bounds leg instead of the others")
     a = ap.parse_args()
-    a.reps = a.reps or (7 if a.objects else 3)
+    a.reps = a.reps or (7 if (a.objects or a.mirrors) else 3)
     dev = "cuda:0"
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
     emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
@@ -379,6 +439,9 @@ def main():
         return
     if a.objects:
         print(json.dumps(objects_leg(a, models, emb, rays, dev, base_args)))
+        return
+    if a.mirrors:
+        print(json.dumps(mirrors_leg(a, models, emb, rays, dev, base_args)))
         return
     off, ms_off, t_off, traced_off = run(base_args)
     res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "

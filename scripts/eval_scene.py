@@ -47,8 +47,18 @@ single-object rule, so the nearest opaque object wins and a tie in depth goes to
 object j at time_offset + time_scale * i / n; a time outside [0, 1] is refused before the first frame.  The flag replaces
 --obj_ckpt_path and the --obj_* flags and is refused beside them.
 
+New mirrors: --app_place_new_mirror [--plane_pos plane_x | plane_y] places the reference's mirror (run.sh MODE 3; the preset
+follows --root_dir).  --mirrors_json FILE, a JSON list of up to 8 entries
+
+    {"center": [x, y, z], "normal": [x, y, z], "up": [x, y, z], "size": [width, height], "shape": "rect" | "ellipse"}
+    {"axis": "x" | "y", "position": c, "normal": [x, y, z], "rect": [u0, u1, w0, w1], "shape": "rect" | "ellipse"}
+
+(shape is optional) places several mirrors on any plane through batched_inference(new_mirrors=): per ray the nearest one that
+the scene does not hide wins.  It implies tracing, may be combined with --objects_json (a placed object is then seen in the
+placed mirrors) and is refused beside --app_place_new_mirror.
+
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
-and the other scene-editing applications (batched_inference has them; this driver does not expose their flags).  The depth colour table is
+and reflection substitution and roughness control (batched_inference has them; this driver does not expose their flags).  The depth colour table is
 frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -109,7 +119,15 @@ def get_opts(argv=None):
     ap.add_argument("--objects_json", type=str, default=None,
                     help="several placed objects: a JSON list of {ckpt_path, model_type, pose_align, scale, translation, bounds, region, "
                          "bounds_res, time_offset, time_scale}; replaces --obj_ckpt_path and the --obj_* flags")
+    # new mirrors: the reference's single mirror, and several on any plane
+    ap.add_argument("--app_place_new_mirror", action="store_true", help="place the reference's new mirror (the preset of --plane_pos and --root_dir)")
+    ap.add_argument("--plane_pos", type=str, default="plane_x", choices=("plane_x", "plane_y"))
+    ap.add_argument("--mirrors_json", type=str, default=None,
+                    help="several new mirrors: a JSON list of {center, normal, up, size, shape} or {axis, position, normal, rect, shape}")
     args = ap.parse_args(argv)
+    if args.mirrors_json is not None and args.app_place_new_mirror:
+        ap.error("--mirrors_json carries every new mirror: it cannot be combined with --app_place_new_mirror (an entry "
+                 "{axis, position, normal, rect} is that mirror)")
     if args.objects_json is not None:
         given = sorted({a.split("=")[0] for a in (sys.argv[1:] if argv is None else argv) if str(a).startswith("--obj_")})
         if given:
@@ -189,6 +207,36 @@ def read_objects_json(path):
     return out
 
 
+MIRROR_KEYS = {"frame": ("center", "normal", "up", "size"), "axis": ("axis", "position", "normal", "rect")}
+
+
+def read_mirrors_json(path):
+    """--mirrors_json FILE -> the list of PlacedMirror, refused with the file and the entry's index when the file is not what
+    the flag describes.  An entry with the key `axis` is an axis-aligned mirror, any other a mirror on a frame."""
+    import json
+    from mirror_nerf_amd import PlacedMirror
+    with open(path) as f:
+        entries = json.load(f)
+    if not isinstance(entries, list) or not 1 <= len(entries) <= 8:
+        raise SystemExit(f"[Error] {path}: --mirrors_json takes a list of 1..8 mirrors")
+    out = []
+    for j, e in enumerate(entries):
+        if not isinstance(e, dict):
+            raise SystemExit(f"[Error] {path}: mirror {j} is not a JSON object")
+        kind = "axis" if "axis" in e else "frame"
+        known = MIRROR_KEYS[kind] + ("shape",)
+        unknown, missing = sorted(set(e) - set(known)), [k for k in MIRROR_KEYS[kind] if e.get(k) is None]
+        if unknown or missing:
+            raise SystemExit(f"[Error] {path}: mirror {j}: unknown keys {unknown}, missing keys {missing} (known: {sorted(known)}; "
+                             f"or those of the other kind, {sorted(MIRROR_KEYS['frame' if kind == 'axis' else 'axis'])})")
+        try:
+            e = dict(e, shape=e.get("shape") or "rect")
+            out.append(PlacedMirror.axis_aligned(**e) if kind == "axis" else PlacedMirror(**e))
+        except (TypeError, ValueError) as err:
+            raise SystemExit(f"[Error] {path}: mirror {j}: {err}") from None
+    return out
+
+
 def object_time(entry, i, n_frames):
     return float(entry["time_offset"]) + float(entry["time_scale"]) * i / n_frames
 
@@ -264,21 +312,29 @@ def object_bounds(args, obj, frame_time=None):
     return b
 
 
-def render(system, rays, args, obj=None, frame_time=None, placed=None):
+def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=None):
     """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object;
-    placed: the frame's list of PlacedObject (--objects_json), in place of obj."""
+    placed: the frame's list of PlacedObject (--objects_json), in place of obj; mirrors: the list of PlacedMirror
+    (--mirrors_json)."""
+    import torch
     import mirror_nerf_amd as M
     extra = dict(obj or {})
     if placed is not None:
         extra = {"placed_objects": placed}
+    if mirrors is not None:
+        extra["new_mirrors"] = mirrors
     if "render_kwargs_test_d_nerf" in extra:
         extra["frame_time"] = frame_time
     bounds = object_bounds(args, obj, frame_time)
     if bounds is not None:
         extra["object_bounds"] = bounds
-    return M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
-                               args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
-                               white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
+    res = M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
+                              args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
+                              white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
+    for k in ("mirror_mask_fine", "mirror_mask_coarse"):      # a new mirror returns the merged mask as torch.bool (eval.py:492-496)
+        if k in res and res[k].dtype == torch.bool:
+            res[k] = res[k].float()
+    return res
 
 
 def save_pfm(path, image):
@@ -341,6 +397,7 @@ def main(argv=None):
             bank = RayBank.from_blender(args.root_dir, args.split, (w, h), args.near, args.far, device=dev)
         n_frames, frame_of = bank.n_frames, bank.frame
     entries = read_objects_json(args.objects_json) if args.objects_json is not None else None
+    mirrors = read_mirrors_json(args.mirrors_json) if args.mirrors_json is not None else None
     if entries is not None:
         check_object_times(entries, n_frames)
     system = load_system(args, dev)
@@ -372,7 +429,7 @@ def main(argv=None):
         for i in range(n_frames):
             sample = frame_of(i)
             results = render(system, sample["rays"], args, system_obj, frame_time=i / n_frames,      # eval.py:1130
-                             placed=placed_objects(fields, i, n_frames) if fields is not None else None)
+                             placed=placed_objects(fields, i, n_frames) if fields is not None else None, mirrors=mirrors)
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
