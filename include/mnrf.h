@@ -339,6 +339,48 @@ int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirrors, MNRF_HO
                        MNRF_HOST const float* normals, MNRF_HOST const float* rects, float near, float* depth, float* mask,
                        float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any, int32_t* index, void* stream);
 
+/* ---- Mirror roughness on partly mirrored chunks: batched_inference with app_control_mirror_roughness (eval.py:506-511,
+ * 622-674).  csrc/mnrf_rough.hip.
+ *
+ * THE RULE, for a level that traces with roughness on: N rays, the thresholded mask, M = the number of rays with mask != 0,
+ * index[p] = the p-th such ray in order (ONE order-preserving compaction per chunk and level -- the one mnrf_reflect_compact
+ * with compact = 1 writes -- and one host read of its count, whatever trace_ray_times is).
+ *   R, the first secondary render, is as without this rule: at level 0 all N rays are reflected with draw 0 and ray i's row is
+ *     i; at levels >= 1 the M mirror rays are reflected and ray index[p]'s row is p.
+ *   J_j, j = 1 .. trace_ray_times, is the render of the M compacted reflections of the mirror rays about
+ *     l2n(normal + draw_j * std); row p belongs to ray index[p].
+ *   A mirror ray, per colour key present (rgb_coarse, rgb_fine): S = ((R[row] + J_1[p]) + J_2[p]) + ..., single fp32 additions
+ *     in that order; its reflection colour is S finished by trace_ray_times + 1 (below).
+ *   A ray of level 0 that is NOT a mirror ray keeps R[i] unchanged: the mean of the one sample it has (the blend gives it
+ *     weight 0 anyway), so rgb_*_reflect stays a consistent image.
+ * Where M == N this is the reference's arithmetic (eval.py:661-674); where M < N the reference adds (M,3) to (N,3) tensors,
+ * which raises or -- with M == 1 -- broadcasts one ray's colours over the chunk: there is nothing of it to reproduce.
+ * Finish: the reference writes `rgb / (trace_ray_times + 1)` (eval.py:671-674); on the device torch evaluates a division by a
+ * host scalar as a MULTIPLICATION by the fp32 reciprocal 1.f / (float)(times + 1) (tests/test_hip_rough_kernels.py holds the
+ * kernel to torch's own `/`), so the driver passes MNRF_MEAN_MULTIPLY with that reciprocal, formed on the host in fp32. */
+#define MNRF_MEAN_NONE 0       /* mnrf_jitter_mean: add only (every group of jitters but the last) */
+#define MNRF_MEAN_DIVIDE 1     /* ... then a = a / finish_value (an IEEE fp32 division) */
+#define MNRF_MEAN_MULTIPLY 2   /* ... then a = a * finish_value */
+
+/* The n_jit jittered reflections of the m mirror rays of a level in one launch.  rays (n_rays,8), x_surface (n_rays,3), normal
+ * (n_rays,3): the level's; noise (n_jit, n_rays, 3): one (n_rays,3) standard-normal draw per jitter, or null (no jitter:
+ * every block of sec is the same); index (m) int32: the source rays, each in [0, n_rays) (a row that is not is skipped).
+ * Row j * m + p of sec (n_jit * m, 8) = [x_surface_i, r, near2, rays[i][7]] with i = index[p] and r the reflection of ray i about
+ * l2n(normal_i + noise[j][i] * noise_std): mnrf_reflect_compact's expressions in its order, so block j equals the sec_rays of
+ * mnrf_reflect_compact run with compact = 1 and noise[j].  m == 0 returns 0 without a launch; a null pointer other than noise, a
+ * negative size, m > n_rays or n_jit < 1 returns MNRF_ERR_ARG. */
+int mnrf_reflect_jitter_fan(const float* rays, const float* x_surface, const float* normal, const float* noise, float noise_std,
+                            const int32_t* index, int64_t m, int64_t n_rays, int n_jit, float near2, float* sec, void* stream);
+
+/* The sums of THE RULE, in place on acc (n_acc,3).  pieces (n_jit, m, 3): the colours of n_jit jittered renders; index (m) int32
+ * or null.  Per p in [0, m): row = index ? index[p] : p;  a = acc[row];  for j = 0 .. n_jit-1: a = a + pieces[j][p];  then, by
+ * finish_mode, nothing, a = a / finish_value or a = a * finish_value;  acc[row] = a.  Rows of acc that index does not name are
+ * neither read nor written.  Precondition: the rows of index are distinct (it is a compaction) and lie in [0, n_acc) (a row
+ * that does not is skipped); acc and pieces do not overlap.  Calls over consecutive groups of jitters, the last one alone
+ * finishing, perform the additions of one call over all of them.  m == 0 returns 0 without a launch. */
+int mnrf_jitter_mean(float* acc, const float* pieces, const int32_t* index, int64_t m, int n_jit, int64_t n_acc, int finish_mode,
+                     float finish_value, void* stream);
+
 /* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,

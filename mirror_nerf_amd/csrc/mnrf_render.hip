@@ -14,6 +14,7 @@
 #include "mnrf_error.h"
 #include "mnrf_fill.h"
 #include "mnrf_rays.h"
+#include "mnrf_reflect.h"
 
 // ------------------------------------------------------------------ error plumbing
 static thread_local char g_err[512] = "";
@@ -462,21 +463,9 @@ __global__ __launch_bounds__(1024) void reflect_compact_kernel(ReflArgs A) {
         float r[3] = {0.f, 0.f, 0.f};
         bool sel = false;
         if (in) {
-            float nv[3], wvv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                nv[k] = A.normal[i * 3 + k];
-                if (A.normal_noise) nv[k] = nv[k] + A.normal_noise[i * 3 + k] * A.noise_std;   // eval.py:506-511
-                wvv[k] = -A.rays[i * 8 + 3 + k];
-            }
-            // l2_normalize (utils/func.py:5-7) of both, then r = 2 (w.n) n - w
-            const float ninv = 1.f / sqrtf(fmaxf(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2], EPS32));
-            const float winv = 1.f / sqrtf(fmaxf(wvv[0] * wvv[0] + wvv[1] * wvv[1] + wvv[2] * wvv[2], EPS32));
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { nv[k] = nv[k] * ninv; wvv[k] = wvv[k] * winv; }
-            const float c = wvv[0] * nv[0] + wvv[1] * nv[1] + wvv[2] * nv[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) r[k] = 2.f * c * nv[k] - wvv[k];
+            // l2_normalize (utils/func.py:5-7) of normal (+ noise * std, eval.py:506-511) and -d, then r = 2 (w.n) n - w
+            const float d[3] = {A.rays[i * 8 + 3], A.rays[i * 8 + 4], A.rays[i * 8 + 5]};
+            mnrf_reflect::direction(A.normal + i * 3, A.normal_noise ? A.normal_noise + i * 3 : nullptr, A.noise_std, d, r);
             if (A.reflect_dir) { for (int k = 0; k < 3; ++k) A.reflect_dir[i * 3 + k] = r[k]; }
             sel = A.compact ? (A.mask[i] != 0.f) : true;
         }
@@ -513,21 +502,10 @@ __global__ __launch_bounds__(256) void reflect_all_kernel(ReflArgs A) {
     A.n = live_rows(A.n, A.n_live);
     if (i == 0) *A.count = (int)A.n;
     if (i >= A.n) return;
-    float nv[3], wvv[3], r[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        nv[k] = A.normal[i * 3 + k];
-        if (A.normal_noise) nv[k] = nv[k] + A.normal_noise[i * 3 + k] * A.noise_std;   // eval.py:506-511
-        wvv[k] = -A.rays[i * 8 + 3 + k];
-    }
-    // the same expressions, in the same order, as reflect_compact_kernel
-    const float ninv = 1.f / sqrtf(fmaxf(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2], EPS32));
-    const float winv = 1.f / sqrtf(fmaxf(wvv[0] * wvv[0] + wvv[1] * wvv[1] + wvv[2] * wvv[2], EPS32));
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { nv[k] = nv[k] * ninv; wvv[k] = wvv[k] * winv; }
-    const float c = wvv[0] * nv[0] + wvv[1] * nv[1] + wvv[2] * nv[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r[k] = 2.f * c * nv[k] - wvv[k];
+    // the same expressions, in the same order, as reflect_compact_kernel (mnrf_reflect.h)
+    float r[3];
+    const float d[3] = {A.rays[i * 8 + 3], A.rays[i * 8 + 4], A.rays[i * 8 + 5]};
+    mnrf_reflect::direction(A.normal + i * 3, A.normal_noise ? A.normal_noise + i * 3 : nullptr, A.noise_std, d, r);
     if (A.reflect_dir) { for (int k = 0; k < 3; ++k) A.reflect_dir[i * 3 + k] = r[k]; }
     float* o = A.sec + i * 8;
     o[0] = A.x_surface[i * 3]; o[1] = A.x_surface[i * 3 + 1]; o[2] = A.x_surface[i * 3 + 2];

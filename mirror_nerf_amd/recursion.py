@@ -15,7 +15,8 @@ order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
 mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
 mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge; several mirrors on any
-plane, new_mirrors=: mnrf_place_mirrors).  One 4-byte device->host read per level decides
+plane, new_mirrors=: mnrf_place_mirrors); roughness adds mnrf_reflect_jitter_fan and mnrf_jitter_mean.  One 4-byte device->host
+read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
 """
@@ -25,6 +26,7 @@ from collections import defaultdict
 import weakref
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -39,7 +41,11 @@ RAY_FORWARD_OFFSET = 0.1   # train.py:232, eval.py:529 (absolute near of a refle
 # every ray a mirror, against 13.21 ms for the field launch and the compositing launch it replaces
 BLENDED_BREAK_EVEN = 0.37
 _MIRROR_FRACTION = weakref.WeakKeyDictionary()      # model of the selected pass -> {recursion level: share last counted}
-JITTER_RAYS = 262144       # rays per batched group of jittered reflections (roughness, eval.py:622-674)
+# How the mean over the trace_ray_times + 1 samples of a mirror ray ends (eval.py:671-674 `rgb / (trace_ray_times + 1)`): on the
+# device torch evaluates a division by a host scalar as a multiplication by the fp32 reciprocal, and so does mnrf_jitter_mean
+# (tests/test_hip_rough_kernels.py compares the kernel with torch's own `/`); the driver forms 1 / (times + 1) in fp32.
+ROUGH_FINISH = _lib.MNRF_MEAN_MULTIPLY
+JITTER_RAYS = 262144      # rays per batched group of jittered reflections (roughness, eval.py:622-674)
 
 # app_place_new_mirror presets (eval.py:369-433), restated as data: the first entry whose key is a substring of args.root_dir
 # wins (None: the reference's `else`).  position: the plane x = position (plane_x) or y = position (plane_y); rect: the
@@ -436,6 +442,27 @@ def _reflect(rays, x_surface, normal, mask, compact, normal_noise=None, noise_st
     return sec[:M], (index[:M] if compact else None), rdir
 
 
+def _reflect_fan(rays, x_surface, normal, noise, noise_std, index):
+    """The noise.shape[0] jittered reflections of the rays index names, block after block: (n_jit * M, 8)
+    (mnrf_reflect_jitter_fan; block j is what _reflect(..., compact=True, noise[j]) gives)."""
+    n_jit, m = noise.shape[0], index.shape[0]
+    sec = _f(rays.device, n_jit * m, 8)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_reflect_jitter_fan(
+        p(rays), p(x_surface.contiguous()), p(normal.contiguous()), p(noise.contiguous()), float(noise_std), p(index), m,
+        rays.shape[0], n_jit, RAY_FORWARD_OFFSET, p(sec), _lib.stream()), "mnrf_reflect_jitter_fan")
+    return sec
+
+
+def _jitter_mean(acc, pieces, index, m, n_jit, finish=None):
+    """acc[row(p)] += pieces[0][p], then pieces[1][p], ... in place (row(p) = index[p], or p where index is None), then the
+    finish of ROUGH_FINISH with `finish` unless it is None (mnrf_jitter_mean)."""
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_jitter_mean(
+        p(acc), p(pieces.contiguous()), p(index), m, n_jit, acc.shape[0], _lib.MNRF_MEAN_NONE if finish is None else ROUGH_FINISH,
+        0.0 if finish is None else finish, _lib.stream()), "mnrf_jitter_mean")
+
+
 def _blend(base, sec, index, mask, want_reflect):
     """m*part + (1-m)*base with part = sec scattered through index (or sec itself)."""
     N, c = base.shape[0], (base.shape[1] if base.dim() == 2 else 1)
@@ -750,6 +777,20 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     the choice, see stage_a),
     _normal_noise (iterator of pre-drawn (n,3) standard-normal tensors, for tests).
 
+    args.app_control_mirror_roughness with args.trace_ray_times and normal_noise_std= (eval.py:506-511, 622-674), on chunks with
+    ANY share of mirror rays.  THE RULE (include/mnrf.h "Mirror roughness"), at a level that traces: R, the first
+    secondary render, is as without roughness but reflected about l2n(normal + draw_0 * std) -- every ray of the chunk at level 0,
+    the M mirror rays at levels >= 1; J_j, j = 1 .. trace_ray_times, renders the M compacted reflections of the mirror rays about
+    l2n(normal + draw_j * std); a mirror ray's reflection colour is ((R + J_1) + J_2) + ... of its rows, single fp32 additions
+    in that order, finished by trace_ray_times + 1 the way torch's `/` does it on the device: multiplied by the fp32 reciprocal.
+    A ray of level 0 that is NOT a mirror ray keeps its row of R, the one sample it has (the blend gives it weight 0; rgb_*_reflect
+    stays a consistent image).  One (N,3) draw per jitter, in the reference's order.  Where every ray of a chunk is a mirror ray
+    this is the reference's arithmetic; where not, the reference's own addition of (M,3) to (N,3) raises or, with M == 1,
+    broadcasts, so there is nothing of it to reproduce.  One order-preserving compaction of the mask and one host read of its
+    count per chunk and level, whatever trace_ray_times is (mnrf_reflect_compact with compact = 1; then mnrf_reflect_jitter_fan
+    and mnrf_jitter_mean per group of jitters; batch_jitter=False keeps one _reflect, with its count read, per jitter and adds
+    through mnrf_jitter_mean too).
+
     Applications (the reference's flags, unchanged): args.app_place_new_mirror with args.plane_pos / args.root_dir (the
     preset, PLACE_MIRROR_PRESETS) and args.near -- every level below max_recursive_level traces, the new mirror is merged into
     the mirror mask right behind the threshold (mnrf_place_mirror), `new_mirror=dict(axis=, position=, normal=, rect=)`
@@ -998,38 +1039,51 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
             else:
                 r2 = recurse(sec.contiguous(), level + 1)
             if rough:                                                     # eval.py:622-674
+                # THE RULE of include/mnrf.h "Mirror roughness" (DESIGN 4.4b).  The reference adds the (M,3) colours of each
+                # jittered render, M = sum(mask), to the first secondary render, which at level 0 has N rows: that works only
+                # where every ray of the chunk is a mirror ray.  Here the sums go through the compaction's index,
+                # so a mirror ray gets the mean of its times + 1 samples and a ray of level 0 that is no mirror ray keeps the
+                # one sample it has; where M == N it is the reference's arithmetic.
                 times = args.trace_ray_times
+                keys = [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]
+                if times > 0:
+                    # the ONE compaction of the level's mask, and the one host read of its count: every jitter compacts through
+                    # the same mask.  At levels >= 1 the first _reflect above made both; at level 0, which reflects every
+                    # ray, mnrf_reflect_compact runs once more with compact = 1 for its index alone
+                    jit_index = index if only_in else _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, True,
+                                                               want_dir=False)[1]
+                    mj = jit_index.shape[0]
+                    acc_index = None if only_in else jit_index        # row of R: p at levels >= 1, index[p] at level 0
+                    for k in keys:
+                        r2[k] = r2[k].contiguous()
+                    finish = float(np.float32(1) / np.float32(times + 1))   # torch's `/ (times + 1)` on the device: see ROUGH_FINISH
                 if batch_jitter and times > 0:
                     # The reference renders the `times` jittered reflections one after the other (run.sh:187: 64 of them,
                     # each a full secondary render).  Rays are independent, so groups of them go through ONE recursion
                     # call (one field launch per pass for the whole group) and the colours are added in the reference's
-                    # order.  Groups are sized to JITTER_RAYS rays (~2.5 GB of per-sample tensors at 64+128 samples).
+                    # order.  Groups are sized to JITTER_RAYS rays (~2.5 GB of per-sample tensors at 64+128 samples).  A group
+                    # is one buffer of draws (one (N,3) draw per jitter, in the reference's order), one mnrf_reflect_jitter_fan,
+                    # one recursion call and one mnrf_jitter_mean per colour key.
                     # Not used when a test injects the draws: their order interleaves with the nested levels' draws.
-                    mj = max(1, r2[f"rgb_{sel}"].shape[0])     # rows the additions below need (eval.py:663-666)
                     g = 0
                     while g < times:
-                        n_g = max(1, min(times - g, JITTER_RAYS // mj))
-                        secs = [_reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, True, draw(N, dev), noise_std,
-                                         want_dir=False)[0] for _ in range(n_g)]
-                        r3 = recurse(torch.cat(secs, 0).contiguous(), level + 1)
-                        for typ in ("coarse", "fine"):
-                            if f"rgb_{typ}" in r2:
-                                for piece in r3[f"rgb_{typ}"].view(n_g, -1, 3).unbind(0):
-                                    r2[f"rgb_{typ}"] = r2[f"rgb_{typ}"] + piece      # same order of additions as eval.py:663-666
+                        n_g = max(1, min(times - g, JITTER_RAYS // max(1, mj)))
+                        noise = torch.stack([draw(N, dev) for _ in range(n_g)]) if noise_iter is not None \
+                            else torch.randn(n_g, N, 3, device=dev)
+                        r3 = recurse(_reflect_fan(rays_chunk, r[f"x_surface_{sel}"], normal, noise, noise_std, jit_index), level + 1)
                         g += n_g
-                else:
-                    for _ in range(times):
+                        for k in keys:
+                            _jitter_mean(r2[k], r3[k], acc_index, mj, n_g, finish if g >= times else None)
+                elif times > 0:
+                    for j in range(times):
                         s2, _, _ = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, True, draw(N, dev),
                                             noise_std, want_dir=False)
                         r3 = recurse(s2.contiguous(), level + 1)
-                        for typ in ("coarse", "fine"):
-                            if f"rgb_{typ}" in r2:
-                                # the reference adds tensors of M = sum(mask) rows to the first secondary
-                                # render; at level 0 that only works when every ray is a mirror
-                                r2[f"rgb_{typ}"] = r2[f"rgb_{typ}"] + r3[f"rgb_{typ}"]
-                for typ in ("coarse", "fine"):
-                    if f"rgb_{typ}" in r2:
-                        r2[f"rgb_{typ}"] = r2[f"rgb_{typ}"] / (times + 1)
+                        for k in keys:
+                            _jitter_mean(r2[k], r3[k], acc_index, mj, 1, finish if j == times - 1 else None)
+                else:
+                    for k in keys:
+                        r2[k] = r2[k] / (times + 1)
             r[f"rgb_{sel}"], refl = _blend(r[f"rgb_{sel}"], r2[f"rgb_{sel}"], index, mask, True)
             r[f"rgb_{sel}_reflect"] = refl
             if only_in:

@@ -47,6 +47,20 @@ around a frame that ends in a synchronise; median and spread (max - min over the
 mirror.  The edit is one elementwise launch per chunk and level in a frame of field passes: nothing is asserted on the times.
 
     python scripts/bench_apps.py --mirrors 1 2 4 8 [--reps 7] > profiles/mirrors_bench.json
+
+--rough runs the mirror-roughness leg INSTEAD (app_control_mirror_roughness, batched_inference's roughness rule) and prints one
+JSON line with two parts.  (a) the all-mirror BASELINE config 4 workload of benchlegs.roughness_leg's `one_bounce_64_jitters`
+(480x360, 64 + 64 samples, chunk 16384, levels 0 and 1, trace_ray_times 64, std 0.0025): ms per frame as the median of --reps
+(default 7) frames after one warm-up frame, the spread (max - min over the median), and the device->host reads of a compaction's
+count per frame (the calls of recursion._reflect that compact, counted in a frame of their own).  With --parent_root DIR -- a
+built checkout of the parent commit -- the same measurement is taken on that checkout's package too: each tree is measured in
+child processes of its own (--rough_child; --package_root names the tree whose package the child imports), two rounds per tree,
+alternating parent, this, parent, this.  (b) a partly mirrored frame, which the parent cannot render: the STRADDLE random-init
+pair at 800x800, bench.py's sample counts and chunk, one bounce, trace_ray_times 4 and 64: ms per frame (median of 3), the share
+of mirror rays, the count reads, and beside them the estimate t(roughness off) + times x (mirror rays) x c, with c = t(roughness
+off) / (rays the roughness-off frame renders, all levels): the per-ray cost of a render in that frame.  Nothing is asserted.
+
+    python scripts/bench_apps.py --rough [--parent_root DIR] [--reps 7] > profiles/rough_bench.json
 """
 import argparse
 import json
@@ -56,7 +70,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# --package_root DIR (the --rough leg's children): the tree whose mirror_nerf_amd is measured; by default this one
+PACKAGE_ROOT = os.path.abspath(sys.argv[sys.argv.index("--package_root") + 1]) if "--package_root" in sys.argv[1:-1] else ROOT
+sys.path.insert(0, PACKAGE_ROOT)
 
 import torch  # noqa: E402
 
@@ -373,6 +389,98 @@ def mirrors_leg(a, models, emb, rays, dev, base_args):
     return res
 
 
+def _rough_frames(models, emb, rays, n_imp, chunk, args, reps, std):
+    """One warm-up frame, one frame that counts the compacting _reflect calls (each reads its count on the host) and the rows
+    of every render_rays call, then `reps` timed frames -> dict."""
+    def frame():
+        out = M.batched_inference(models, emb, rays, N_SAMPLES, n_imp, False, chunk, args=args, trace_secondary_rays=True,
+                                  normal_noise_std=std, to_cpu=False)
+        torch.cuda.synchronize()
+        return out
+
+    out = frame()
+    reads, rows = [0], [0]
+    reflect, render = REC._reflect, REC.render_rays
+
+    def counting_reflect(rays_, x, n, mask, compact, *a, **k):
+        reads[0] += 1 if compact else 0
+        return reflect(rays_, x, n, mask, compact, *a, **k)
+
+    def counting_render(models_, embeddings, r, *a, **k):
+        rows[0] += int(r.shape[0])
+        return render(models_, embeddings, r, *a, **k)
+
+    REC._reflect, REC.render_rays = counting_reflect, counting_render
+    try:
+        frame()
+    finally:
+        REC._reflect, REC.render_rays = reflect, render
+    times = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frame()
+        times.append((time.perf_counter() - t0) * 1e3)
+    ms = statistics.median(times)
+    mask = out["mirror_mask_fine"] != 0
+    return {"ms_per_frame": round(ms, 1), "ms_reps": [round(t, 1) for t in times], "spread": round((max(times) - min(times)) / ms, 4),
+            "count_reads_per_frame": reads[0], "rays_rendered_per_frame": rows[0], "mirror_share_level0": round(float(mask.float().mean()), 4)}
+
+
+def rough_all_mirror(dev, reps):
+    """Part (a) of the --rough leg on the package this process imported."""
+    models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
+    emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
+    rays = SY.device_rays(360, 480, dev)
+    args = dict(ARGS, max_recursive_level=1, app_control_mirror_roughness=True, trace_ray_times=64)
+    return _rough_frames(models, emb, rays, 64, 16384, args, reps, 0.0025)
+
+
+def rough_leg(a, dev):
+    """The --rough leg (module docstring) -> the result dict."""
+    import subprocess
+    reps = a.reps
+    res = {"workload_a": f"all-mirror random-init pair, 480x360, {N_SAMPLES} + 64 samples, chunk 16384, max_recursive_level 1 (levels 0 and "
+                         "1), trace_ray_times 64, normal_noise_std 0.0025 (benchlegs.roughness_leg one_bounce_64_jitters)",
+           "protocol_a": f"per round a fresh process: one warm-up frame, one counting frame, then {reps} timed frames; host clock around a "
+                         "frame that ends in a synchronise; median, spread = (max - min) / median; rounds alternate parent, this"}
+    if a.parent_root:
+        rounds = {"parent": [], "this": []}
+        for _ in range(2):
+            for name, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--rough_child", "--reps", str(reps), "--package_root", root],
+                                   capture_output=True, text=True)
+                if r.returncode != 0:
+                    raise RuntimeError(f"the {name} round failed: {r.stderr[-2000:]}")
+                rounds[name].append(json.loads(r.stdout.strip().splitlines()[-1]))
+        res.update(rounds)
+        for name in rounds:
+            frames = [t for r in rounds[name] for t in r["ms_reps"]]
+            res[name + "_ms_per_frame"] = round(statistics.median(frames), 1)
+            res[name + "_spread"] = round((max(frames) - min(frames)) / statistics.median(frames), 4)
+        res["this_over_parent"] = round(res["this_ms_per_frame"] / res["parent_ms_per_frame"], 4)
+    else:
+        res["this"] = [rough_all_mirror(dev, reps)]
+    # (b) a partly mirrored frame
+    models, _ = SY.build_models(dev, SY.STRADDLE, seed=0)
+    emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
+    rays = SY.device_rays(H, W, dev)
+    base = dict(ARGS, max_recursive_level=1)
+    off = _rough_frames(models, emb, rays, N_IMPORTANCE, CHUNK, base, 3, 0)
+    per_ray = off["ms_per_frame"] / off["rays_rendered_per_frame"]
+    mirror_rays = round(off["mirror_share_level0"] * rays.shape[0])
+    part = {"workload": f"STRADDLE random-init pair, {W}x{H}, {N_SAMPLES} + {N_IMPORTANCE} samples, chunk {CHUNK}, max_recursive_level 1, "
+                        "normal_noise_std 0.01; the parent raises on this frame",
+            "roughness_off": off, "ms_per_rendered_ray_of_the_roughness_off_frame": per_ray, "mirror_rays_level0": mirror_rays}
+    for times in (4, 64):
+        got = _rough_frames(models, emb, rays, N_IMPORTANCE, CHUNK, dict(base, app_control_mirror_roughness=True, trace_ray_times=times), 3, 0.01)
+        got["estimate_ms"] = round(off["ms_per_frame"] + times * mirror_rays * per_ray, 1)
+        got["measured_over_estimate"] = round(got["ms_per_frame"] / got["estimate_ms"], 4)
+        part[f"trace_ray_times_{times}"] = got
+    res["partly_mirrored"] = part
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=None, help="timed frames per route (default 3; 7 for --objects)")
@@ -383,9 +491,19 @@ def main():
     ap.add_argument("--no_object", action="store_true", help="skip the app_reflect_newly_placed_objects leg")
     ap.add_argument("--no_dnerf", action="store_true", help="skip the leg with a D-NeRF object")
     ap.add_argument("--obj_bounds", action="store_true", help="run the object-bounds leg instead of the others")
+    ap.add_argument("--rough", action="store_true", help="run the mirror-roughness leg instead of the others")
+    ap.add_argument("--parent_root", type=str, default=None, help="--rough: a built checkout of the parent commit to measure beside this tree")
+    ap.add_argument("--rough_child", action="store_true", help="(--rough's child process) part (a) on the package of --package_root")
+    ap.add_argument("--package_root", type=str, default=None, metavar="DIR", help="(--rough's child process) the tree whose package is imported")
     a = ap.parse_args()
-    a.reps = a.reps or (7 if (a.objects or a.mirrors) else 3)
+    a.reps = a.reps or (7 if (a.objects or a.mirrors or a.rough or a.rough_child) else 3)
     dev = "cuda:0"
+    if a.rough_child:
+        print(json.dumps(rough_all_mirror(dev, a.reps)))
+        return
+    if a.rough:
+        print(json.dumps(rough_leg(a, dev)))
+        return
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
     emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
     rays = SY.device_rays(H, W, dev)

@@ -57,9 +57,18 @@ follows --root_dir).  --mirrors_json FILE, a JSON list of up to 8 entries
 the scene does not hide wins.  It implies tracing, may be combined with --objects_json (a placed object is then seen in the
 placed mirrors) and is refused beside --app_place_new_mirror.
 
-Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader
-and reflection substitution and roughness control (batched_inference has them; this driver does not expose their flags).  The depth colour table is
-frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no CPU path.
+Mirror roughness (run.sh "control_mirror_roughness"): --app_control_mirror_roughness --trace_ray_times T --normal_noise_std S
+renders every mirror pixel as the mean of T + 1 reflections about jittered normals (batched_inference's roughness rule: a
+frame may hold any share of mirror pixels; a pixel that is no mirror keeps its single reflection sample in rgb_*_reflect).
+--normal_noise_std_changes lets S follow the reference's per-frame cycle (eval.py:1130-1136): frame i of n uses
+S * c with p = i / n and c = 2 p below one half, 1 - 2 (p - 0.5) from there on.  The flag is refused beside the object and
+new-mirror applications, with batched_inference's own messages.
+
+Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader,
+reflection substitution (batched_inference has it; this driver does not expose its flags) and --render_coarse_rgb (it sets
+test_time=False and writes a second set of coarse images, eval.py:1148, 1178: the driver renders with test_time=True only).  The
+depth colour table is frames.jet_table(), a restatement that is not pinned against cv2.COLORMAP_JET.  Needs a GPU: there is no
+CPU path.
 """
 import argparse
 import os
@@ -124,7 +133,25 @@ def get_opts(argv=None):
     ap.add_argument("--plane_pos", type=str, default="plane_x", choices=("plane_x", "plane_y"))
     ap.add_argument("--mirrors_json", type=str, default=None,
                     help="several new mirrors: a JSON list of {center, normal, up, size, shape} or {axis, position, normal, rect, shape}")
+    # mirror roughness, named as in the reference's eval.py:60-70
+    ap.add_argument("--app_control_mirror_roughness", action="store_true",
+                    help="render mirror pixels as the mean of trace_ray_times + 1 reflections about jittered normals")
+    ap.add_argument("--trace_ray_times", type=int, default=4, help="jittered reflections per mirror pixel beside the first")
+    ap.add_argument("--normal_noise_std", type=float, default=0.01, help="standard deviation of the jitter added to the normal")
+    ap.add_argument("--normal_noise_std_changes", action="store_true",
+                    help="scale --normal_noise_std by the frame's place in the split: 0 -> 1 -> 0 (eval.py:1130-1136)")
     args = ap.parse_args(argv)
+    if args.app_control_mirror_roughness:      # batched_inference's own refusals (_refuse_apps), before anything is loaded
+        if args.trace_ray_times < 0:
+            ap.error("--trace_ray_times counts renders: it cannot be negative")
+        if args.app_reflect_newly_placed_objects:
+            ap.error("app_reflect_newly_placed_objects cannot be combined with app_control_mirror_roughness (one application at a time)")
+        if args.app_place_new_mirror:
+            ap.error("app_control_mirror_roughness cannot be combined with app_place_new_mirror (one application at a time, except "
+                     "place-mirror with substitution)")
+        if args.mirrors_json is not None:
+            ap.error("app_control_mirror_roughness cannot be combined with new_mirrors= (one application at a time, except "
+                     "placed mirrors with placed objects or substitution)")
     if args.mirrors_json is not None and args.app_place_new_mirror:
         ap.error("--mirrors_json carries every new mirror: it cannot be combined with --app_place_new_mirror (an entry "
                  "{axis, position, normal, rect} is that mirror)")
@@ -312,10 +339,18 @@ def object_bounds(args, obj, frame_time=None):
     return b
 
 
-def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=None):
+def frame_noise_std(args, i, n_frames):
+    """eval.py:1130-1136: the jitter of frame i of n -- --normal_noise_std, or with --normal_noise_std_changes that value
+    times a cycle that rises from 0 to 1 over the first half of the split and falls back over the second."""
+    progress = i / n_frames
+    cycle = progress * 2 if progress < 0.5 else 1 - (progress - 0.5) * 2
+    return args.normal_noise_std * cycle if args.normal_noise_std_changes else args.normal_noise_std
+
+
+def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=None, normal_noise_std=0):
     """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object;
     placed: the frame's list of PlacedObject (--objects_json), in place of obj; mirrors: the list of PlacedMirror
-    (--mirrors_json)."""
+    (--mirrors_json); normal_noise_std: the frame's jitter (--app_control_mirror_roughness)."""
     import torch
     import mirror_nerf_amd as M
     extra = dict(obj or {})
@@ -330,7 +365,7 @@ def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=N
         extra["object_bounds"] = bounds
     res = M.batched_inference(system.models, system.embeddings, rays, args.N_samples, args.N_importance, args.use_disp,
                               args.chunk, args=args, trace_secondary_rays=args.trace_secondary_rays,
-                              white_back=args.white_back, to_cpu=False, maps_only=True, **extra)
+                              white_back=args.white_back, to_cpu=False, maps_only=True, normal_noise_std=normal_noise_std, **extra)
     for k in ("mirror_mask_fine", "mirror_mask_coarse"):      # a new mirror returns the merged mask as torch.bool (eval.py:492-496)
         if k in res and res[k].dtype == torch.bool:
             res[k] = res[k].float()
@@ -429,7 +464,8 @@ def main(argv=None):
         for i in range(n_frames):
             sample = frame_of(i)
             results = render(system, sample["rays"], args, system_obj, frame_time=i / n_frames,      # eval.py:1130
-                             placed=placed_objects(fields, i, n_frames) if fields is not None else None, mirrors=mirrors)
+                             placed=placed_objects(fields, i, n_frames) if fields is not None else None, mirrors=mirrors,
+                             normal_noise_std=frame_noise_std(args, i, n_frames))
             typ = "fine" if "rgb_fine" in results else "coarse"
             want = [s for s in frames.STEMS if s != "depth" or depth_png]
             images = frames.finish_frame(results, typ, split_extrema=extrema, want=want)
