@@ -381,7 +381,43 @@ int mnrf_reflect_jitter_fan(const float* rays, const float* x_surface, const flo
 int mnrf_jitter_mean(float* acc, const float* pieces, const int32_t* index, int64_t m, int n_jit, int64_t n_acc, int finish_mode,
                      float finish_value, void* stream);
 
-/* Backward of mnrf_composite (training).  Inputs: the forward inputs (rays, sigma, z_vals, noise,
+/* ---- A roughness per mirror: batched_inference(rough_times=T, scene_roughness=, new_mirrors=[PlacedMirror(..., roughness=)]).
+ * csrc/mnrf_rough.hip.  Not the reference's flag (one std for every mirror ray of the frame, above): the std is a per-ray row.
+ *
+ * THE RULE, for a level that traces: N rays, the thresholded (and merged) mask, and index (N int32) as mnrf_place_mirrors wrote
+ * it at THIS level -- -1 everywhere where no list is placed or the level places none; K mirrors with roughness[k] >= 0.
+ *   std_i = roughness[index_i] where 0 <= index_i < K, otherwise scene_roughness (an index outside [-1, K) counts as -1).
+ *   The first reflection (every ray at level 0, the mirror rays at levels >= 1) is taken about l2n(normal_i + draw_0[i] * std_i)
+ *     where std_i > 0 and about l2n(normal_i), with NO addition, where std_i == 0: the bits of the frame without roughness, a
+ *     -0 component included.
+ *   J = {i : mask_i != 0 and std_i > 0}.  Each ray of J gets T further reflections about l2n(normal_i + draw_j[i] * std_i),
+ *     j = 1 .. T; its reflection colour is ((R + J_1) + J_2) + ... finished as above by T + 1, added through the index of ONE
+ *     order-preserving compaction of J per chunk and level.  A mirror ray outside J (a polished mirror) and a ray of level 0
+ *     that is no mirror ray keep the single sample they have.
+ *   Draws: one (N,3) draw for the first reflection of every tracing level, then T more iff J is not empty at that level -- so
+ *     where every std equals S > 0 the draws, the launches' inputs and the result are those of "Mirror roughness" above with
+ *     trace_ray_times = T and std S.  Count reads: the mask's (levels >= 1) plus J's per chunk and level, whatever T is. */
+
+/* std_rows (n_rays) = std_i of THE RULE; jitter_mask (n_rays) = 1.f where ray i is in J, else 0.f; *any (int32, device, caller
+ * zeroes it, null = skip) is OR-ed with "J is not empty".  index (n_rays int32): null = all -1; mask (n_rays); n_mirrors in
+ * 0..MNRF_MIRRORS_MAX; roughness: a HOST array of n_mirrors floats (null allowed where n_mirrors == 0), each finite and >= 0, as
+ * scene_roughness; they travel in the kernel's argument block.  n_rays == 0 returns 0 without a launch. */
+int mnrf_rough_rows(const int32_t* index, const float* mask, int64_t n_rays, int n_mirrors, MNRF_HOST const float* roughness,
+                    float scene_roughness, float* std_rows, float* jitter_mask, int32_t* any, void* stream);
+
+/* out (n_rays,3): per component out_i = std_rows[i] > 0 ? normal_i + noise_i * std_rows[i] : normal_i -- one multiplication and
+ * one addition, mnrf_reflect.h's own, or the untouched value.  mnrf_reflect_compact with a null noise pointer on `out` then gives
+ * the bits it gives on `normal` with the noise and the std.  normal, noise (n_rays,3); out does not overlap them. */
+int mnrf_perturb_normals(const float* normal, const float* noise, const float* std_rows, int64_t n_rays, float* out, void* stream);
+
+/* mnrf_reflect_jitter_fan with the std of source ray i = std_rows[i] (n_rays) in place of noise_std: the same layout (row
+ * j * m + p of sec is ray index[p] with draw noise[j][index[p]]), the same expressions (mnrf_reflect.h), the same refusals;
+ * std_rows must not be null.  m == 0 returns 0 without a launch; a row whose index is outside [0, n_rays) is not written. */
+int mnrf_reflect_jitter_fan_rows(const float* rays, const float* x_surface, const float* normal, const float* noise,
+                                 const float* std_rows, const int32_t* index, int64_t m, int64_t n_rays, int n_jit, float near2,
+                                 float* sec, void* stream);
+
+/* Backward of mnrf_composite (training). Inputs: the forward inputs (rays, sigma, z_vals, noise,
  * rgb, is_mirror, pred_normal, normal), the forward outputs weights (n_rays,S) and depth (n_rays),
  * and the upstream gradients of every per-ray output (null = zero): g_weights (n_rays,S), g_opacity,
  * g_rgb_map (.,3), g_depth, g_mirror_mask, g_surf_normal (.,3), g_surf_normal_grad (.,3),

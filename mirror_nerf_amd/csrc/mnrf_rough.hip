@@ -13,6 +13,14 @@
 // jitter_mean_kernel: acc[row(p)] = ((acc[row(p)] + pieces[0][p]) + pieces[1][p]) + ..., then the finish -- single fp32 additions
 // in the order the reference adds its renders (eval.py:661-666).  One thread per (p, channel): the pieces are read coalesced,
 // 12 B per row and jitter; rows of acc that index does not name are neither read nor written.
+//
+// A roughness per placed mirror (include/mnrf.h "A roughness per mirror", batched_inference rough_times=): the standard deviation
+// becomes a per-ray row.  rough_rows_kernel forms it from the index mnrf_place_mirrors wrote (std_rows) together with the 0/1
+// mask of the jitter set J = {mask != 0 and std > 0} and its "any" flag; perturb_normals_kernel adds draw * std to the normals
+// of the rays with std > 0 and copies the others untouched (no `+ 0`: a -0 stays -0), so mnrf_reflect_compact without noise
+// then evaluates mnrf_reflect.h's remaining operations on them; reflect_jitter_fan_rows_kernel is reflect_jitter_fan_kernel with
+// std_rows[i] in place of the call's one std (one body, a template flag).  All three one thread per ray (or per 4 floats),
+// 256 threads per workgroup, memory-bound.
 // Compiled with -ffp-contract=off and IEEE division, as the rest of the library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,9 +33,11 @@ namespace {
 
 struct FanArgs {
     const float* rays; const float* x_surface; const float* normal; const float* noise; float noise_std;
+    const float* std_rows;                             // ROWS: the std of source ray i is std_rows[i], noise_std is not read
     const int* index; long long m, n_rays, total; float near2; float* sec; int wide;
 };
 
+template <bool ROWS>
 __global__ __launch_bounds__(256) void reflect_jitter_fan_kernel(FanArgs A) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // row j * m + p of sec
     if (t >= A.total) return;
@@ -44,7 +54,8 @@ __global__ __launch_bounds__(256) void reflect_jitter_fan_kernel(FanArgs A) {
         d[0] = q[3]; d[1] = q[4]; d[2] = q[5]; far = q[7];
     }
     float r[3];
-    mnrf_reflect::direction(A.normal + i * 3, A.noise ? A.noise + (j * A.n_rays + i) * 3 : nullptr, A.noise_std, d, r);
+    mnrf_reflect::direction(A.normal + i * 3, A.noise ? A.noise + (j * A.n_rays + i) * 3 : nullptr, ROWS ? A.std_rows[i] : A.noise_std,
+                            d, r);
     const float* x = A.x_surface + i * 3;
     if (A.wide) {
         float4* o = reinterpret_cast<float4*>(A.sec) + t * 2;
@@ -75,6 +86,48 @@ __global__ __launch_bounds__(256) void jitter_mean_kernel(float* __restrict__ ac
     acc[row * 3 + ch] = a;
 }
 
+struct RowsArgs {
+    const int* index; const float* mask; long long n; int K; float rough[MNRF_MIRRORS_MAX]; float scene;
+    float* std_rows; float* jitter_mask; int* any;
+};
+
+__global__ __launch_bounds__(256) void rough_rows_kernel(RowsArgs A) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool in_j = false;
+    if (i < A.n) {
+        const int idx = A.index ? A.index[i] : -1;
+        float s = A.scene;                             // no placed mirror taken, or an index outside [-1, K): the scene's own
+#pragma unroll
+        for (int k = 0; k < MNRF_MIRRORS_MAX; ++k)     // (a select per mirror: the table stays in the argument registers)
+            if (k < A.K && idx == k) s = A.rough[k];
+        in_j = A.mask[i] != 0.f && s > 0.f;
+        A.std_rows[i] = s;
+        A.jitter_mask[i] = in_j ? 1.f : 0.f;
+    }
+    if (A.any && __ballot(in_j) != 0ull && (threadIdx.x & 63) == 0) atomicOr(A.any, 1);
+}
+
+// element e of the flat (n_rays * 3) arrays belongs to ray e / 3
+__device__ __forceinline__ float perturbed(float nrm, float draw, float s) { return s > 0.f ? nrm + draw * s : nrm; }
+
+__global__ __launch_bounds__(256) void perturb_normals_kernel(const float* __restrict__ normal, const float* __restrict__ noise,
+                                                              const float* __restrict__ std_rows, long long total, int wide,
+                                                              float* __restrict__ out) {
+    const long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;      // four consecutive floats per thread
+    if (e0 >= total) return;
+    if (wide && e0 + 4 <= total) {                     // 16-byte aligned bases and a whole word: one 16-byte access per array
+        const float4 a = *reinterpret_cast<const float4*>(normal + e0), b = *reinterpret_cast<const float4*>(noise + e0);
+        float4 o;
+        o.x = perturbed(a.x, b.x, std_rows[(e0 + 0) / 3]);
+        o.y = perturbed(a.y, b.y, std_rows[(e0 + 1) / 3]);
+        o.z = perturbed(a.z, b.z, std_rows[(e0 + 2) / 3]);
+        o.w = perturbed(a.w, b.w, std_rows[(e0 + 3) / 3]);
+        *reinterpret_cast<float4*>(out + e0) = o;
+    } else {
+        for (long long e = e0; e < e0 + 4 && e < total; ++e) out[e] = perturbed(normal[e], noise[e], std_rows[e / 3]);
+    }
+}
+
 }  // namespace
 
 extern "C" int mnrf_reflect_jitter_fan(const float* rays, const float* x_surface, const float* normal, const float* noise,
@@ -91,8 +144,60 @@ extern "C" int mnrf_reflect_jitter_fan(const float* rays, const float* x_surface
     A.rays = rays; A.x_surface = x_surface; A.normal = normal; A.noise = noise; A.noise_std = noise_std;
     A.index = index; A.m = (long long)m; A.n_rays = (long long)n_rays; A.total = total; A.near2 = near2; A.sec = sec;
     A.wide = (((uintptr_t)rays | (uintptr_t)sec) & 15u) == 0;
-    hipLaunchKernelGGL(reflect_jitter_fan_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(reflect_jitter_fan_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
     return mnrf_check_launch("mnrf_reflect_jitter_fan");
+}
+
+extern "C" int mnrf_reflect_jitter_fan_rows(const float* rays, const float* x_surface, const float* normal, const float* noise,
+                                            const float* std_rows, const int32_t* index, int64_t m, int64_t n_rays, int n_jit,
+                                            float near2, float* sec, void* stream) {
+    if (m < 0 || n_rays < 0 || n_rays > 0x7fffffffLL || m > n_rays) return mnrf_fail(MNRF_ERR_ARG, "mnrf_reflect_jitter_fan_rows: bad size");
+    if (n_jit < 1) return mnrf_fail(MNRF_ERR_ARG, "mnrf_reflect_jitter_fan_rows: n_jit must be at least 1");
+    if (m == 0) return MNRF_OK;
+    if (!rays || !x_surface || !normal || !std_rows || !index || !sec)
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_reflect_jitter_fan_rows: null pointer");
+    const long long total = (long long)m * n_jit;
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return mnrf_fail(MNRF_ERR_ARG, "mnrf_reflect_jitter_fan_rows: n_jit * m is too large for one launch");
+    FanArgs A{};
+    A.rays = rays; A.x_surface = x_surface; A.normal = normal; A.noise = noise; A.std_rows = std_rows;
+    A.index = index; A.m = (long long)m; A.n_rays = (long long)n_rays; A.total = total; A.near2 = near2; A.sec = sec;
+    A.wide = (((uintptr_t)rays | (uintptr_t)sec) & 15u) == 0;
+    hipLaunchKernelGGL(reflect_jitter_fan_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_reflect_jitter_fan_rows");
+}
+
+extern "C" int mnrf_rough_rows(const int32_t* index, const float* mask, int64_t n_rays, int n_mirrors, const float* roughness,
+                               float scene_roughness, float* std_rows, float* jitter_mask, int32_t* any, void* stream) {
+    if (n_rays < 0 || n_rays > 0x7fffffffLL) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: bad size");
+    if (n_mirrors < 0 || n_mirrors > MNRF_MIRRORS_MAX) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: n_mirrors must be in 0..8");
+    if (n_mirrors > 0 && !roughness) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: the per-mirror host array is null");
+    RowsArgs A{};
+    for (int k = 0; k < n_mirrors; ++k) {
+        if (!(roughness[k] >= 0.f) || roughness[k] > 3.402823466e+38f)
+            return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: a roughness must be finite and not negative");
+        A.rough[k] = roughness[k];
+    }
+    if (!(scene_roughness >= 0.f) || scene_roughness > 3.402823466e+38f)
+        return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: scene_roughness must be finite and not negative");
+    if (n_rays == 0) return MNRF_OK;
+    if (!mask || !std_rows || !jitter_mask) return mnrf_fail(MNRF_ERR_ARG, "mnrf_rough_rows: null pointer");
+    A.index = index; A.mask = mask; A.n = (long long)n_rays; A.K = n_mirrors; A.scene = scene_roughness;
+    A.std_rows = std_rows; A.jitter_mask = jitter_mask; A.any = any;
+    hipLaunchKernelGGL(rough_rows_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch("mnrf_rough_rows");
+}
+
+extern "C" int mnrf_perturb_normals(const float* normal, const float* noise, const float* std_rows, int64_t n_rays, float* out,
+                                    void* stream) {
+    if (n_rays < 0 || n_rays > 0x7fffffffLL) return mnrf_fail(MNRF_ERR_ARG, "mnrf_perturb_normals: bad size");
+    if (n_rays == 0) return MNRF_OK;
+    if (!normal || !noise || !std_rows || !out) return mnrf_fail(MNRF_ERR_ARG, "mnrf_perturb_normals: null pointer");
+    const long long total = (long long)n_rays * 3;
+    const int wide = (((uintptr_t)normal | (uintptr_t)noise | (uintptr_t)out) & 15u) == 0;
+    hipLaunchKernelGGL(perturb_normals_kernel, dim3((unsigned)(((total + 3) / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       normal, noise, std_rows, total, wide, out);
+    return mnrf_check_launch("mnrf_perturb_normals");
 }
 
 extern "C" int mnrf_jitter_mean(float* acc, const float* pieces, const int32_t* index, int64_t m, int n_jit, int64_t n_acc,

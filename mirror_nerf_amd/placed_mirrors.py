@@ -13,6 +13,11 @@ One deliberate difference from the single mirror: the reference writes the plane
 BEFORE its two filters (eval.py:458-460), so a second mirror behind the first would overwrite the normal of rays that hit the
 first.  Here the normal of a ray that is inside a shape but takes no mirror is kept.  The device pass is mnrf_place_mirrors,
 one launch for the whole list.
+
+A mirror may be frosted: `roughness` is the standard deviation of the normal jitter of the rays that take it, read by
+`batched_inference(rough_times=T, scene_roughness=S)` alone (include/mnrf.h "A roughness per mirror"): those rays
+get the mean of T + 1 reflections about jittered normals, the rays of a polished mirror are traced once.  roughness_row packs the
+list's values for mnrf_rough_rows; without rough_times a list that holds a frosted mirror is refused.
 """
 import ctypes
 
@@ -20,7 +25,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors"]
+__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors", "roughness_row"]
 
 MAX_MIRRORS = 8      # MNRF_MIRRORS_MAX
 SHAPES = ("rect", "ellipse")
@@ -42,10 +47,21 @@ def _vec(v, n, what):
     return a
 
 
+def _roughness(v, what="PlacedMirror: roughness"):
+    """A standard deviation of the normal jitter: rounded once to float32; refused when negative, NaN or infinite."""
+    try:
+        s = np.float32(v)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{what} is one number, not {v!r}") from None
+    if np.ndim(s) != 0 or not np.isfinite(s) or s < 0:
+        raise ValueError(f"{what} must be finite and not negative, not {v!r}")
+    return float(s)
+
+
 class PlacedMirror:
     """One mirror of `new_mirrors=`.
 
-    PlacedMirror(center, normal, up, size=(width, height), shape="rect" | "ellipse"): the plane through `center` with normal
+    PlacedMirror(center, normal, up, size=(width, height), shape="rect" | "ellipse", roughness=0.0): the plane through `center` with normal
     `normal` (the side the mirror faces); `up` fixes the rotation about the normal -- the height runs along the part of `up` that
     lies in the plane, the width along cross(that, normal).  The frame is built in float64 and rounded once to float32:
         n = normal / |normal|,  e_w = normalize(up - (up . n) n),  e_u = normalize(cross(e_w, n)),
@@ -53,13 +69,19 @@ class PlacedMirror:
     The float64 frame stays in .frame64 (rows n, e_u, e_w).  Refused: a zero normal, an up parallel to the normal, a size that is
     not positive, input that is not finite.
 
-    PlacedMirror.axis_aligned(axis, position, normal, rect, shape="rect"): the mirror of `new_mirror=`, on the plane
-    x = position (axis "x", rect = (y0, y1, z0, z1)) or y = position (axis "y", rect = (x0, x1, z0, z1)); `normal` is what is
-    written to the rays that take it, as given."""
+    PlacedMirror.axis_aligned(axis, position, normal, rect, shape="rect", roughness=0.0): the mirror of `new_mirror=`, on the
+    plane x = position (axis "x", rect = (y0, y1, z0, z1)) or y = position (axis "y", rect = (x0, x1, z0, z1)); `normal` is what
+    is written to the rays that take it, as given.
 
-    def __init__(self, center, normal, up, size, shape="rect"):
+    roughness: the standard deviation of the normal jitter of the rays that take this mirror (0: polished), rounded once to
+    float32 and kept as .roughness; negative, NaN and infinite are refused.  It is used by `batched_inference(rough_times=T)`
+    alone -- a call without rough_times refuses a list that holds a mirror with roughness > 0.  It is not a key
+    of as_dict(): mnrf_place_mirrors does not receive it."""
+
+    def __init__(self, center, normal, up, size, shape="rect", roughness=0.0):
         if shape not in SHAPES:
             raise ValueError(f"PlacedMirror: shape must be 'rect' or 'ellipse', not {shape!r}")
+        self.roughness = _roughness(roughness)
         c, n, up, size = _vec(center, 3, "center"), _vec(normal, 3, "normal"), _vec(up, 3, "up"), _vec(size, 2, "size")
         if not (size > 0.0).all():
             raise ValueError(f"PlacedMirror: size = (width, height) must be positive, not {tuple(size)}")
@@ -85,7 +107,7 @@ class PlacedMirror:
         self.axis, self.position = None, None
 
     @classmethod
-    def axis_aligned(cls, axis, position, normal, rect, shape="rect"):
+    def axis_aligned(cls, axis, position, normal, rect, shape="rect", roughness=0.0):
         if shape not in SHAPES:
             raise ValueError(f"PlacedMirror: shape must be 'rect' or 'ellipse', not {shape!r}")
         if axis not in ("x", "y"):
@@ -93,6 +115,7 @@ class PlacedMirror:
         n, rect = _vec(normal, 3, "normal"), _vec(rect, 4, "rect")
         position = _vec([position], 1, "position")[0]
         self = cls.__new__(cls)
+        self.roughness = _roughness(roughness)
         self.kind, self.shape, self.frame64 = "axis", shape, None
         self.axis, self.position = axis, _f32(position)
         self.normal = tuple(_f32(v) for v in n)
@@ -106,9 +129,10 @@ class PlacedMirror:
                     e_u=self.e_u, e_w=self.e_w, rect=self.rect)
 
     def __repr__(self):
+        rough = f", roughness={self.roughness}" if self.roughness != 0 else ""
         if self.kind == "axis":
-            return f"PlacedMirror.axis_aligned({self.axis!r}, {self.position}, normal={self.normal}, rect={self.rect}, shape={self.shape!r})"
-        return f"PlacedMirror(center={self.center}, normal={self.normal}, e_u={self.e_u}, e_w={self.e_w}, rect={self.rect}, shape={self.shape!r})"
+            return f"PlacedMirror.axis_aligned({self.axis!r}, {self.position}, normal={self.normal}, rect={self.rect}, shape={self.shape!r}{rough})"
+        return f"PlacedMirror(center={self.center}, normal={self.normal}, e_u={self.e_u}, e_w={self.e_w}, rect={self.rect}, shape={self.shape!r}{rough})"
 
 
 def refuse(args, models, kwargs):
@@ -138,6 +162,20 @@ def refuse(args, models, kwargs):
                          "predicted mirror mask, and substitution replaces what the mask marks")
     if getattr(args, "near", None) is None:
         raise ValueError("new_mirrors= needs args.near: the foreground test compares the depth with it (eval.py:169-171)")
+    if kwargs.get("rough_times") is None:
+        for k, m in enumerate(mirrors):
+            if getattr(m, "roughness", 0.0) > 0:
+                raise ValueError(f"new_mirrors[{k}] has roughness {m.roughness}, which only the per-mirror roughness route reads: pass "
+                                 "rough_times=T (the number of jittered reflections beside the first) to batched_inference")
+
+
+def roughness_row(mirrors):
+    """The host array of mnrf_rough_rows for a list of PlacedMirror (or none): (K, roughness[K])."""
+    K = len(mirrors) if mirrors is not None else 0
+    row = (ctypes.c_float * max(K, 1))()
+    for k in range(K):
+        row[k] = mirrors[k].roughness
+    return K, row
 
 
 def pack(mirrors):

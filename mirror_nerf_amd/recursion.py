@@ -15,7 +15,8 @@ order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
 mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
 mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge; several mirrors on any
-plane, new_mirrors=: mnrf_place_mirrors); roughness adds mnrf_reflect_jitter_fan and mnrf_jitter_mean.  One 4-byte device->host
+plane, new_mirrors=: mnrf_place_mirrors); roughness adds mnrf_reflect_jitter_fan and mnrf_jitter_mean (a roughness per
+mirror, rough_times=: mnrf_rough_rows, mnrf_perturb_normals and mnrf_reflect_jitter_fan_rows beside them).  One 4-byte device->host
 read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
 through `mirror_mask.bool().any()` (train.py:175, eval.py:315).
@@ -169,11 +170,46 @@ def load_object_system(ckpt_path, device, N_importance=64, trusted=False):
     return SimpleNamespace(models=models, embeddings={"xyz": Embedding(10), "dir": Embedding(4)})
 
 
+def resolve_rough_rows(kwargs):
+    """rough_times=, scene_roughness= -> (T, the scene's own std as a float32 value), or (None, 0.0) where rough_times is not given."""
+    times = kwargs.get("rough_times")
+    if times is None:
+        return None, 0.0
+    if isinstance(times, bool) or not isinstance(times, (int, np.integer)) or times < 1:
+        raise ValueError(f"rough_times is an int of at least 1 (the jittered reflections beside the first; None: off), not {times!r}")
+    from .placed_mirrors import _roughness
+    return int(times), _roughness(kwargs.get("scene_roughness", 0.0), "scene_roughness")
+
+
+def _refuse_rough_rows(args, kwargs):
+    """The refusals of rough_times= (a roughness per mirror), each with its reason."""
+    resolve_rough_rows(kwargs)
+    if getattr(args, "app_control_mirror_roughness", False):
+        raise ValueError("rough_times= cannot be combined with app_control_mirror_roughness: one roughness rule per call (the flag "
+                         "jitters every mirror ray with normal_noise_std=; rough_times= takes the std per mirror and scene_roughness=)")
+    if getattr(args, "app_place_new_mirror", False) or kwargs.get("new_mirror") is not None:
+        raise ValueError("rough_times= cannot be combined with app_place_new_mirror or new_mirror= (the single mirror carries no "
+                         "roughness; PlacedMirror.axis_aligned(..., roughness=) in new_mirrors= takes its keys)")
+    from .placed_objects import SINGLE_OBJECT_KEYWORDS
+    given = [k for k in SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
+    if given or (getattr(args, "app_reflect_newly_placed_objects", False) and kwargs.get("placed_objects") is None):
+        raise ValueError("rough_times= is combined with objects through placed_objects=[PlacedObject(...), ...], not with the "
+                         f"single-object keywords ({', '.join(k + '=' for k in given) or 'app_reflect_newly_placed_objects without placed_objects='})")
+    if getattr(args, "app_reflection_substitution", False):
+        raise ValueError("rough_times= cannot be combined with app_reflection_substitution (the substituted render is traced once, "
+                         "without the recursion the jitters go through)")
+
+
 def _refuse_apps(args, models, kwargs):
     """The application flags batched_inference cannot honour, refused up front with the reason."""
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))
     multi = kwargs.get("new_mirrors") is not None
+    if kwargs.get("rough_times") is not None:         # a roughness per mirror (DESIGN 4.4c): allowed alone, beside new_mirrors=
+        _refuse_rough_rows(args, kwargs)              # and beside placed_objects=; those keep their own refusals, below
+    elif kwargs.get("scene_roughness") not in (None, 0, 0.0):
+        raise ValueError(f"scene_roughness={kwargs['scene_roughness']!r} is read by the per-mirror roughness route alone: pass "
+                         "rough_times=T (the number of jittered reflections beside the first)")
     if multi:                                         # its own refusals; what it is allowed beside keeps its own, below
         from .placed_mirrors import refuse as refuse_mirrors
         refuse_mirrors(args, models, kwargs)
@@ -451,6 +487,37 @@ def _reflect_fan(rays, x_surface, normal, noise, noise_std, index):
     _lib.check(_lib.lib().mnrf_reflect_jitter_fan(
         p(rays), p(x_surface.contiguous()), p(normal.contiguous()), p(noise.contiguous()), float(noise_std), p(index), m,
         rays.shape[0], n_jit, RAY_FORWARD_OFFSET, p(sec), _lib.stream()), "mnrf_reflect_jitter_fan")
+    return sec
+
+
+def _rough_rows(index, mask, rough_row, scene_roughness, flag=None):
+    """-> (std_rows (N,), jitter_mask (N,)): the std of every ray and the 0/1 mask of the jitter set J (mnrf_rough_rows).  index:
+    (N,) int32 as mnrf_place_mirrors wrote it at this level, or None (all -1); rough_row: placed_mirrors.roughness_row."""
+    N = mask.shape[0]
+    std_rows, jitter_mask = _f(mask.device, N), _f(mask.device, N)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_rough_rows(p(index), p(mask), N, rough_row[0], rough_row[1], float(scene_roughness), p(std_rows),
+                                          p(jitter_mask), p(flag), _lib.stream()), "mnrf_rough_rows")
+    return std_rows, jitter_mask
+
+
+def _perturb_normals(normal, noise, std_rows):
+    """normal + noise * std on the rows with std > 0, the others as they are (mnrf_perturb_normals): (N,3)."""
+    out = torch.empty_like(noise)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_perturb_normals(p(normal.contiguous()), p(noise), p(std_rows), noise.shape[0], p(out), _lib.stream()),
+               "mnrf_perturb_normals")
+    return out
+
+
+def _reflect_fan_rows(rays, x_surface, normal, noise, std_rows, index):
+    """_reflect_fan with the std of every ray in std_rows (N,) (mnrf_reflect_jitter_fan_rows)."""
+    n_jit, m = noise.shape[0], index.shape[0]
+    sec = _f(rays.device, n_jit * m, 8)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_reflect_jitter_fan_rows(
+        p(rays), p(x_surface.contiguous()), p(normal.contiguous()), p(noise.contiguous()), p(std_rows), p(index), m,
+        rays.shape[0], n_jit, RAY_FORWARD_OFFSET, p(sec), _lib.stream()), "mnrf_reflect_jitter_fan_rows")
     return sec
 
 
@@ -839,7 +906,26 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     it, eval.py:458-460: that is why mirrors cannot be chained).  Allowed beside placed_objects= (the objects are merged first,
     the mirrors see the resulting depth) and beside app_reflection_substitution; refused beside app_place_new_mirror /
     new_mirror=, the single-object keywords and roughness.  The result gains new_mirror_index: int32 per ray of the call's own
-    rays, the mirror the ray took at level 0, -1 for none."""
+    rays, the mirror the ray took at level 0, -1 for none.
+
+    rough_times=T (an int >= 1; None, the default: off) with scene_roughness=S (float32, >= 0, finite; default 0) and the
+    `roughness` of each PlacedMirror: a roughness PER MIRROR (include/mnrf.h "A roughness per mirror").  At a level
+    that traces, the std of ray i is the roughness of the placed mirror it took at THAT level (mnrf_place_mirrors' index) or S
+    where it took none -- the scene's own mirrors.  The first reflection is the existing one, about l2n(normal + draw_0 * std_i)
+    where std_i > 0 and about l2n(normal) with no addition where std_i == 0 (the bits of the frame without roughness); the rays
+    of J = {mask != 0 and std > 0} get T further reflections about l2n(normal + draw_j * std_i) and the mean of their T + 1
+    samples, added and finished as the roughness rule above does it; a mirror ray outside J (a polished mirror) and a ray of
+    level 0 that is no mirror ray keep their single sample.  One (N,3) draw per tracing level, then T more iff J is not empty:
+    where every std equals S > 0 the draws, the launches' inputs and the result are those of args.app_control_mirror_roughness
+    with trace_ray_times = T and normal_noise_std = S.  At most two count reads per chunk and level (the mask's at levels >= 1,
+    J's), whatever T is.  mnrf_rough_rows, mnrf_perturb_normals and mnrf_reflect_jitter_fan_rows; batch_jitter=False makes a
+    jitter mnrf_perturb_normals followed by mnrf_reflect_compact on J's mask.  Allowed alone, beside new_mirrors=, beside
+    placed_objects= (the objects are merged at every level of every render, the jittered ones included; object_used counts
+    every render) and beside both; refused beside args.app_control_mirror_roughness (one roughness rule per call),
+    app_place_new_mirror / new_mirror=, the single-object keywords and app_reflection_substitution.  normal_noise_std= and
+    args.trace_ray_times are not read; _normal_noise= and batch_jitter= work as with the flag.  Without rough_times a mirror
+    with roughness > 0, or a scene_roughness > 0, is refused.  The route takes the exclusions of the flag: no pipelined
+    stage, no blended level, no colour/depth-only last level."""
     args = kwargs.get("args")
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
@@ -889,6 +975,13 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     # the default contract
     maps_only = bool(kwargs.get("maps_only", to_cpu == "maps"))
     rough = getattr(args, "app_control_mirror_roughness", False)
+    # a roughness per mirror: its own keywords, its own branch of stage_b; it takes every exclusion `rough` takes
+    rough_times, scene_roughness = resolve_rough_rows(kwargs)
+    rough_rows = rough_times is not None
+    if rough_rows:
+        from .placed_mirrors import roughness_row
+        rough_row = roughness_row(kwargs.get("new_mirrors"))
+        jitters_possible = scene_roughness > 0 or any(v > 0 for v in rough_row[1][:rough_row[0]])   # else J is empty, known here
     batch_jitter = kwargs.get("batch_jitter", noise_iter is None)   # see the roughness branch of recurse()
     one_field = getattr(args, "only_one_field", False)
     fine_epoch = getattr(args, "only_one_field_fine_epoch", 2)
@@ -910,7 +1003,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # The last level of a recursion traces nothing: its caller (stage_b of the level above) reads rgb_* and depth_* of it
         # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
         # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
-        rgb_depth = 1 <= level == args.max_recursive_level and not rough
+        rgb_depth = 1 <= level == args.max_recursive_level and not (rough or rough_rows)
         # A level that traces has its colour replaced by m * reflected + (1 - m) * colour in stage_b, m = 1 wherever the
         # composited mirror value is not below 0.5 (the threshold, then `!= 0`): the colour of such a ray reaches nothing --
         # no other key of the result carries it -- so the final pass may leave it out and write 0 (render_rays
@@ -928,7 +1021,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # pixels never takes the slower route for more than the chunks it takes to notice a change.
         # `blended_level=True` / `False` forces the choice (tests, measurements).
         can_blend = bool(level < args.max_recursive_level and trace_flag and test_time and blend_mode is not False
-                         and not (rough or place or subst or objects or multi))
+                         and not (rough or rough_rows or place or subst or objects or multi))
         evidence = mirror_fraction.get(level)
         blended = can_blend and (blend_mode is True or (evidence is not None and evidence >= BLENDED_BREAK_EVEN))
         count_it = can_blend and blend_mode is not True
@@ -960,10 +1053,12 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         edit = None
         if place and not last:
             edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
-        if multi and level == 0:          # the mirror each of the call's own rays took; -1 where the list is not applied
+        # (with a roughness per mirror every level that places mirrors keeps its index: the std of a ray follows the mirror it
+        # took at THAT level; only level 0's is returned)
+        if multi and (level == 0 or (rough_rows and not last)):      # the mirror each ray took; -1 where the list is not applied
             r["new_mirror_index"] = torch.full((rays_chunk.shape[0],), -1, dtype=torch.int32, device=rays_chunk.device)
         if multi and not last:
-            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index") if level == 0 else None)  # noqa: E731
+            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index"))  # noqa: E731
         pending, any_mirror, counted = None, False, None
         if mask is not None:
             if host_flags is not None and not last and rays_chunk.shape[0]:
@@ -1024,8 +1119,17 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         # `mirror_mask = mirror_mask.bool()` then `.float()` (eval.py:307, 689): an exact 0.5 blends as 1
         mask = (mask != 0).float()
         normal = _pick_normal(r, sel)
-        nn0 = draw(N, dev) if rough else None                             # eval.py:506-511
-        sec, index, rdir = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, only_in, nn0, noise_std)
+        nn0 = draw(N, dev) if (rough or rough_rows) else None             # eval.py:506-511
+        first_normal, first_std = normal, noise_std
+        if rough_rows:
+            # THE RULE of include/mnrf.h "A roughness per mirror" (DESIGN 4.4c): the std of a ray follows the mirror it took at
+            # this level.  The first reflection is the existing launch on normals that carry draw_0 * std already (no addition
+            # where the std is 0: the bits of the frame without roughness); with every std 0 there is nothing to add at all.
+            if jitters_possible:
+                std_rows, jitter_mask = _rough_rows(r.get("new_mirror_index"), mask, rough_row, scene_roughness)
+                first_normal = _perturb_normals(normal, nn0, std_rows)
+            nn0, first_std = None, 0.0                                    # (the draw is made either way: the order of draws)
+        sec, index, rdir = _reflect(rays_chunk, r[f"x_surface_{sel}"], first_normal, mask, only_in, nn0, first_std)
         r["reflect_direction"] = rdir
         if sec.shape[0] > 0:
             if subst:                                                     # eval.py:550-613: no recursion below
@@ -1084,6 +1188,37 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                 else:
                     for k in keys:
                         r2[k] = r2[k] / (times + 1)
+            elif rough_rows and jitters_possible:
+                # The branch above with J = {mask != 0 and std > 0} in the mask's place: ONE compaction of J and the read of its
+                # count (the second and last of the level), the fan with the std per ray, the same groups, sums and finish.  A
+                # mirror ray outside J keeps its one sample; an empty J takes no further draw.
+                keys = [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]
+                jit_index = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, jitter_mask, True, want_dir=False)[1]
+                mj = jit_index.shape[0]
+                if mj > 0:
+                    if only_in:       # row of R: the ray's rank in the mask's compaction, from the two indices, on the device
+                        rank = torch.empty(N, dtype=torch.int32, device=dev)
+                        rank[index.long()] = torch.arange(index.shape[0], dtype=torch.int32, device=dev)
+                        acc_index = rank[jit_index.long()]
+                    else:
+                        acc_index = jit_index
+                    for k in keys:
+                        r2[k] = r2[k].contiguous()
+                    finish = float(np.float32(1) / np.float32(rough_times + 1))
+                    g = 0
+                    while g < rough_times:
+                        n_g = max(1, min(rough_times - g, JITTER_RAYS // mj)) if batch_jitter else 1
+                        if batch_jitter:
+                            noise = torch.stack([draw(N, dev) for _ in range(n_g)]) if noise_iter is not None \
+                                else torch.randn(n_g, N, 3, device=dev)
+                            s2 = _reflect_fan_rows(rays_chunk, r[f"x_surface_{sel}"], normal, noise, std_rows, jit_index)
+                        else:         # one by one: a jitter is mnrf_perturb_normals, then mnrf_reflect_compact on J's mask
+                            s2 = _reflect(rays_chunk, r[f"x_surface_{sel}"], _perturb_normals(normal, draw(N, dev), std_rows),
+                                          jitter_mask, True, want_dir=False)[0].contiguous()
+                        r3 = recurse(s2, level + 1)
+                        g += n_g
+                        for k in keys:
+                            _jitter_mean(r2[k], r3[k], acc_index, mj, n_g, finish if g >= rough_times else None)
             r[f"rgb_{sel}"], refl = _blend(r[f"rgb_{sel}"], r2[f"rgb_{sel}"], index, mask, True)
             r[f"rgb_{sel}_reflect"] = refl
             if only_in:
@@ -1105,7 +1240,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     staged, staged_rows, hold = {}, defaultdict(int), []
     copy_stream = _copy_stream(rays.device) if stage_maps else None
     starts = list(range(0, rays.shape[0], chunk))
-    pipelined = rays.is_cuda and not rough and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
+    pipelined = rays.is_cuda and not (rough or rough_rows) and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
     host_flags = torch.zeros(2, dtype=torch.int32).pin_memory() if pipelined else None
     host_counts = torch.zeros(2, dtype=torch.int64).pin_memory() if pipelined else None
     ahead = stage_a(rays[:chunk].contiguous(), 0, host_flags, 0) if (pipelined and starts) else None

@@ -61,6 +61,17 @@ of mirror rays, the count reads, and beside them the estimate t(roughness off) +
 off) / (rays the roughness-off frame renders, all levels): the per-ray cost of a render in that frame.  Nothing is asserted.
 
     python scripts/bench_apps.py --rough [--parent_root DIR] [--reps 7] > profiles/rough_bench.json
+
+--rough_mirrors runs the leg of a roughness per mirror INSTEAD (batched_inference rough_times=, scene_roughness=,
+PlacedMirror(roughness=)) on part (b)'s frame -- STRADDLE, 800x800, one bounce -- and prints one JSON line.  Per part one warm-up
+and one counting frame per route, then --reps rounds (default 7) alternating the routes frame by frame; median and spread.
+(a) rough_times=4, scene_roughness=0.01 alone beside app_control_mirror_roughness with trace_ray_times 4 and std 0.01: the same
+draws, launches and result, so the ratio is the route's overhead.  (b) one frosted placed mirror (roughness 0.03) taken by about
+5 % and about 25 % of the primary rays, the scene's own mirror polished, T = 4 and 64: ms per frame, the rays in J, the count
+reads, and the estimate t(off) + T x |J| x c with c = t(off) / (rays the roughness-off frame renders) and `off` the same frame
+with the mirror polished and no rough_times.  (c) the same with scene_roughness=0.01.  Nothing is asserted.
+
+    python scripts/bench_apps.py --rough_mirrors [--reps 7] > profiles/rough_mirrors_bench.json
 """
 import argparse
 import json
@@ -481,6 +492,108 @@ def rough_leg(a, dev):
     return res
 
 
+def _rough_mirrors_frames(models, emb, rays, args, **kw):
+    """One warm-up frame and one frame that counts, per recursion level, the compacting _reflect calls (each reads its count on
+    the host), the rays of J (the rows of every mnrf_jitter_mean) and the rows of every render_rays call -> (dict, frame); the
+    caller times `frame` (the routes of a part alternate frame by frame)."""
+    def frame():
+        out = M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=args, trace_secondary_rays=True,
+                                  to_cpu=False, maps_only=True, **kw)
+        torch.cuda.synchronize()
+        return out
+
+    out = frame()
+    reads, rows, in_j = [0], [0], [0]
+    reflect, render, mean = REC._reflect, REC.render_rays, REC._jitter_mean
+
+    def counting_reflect(rays_, x, n, mask, compact, *a, **k):
+        reads[0] += 1 if compact else 0
+        return reflect(rays_, x, n, mask, compact, *a, **k)
+
+    def counting_render(models_, embeddings, r, *a, **k):
+        rows[0] += int(r.shape[0])
+        return render(models_, embeddings, r, *a, **k)
+
+    def counting_mean(acc, pieces, index, m, n_jit, finish=None):
+        in_j[0] += m if finish is not None else 0      # (the finishing call of a chunk and level: once per J)
+        return mean(acc, pieces, index, m, n_jit, finish)
+
+    REC._reflect, REC.render_rays, REC._jitter_mean = counting_reflect, counting_render, counting_mean
+    try:
+        frame()
+    finally:
+        REC._reflect, REC.render_rays, REC._jitter_mean = reflect, render, mean
+    print(f"counted: {sorted(kw)} {args.get('trace_ray_times', '')}", file=sys.stderr, flush=True)
+    mask = out["mirror_mask_fine"] != 0
+    keys = len([k for k in ("rgb_coarse", "rgb_fine") if k in out]) or 1
+    got = {"count_reads_per_frame": reads[0], "rays_rendered_per_frame": rows[0], "rays_in_J_level0": in_j[0] // keys,
+           "mirror_share_level0": round(float(mask.float().mean()), 4)}
+    if "new_mirror_index" in out:
+        got["placed_mirror_share_level0"] = round(float((out["new_mirror_index"] >= 0).float().mean()), 4)
+    return got, frame
+
+
+def _alternate(routes, reps):
+    """routes: name -> (dict, frame).  `reps` rounds that alternate the routes frame by frame; median and spread into each dict."""
+    times = {name: [] for name in routes}
+    for _ in range(reps):
+        for name, (_, frame) in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            frame()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    for name, (got, _) in routes.items():
+        ms = statistics.median(times[name])
+        got.update(ms_per_frame=round(ms, 1), ms_reps=[round(t, 1) for t in times[name]], spread=round((max(times[name]) - min(times[name])) / ms, 4))
+    return {name: got for name, (got, _) in routes.items()}
+
+
+def rough_mirrors_leg(a, dev):
+    """The --rough_mirrors leg (module docstring) -> the result dict."""
+    import math
+    import numpy as np
+    from mirror_nerf_amd import PlacedMirror
+    reps = a.reps
+    models, _ = SY.build_models(dev, SY.STRADDLE, seed=0)
+    emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}
+    rays = SY.device_rays(H, W, dev)
+    base = dict(ARGS, max_recursive_level=1, near=1e9)
+    res = {"workload": f"STRADDLE random-init pair, {W}x{H}, {N_SAMPLES} + {N_IMPORTANCE} samples, chunk {CHUNK}, max_recursive_level 1, near 1e9 "
+                       "(nothing hides a placed mirror), maps_only; the placed mirror is a square 0.5 down the central ray, tilted by 0.2 about z",
+           "protocol": f"per part: one warm-up and one counting frame per route, then {reps} rounds alternating the routes frame by frame; host "
+                       "clock around a frame that ends in a synchronise; median, spread = (max - min) / median of a route's frames"}
+    # (a) the new route with one std everywhere beside the flag's route
+    flag = dict(base, app_control_mirror_roughness=True, trace_ray_times=4)
+    part = _alternate({"flag": _rough_mirrors_frames(models, emb, rays, flag, normal_noise_std=0.01),
+                       "rough_times": _rough_mirrors_frames(models, emb, rays, base, rough_times=4, scene_roughness=0.01)}, reps)
+    part["rough_times_over_flag"] = round(part["rough_times"]["ms_per_frame"] / part["flag"]["ms_per_frame"], 4)
+    res["a_overhead_T4_std0.01"] = part
+    # (b), (c) one frosted placed mirror taken by about 5 % and about 25 % of the primary rays
+    eye = np.array((0.0, -4.0, 1.5))                                        # synthetic.look_at_pose's defaults
+    view = -eye / np.linalg.norm(eye)
+    right = np.cross(view, (0.0, 0.0, 1.0))
+    right /= np.linalg.norm(right)
+    for share in (0.05, 0.25):
+        side = math.sqrt(share) * 2 * 0.5 * math.tan(SY.CAMERA_ANGLE_X / 2)
+        mirror = dict(center=eye + 0.5 * view, normal=-view + 0.2 * right, up=(0, 0, 1), size=(side, side))
+        polished, frosted = [PlacedMirror(**mirror)], [PlacedMirror(**mirror, roughness=0.03)]
+        routes = {"off": _rough_mirrors_frames(models, emb, rays, base, new_mirrors=polished)}
+        for times in (4, 64):
+            routes[f"b_scene_polished_T{times}"] = _rough_mirrors_frames(models, emb, rays, base, new_mirrors=frosted, rough_times=times)
+            routes[f"c_scene_frosted_T{times}"] = _rough_mirrors_frames(models, emb, rays, base, new_mirrors=frosted, rough_times=times,
+                                                                      scene_roughness=0.01)
+        part = _alternate(routes, reps)
+        per_ray = part["off"]["ms_per_frame"] / part["off"]["rays_rendered_per_frame"]
+        part["ms_per_rendered_ray_of_the_off_frame"] = per_ray
+        for name, got in part.items():
+            if name[:2] in ("b_", "c_"):
+                times = int(name.rsplit("T", 1)[1])
+                got["estimate_ms"] = round(part["off"]["ms_per_frame"] + times * got["rays_in_J_level0"] * per_ray, 1)
+                got["measured_over_estimate"] = round(got["ms_per_frame"] / got["estimate_ms"], 4)
+        res[f"placed_mirror_about_{round(share * 100)}_percent"] = part
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=None, help="timed frames per route (default 3; 7 for --objects)")
@@ -495,14 +608,18 @@ def main():
     ap.add_argument("--parent_root", type=str, default=None, help="--rough: a built checkout of the parent commit to measure beside this tree")
     ap.add_argument("--rough_child", action="store_true", help="(--rough's child process) part (a) on the package of --package_root")
     ap.add_argument("--package_root", type=str, default=None, metavar="DIR", help="(--rough's child process) the tree whose package is imported")
+    ap.add_argument("--rough_mirrors", action="store_true", help="run the leg of a roughness per mirror instead of the others")
     a = ap.parse_args()
-    a.reps = a.reps or (7 if (a.objects or a.mirrors or a.rough or a.rough_child) else 3)
+    a.reps = a.reps or (7 if (a.objects or a.mirrors or a.rough or a.rough_child or a.rough_mirrors) else 3)
     dev = "cuda:0"
     if a.rough_child:
         print(json.dumps(rough_all_mirror(dev, a.reps)))
         return
     if a.rough:
         print(json.dumps(rough_leg(a, dev)))
+        return
+    if a.rough_mirrors:
+        print(json.dumps(rough_mirrors_leg(a, dev)))
         return
     models, _ = SY.build_models(dev, SY.ALL_MIRROR, seed=0)
     emb = {"xyz": M.Embedding(10), "dir": M.Embedding(4)}

@@ -55,7 +55,8 @@ follows --root_dir).  --mirrors_json FILE, a JSON list of up to 8 entries
 
 (shape is optional) places several mirrors on any plane through batched_inference(new_mirrors=): per ray the nearest one that
 the scene does not hide wins.  It implies tracing, may be combined with --objects_json (a placed object is then seen in the
-placed mirrors) and is refused beside --app_place_new_mirror.
+placed mirrors) and is refused beside --app_place_new_mirror.  An entry of either kind may carry "roughness": s, the standard
+deviation of the normal jitter of the rays that take that mirror (read with --rough_times, below).
 
 Mirror roughness (run.sh "control_mirror_roughness"): --app_control_mirror_roughness --trace_ray_times T --normal_noise_std S
 renders every mirror pixel as the mean of T + 1 reflections about jittered normals (batched_inference's roughness rule: a
@@ -63,6 +64,13 @@ frame may hold any share of mirror pixels; a pixel that is no mirror keeps its s
 --normal_noise_std_changes lets S follow the reference's per-frame cycle (eval.py:1130-1136): frame i of n uses
 S * c with p = i / n and c = 2 p below one half, 1 - 2 (p - 0.5) from there on.  The flag is refused beside the object and
 new-mirror applications, with batched_inference's own messages.
+
+A roughness per mirror: --rough_times T [--scene_roughness S] renders the pixels of every mirror whose roughness is not 0 as the
+mean of T + 1 reflections about jittered normals (batched_inference(rough_times=, scene_roughness=)): a placed mirror has the
+"roughness" of its --mirrors_json entry, the scene's own mirrors have S (default 0: polished), and a polished mirror is traced
+once.  Allowed alone, beside --mirrors_json and beside --objects_json; refused beside --app_control_mirror_roughness (one
+roughness rule per call) and --app_place_new_mirror.  --trace_ray_times and --normal_noise_std are not read, and the per-frame
+cycle of --normal_noise_std_changes does not apply.
 
 Out of scope: the other GIFs of save_gif_and_print_mean_psnr (imageio is not a dependency of this project), the COLMAP reader,
 reflection substitution (batched_inference has it; this driver does not expose its flags) and --render_coarse_rgb (it sets
@@ -140,7 +148,26 @@ def get_opts(argv=None):
     ap.add_argument("--normal_noise_std", type=float, default=0.01, help="standard deviation of the jitter added to the normal")
     ap.add_argument("--normal_noise_std_changes", action="store_true",
                     help="scale --normal_noise_std by the frame's place in the split: 0 -> 1 -> 0 (eval.py:1130-1136)")
+    # a roughness per mirror: this project's own flags (batched_inference rough_times=, scene_roughness=)
+    ap.add_argument("--rough_times", type=int, default=None,
+                    help="jittered reflections beside the first for the rays of every mirror whose roughness is not 0")
+    ap.add_argument("--scene_roughness", type=float, default=0.0,
+                    help="with --rough_times: the jitter's standard deviation on the scene's own mirrors (placed ones: `roughness` in --mirrors_json)")
     args = ap.parse_args(argv)
+    if args.rough_times is not None:           # batched_inference's own refusals (_refuse_rough_rows), before anything is loaded
+        if args.rough_times < 1:
+            ap.error("--rough_times counts the jittered reflections beside the first: at least 1")
+        if not 0 <= args.scene_roughness < float("inf"):
+            ap.error("--scene_roughness must be finite and not negative")
+        if args.app_control_mirror_roughness:
+            ap.error("rough_times= cannot be combined with app_control_mirror_roughness: one roughness rule per call")
+        if args.app_place_new_mirror:
+            ap.error("rough_times= cannot be combined with app_place_new_mirror (the single mirror carries no roughness; an entry "
+                     "{axis, position, normal, rect, roughness} of --mirrors_json is that mirror)")
+        if args.app_reflect_newly_placed_objects and args.objects_json is None:
+            ap.error("rough_times= is combined with objects through --objects_json, not with --obj_ckpt_path")
+    elif args.scene_roughness != 0:
+        ap.error("--scene_roughness is read with --rough_times T alone")
     if args.app_control_mirror_roughness:      # batched_inference's own refusals (_refuse_apps), before anything is loaded
         if args.trace_ray_times < 0:
             ap.error("--trace_ray_times counts renders: it cannot be negative")
@@ -251,13 +278,13 @@ def read_mirrors_json(path):
         if not isinstance(e, dict):
             raise SystemExit(f"[Error] {path}: mirror {j} is not a JSON object")
         kind = "axis" if "axis" in e else "frame"
-        known = MIRROR_KEYS[kind] + ("shape",)
+        known = MIRROR_KEYS[kind] + ("shape", "roughness")
         unknown, missing = sorted(set(e) - set(known)), [k for k in MIRROR_KEYS[kind] if e.get(k) is None]
         if unknown or missing:
             raise SystemExit(f"[Error] {path}: mirror {j}: unknown keys {unknown}, missing keys {missing} (known: {sorted(known)}; "
                              f"or those of the other kind, {sorted(MIRROR_KEYS['frame' if kind == 'axis' else 'axis'])})")
         try:
-            e = dict(e, shape=e.get("shape") or "rect")
+            e = dict(e, shape=e.get("shape") or "rect", roughness=0.0 if e.get("roughness") is None else e["roughness"])
             out.append(PlacedMirror.axis_aligned(**e) if kind == "axis" else PlacedMirror(**e))
         except (TypeError, ValueError) as err:
             raise SystemExit(f"[Error] {path}: mirror {j}: {err}") from None
@@ -350,7 +377,8 @@ def frame_noise_std(args, i, n_frames):
 def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=None, normal_noise_std=0):
     """The per-ray maps of one frame, on the device.  obj: load_object's dict; frame_time: the time of a D-NeRF object;
     placed: the frame's list of PlacedObject (--objects_json), in place of obj; mirrors: the list of PlacedMirror
-    (--mirrors_json); normal_noise_std: the frame's jitter (--app_control_mirror_roughness)."""
+    (--mirrors_json); normal_noise_std: the frame's jitter (--app_control_mirror_roughness).  --rough_times and --scene_roughness
+    travel as batched_inference's keywords of the same names."""
     import torch
     import mirror_nerf_amd as M
     extra = dict(obj or {})
@@ -358,6 +386,8 @@ def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=N
         extra = {"placed_objects": placed}
     if mirrors is not None:
         extra["new_mirrors"] = mirrors
+    if getattr(args, "rough_times", None) is not None:
+        extra.update(rough_times=args.rough_times, scene_roughness=args.scene_roughness)
     if "render_kwargs_test_d_nerf" in extra:
         extra["frame_time"] = frame_time
     bounds = object_bounds(args, obj, frame_time)
