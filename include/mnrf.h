@@ -464,11 +464,12 @@ int64_t mnrf_train_mask_words(int64_t B);
 int64_t mnrf_train_workspace_floats(int64_t B);
 
 /* mnrf_field_forward for training: all four heads (+ `normal` when non-null), and keeps in
- * save_x / save_mask / save_inv what mnrf_field_backward needs (no recomputation). */
+ * save_x / save_mask / save_inv what mnrf_field_backward needs (no recomputation).  save_x is a workspace without an element
+ * type of its own: mnrf_train_save_floats(B) fp32 rows, or with MNRF_TRAIN_PLANES mnrf_train_planes_bytes(B) bytes of f16 tiles. */
 int mnrf_field_forward_train(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                              const float* rays, const float* z_vals, int spr, const float* dir_emb,
                              int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
-                             float* is_mirror, float* normal, float* save_x, uint64_t* save_mask,
+                             float* is_mirror, float* normal, void* save_x, uint64_t* save_mask,
                              float* save_inv, float* save_invj, unsigned flags /* 0 or MNRF_SPLIT_F16 [| MNRF_TRAIN_PLANES] */, void* stream);
 
 /* Backward of the field MLP: given dL/d{sigma (B), rgb (B,3), pred_normal (B,3), is_mirror (B)},
@@ -732,7 +733,7 @@ int mnrf_ray_grads_n(const float* d_xyz, const float* z_vals, const float* d_dir
 int mnrf_field_forward_train_n(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                const float* rays, const float* z_vals, int spr, const float* dir_emb,
                                int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
-                               float* is_mirror, float* normal, float* save_x, uint64_t* save_mask,
+                               float* is_mirror, float* normal, void* save_x, uint64_t* save_mask,
                                float* save_inv, float* save_invj, unsigned flags, const int32_t* n_live, void* stream);
 int mnrf_field_backward_planes_n(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                  const float* rays, const float* z_vals, int spr,

@@ -5,6 +5,7 @@ a RuntimeError is raised.  torch is imported first so that the HIP runtime
 already loaded by torch (same SONAME libamdhip64.so.7) is the one the library
 binds to -- device pointers and streams then belong to one runtime.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -24,11 +25,14 @@ def _read_header():
     if not os.path.exists(HEADER):
         raise RuntimeError(f"{HEADER} not found: the binding of libmnrf_hip.so is read from the header, there is no other copy")
     with open(HEADER) as f:
-        return _abi.parse_header(f.read())
+        return _abi.parse_header(f.read(), pointees=POINTEES)
 
 
 # Once per process: every `#define MNRF_*` integer, the argument structs as ctypes.Structure classes, and
-# name -> (restype, argtypes) of every prototype (see _abi.py for the typing rule).
+# name -> (restype, argtypes) of every prototype (see _abi.py for the typing rule), and, filled in the same pass, POINTEES: name ->
+# (element class, declared base type) of each single-level device pointer by argument position (None elsewhere), which only
+# the checked mode below looks at.
+POINTEES = {}
 CONSTANTS, STRUCTS, SIGNATURES = _read_header()
 globals().update(CONSTANTS)          # _lib.MNRF_SPLIT_F16, ...
 N_PARAMS = CONSTANTS["MNRF_N_PARAMS"]
@@ -61,6 +65,8 @@ def lib():
             fn.restype = res
             fn.argtypes = args
         _lib = L
+        if _checked:
+            _set_argtypes(True)
     return _lib
 
 
@@ -71,7 +77,10 @@ def check(code, what):
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL).  Tensors must be fp32/int32, contiguous, on the GPU."""
+    """Device pointer of a tensor (None -> NULL) as a plain c_void_p.  Checked here: the tensor is on the GPU, on the current
+    device, and contiguous.  NOT checked: its dtype and its extent -- the element type the kernel reads is the one mnrf.h
+    declares for that argument, and holding a tensor to it is the caller's business (the public entry points convert or refuse
+    a tensor of another precision where it enters).  `with checked():` makes a mismatch of the element type an ArgumentError."""
     if t is None:
         return None
     if not t.is_cuda:
@@ -85,6 +94,124 @@ def ptr(t):
                            "call torch.cuda.set_device / use `with torch.cuda.device(t.device)`")
     return ctypes.c_void_p(t.data_ptr())
 
+
+# ---- the checked mode: the element types of mnrf.h held against the dtypes of the tensors behind the pointers.  Off by default:
+# a from_param written in Python costs ~0.2 us per pointer argument, and a step makes some hundred launches of 10-20 pointers each.
+
+CLASS_DTYPES = {"float": (torch.float32,), "double": (torch.float64,), "int32": (torch.int32,), "int64": (torch.int64,),
+                "byte": (torch.uint8, torch.int8, torch.bool), "void": None, "struct": None}      # None: anything
+
+
+class DevicePtr(ctypes.c_void_p):
+    """What ptr() returns in the checked mode: the address, and the dtype of the tensor it came from."""
+    dtype = None
+
+
+class _TypedPtr(ctypes.c_void_p):
+    """argtypes entry of one device pointer in the checked mode (one subclass per function and position).  ctypes calls
+    from_param for every argument before it enters the C function; what it raises surfaces as ctypes.ArgumentError."""
+    _where, _declared, _accepts = "", "void", None
+
+    @classmethod
+    def from_param(cls, value):
+        dtype = getattr(value, "dtype", None)          # None, ints and a plain c_void_p carry none: passed on unchecked
+        if dtype is not None and cls._accepts is not None and dtype not in cls._accepts:
+            raise TypeError(f"{cls._where}: mnrf.h declares {cls._declared}*, the tensor is {dtype}")
+        return ctypes.c_void_p.from_param(value)
+
+
+_checked = 0
+_typed = {}          # name -> argtypes with a _TypedPtr subclass at every classified pointer, made on first use
+
+
+def _typed_argtypes(name):
+    if name not in _typed:
+        args = list(SIGNATURES[name][1])
+        for i, c in enumerate(POINTEES[name]):
+            if c is not None:
+                args[i] = type(f"{name}_arg{i}", (_TypedPtr,), {
+                    "_where": f"{name}, argument {i + 1}", "_declared": c[1], "_accepts": CLASS_DTYPES[c[0]]})
+        _typed[name] = args
+    return _typed[name]
+
+
+def _set_argtypes(typed):
+    if _lib is not None:
+        for name, (_, args) in SIGNATURES.items():
+            getattr(_lib, name).argtypes = _typed_argtypes(name) if typed else args
+
+
+def _ptr_checked(t):
+    """ptr() of the checked mode: the same checks, and the pointer remembers the tensor's dtype."""
+    p = _ptr_plain(t)
+    if p is None:
+        return None
+    q = DevicePtr(p.value)
+    q.dtype = t.dtype
+    return q
+
+
+_ptr_plain = ptr
+
+
+def _enter_checked():
+    global _checked, ptr
+    _checked += 1
+    if _checked == 1:
+        ptr = _ptr_checked
+        _set_argtypes(True)
+
+
+def _leave_checked():
+    global _checked, ptr
+    _checked -= 1
+    if _checked == 0:
+        ptr = _ptr_plain
+        _set_argtypes(False)
+
+
+@contextlib.contextmanager
+def checked():
+    """Inside, every entry point of lib() refuses a ptr(t) whose dtype is not in the class mnrf.h declares for that argument:
+    ctypes.ArgumentError naming function, position, declared type and dtype, raised before the C function is entered.  Leaving
+    restores ptr and the argtypes objects of the default path.  MNRF_CHECK_ABI=1 at import turns it on for the whole process."""
+    _enter_checked()
+    try:
+        yield
+    finally:
+        _leave_checked()
+
+
+if os.environ.get("MNRF_CHECK_ABI", "") == "1":
+    _enter_checked()
+
+
+# ---- the rule of the public entry points for a caller's tensor of another precision or layout: an input is converted, a tensor
+# the call writes into is refused (DESIGN "The Python-to-kernel boundary").  Applied where a tensor enters, never per launch.
+
+def f32_in(t):
+    """An input the kernels read as float32 rows: the tensor itself, or its float32 contiguous copy (None stays None)."""
+    if t is None or (t.dtype == torch.float32 and t.is_contiguous()):
+        return t
+    return t.float().contiguous()
+
+
+def i32_in(t):
+    """An input the kernels read as int32: the tensor itself, or its int32 contiguous copy (None stays None)."""
+    if t is None or (t.dtype == torch.int32 and t.is_contiguous()):
+        return t
+    return t.int().contiguous()
+
+
+def written(t, dtypes, name):
+    """A tensor the call writes into: refused unless it is contiguous and of one of `dtypes` (None passes)."""
+    if t is not None and (t.dtype not in dtypes or not t.is_contiguous()):
+        raise ValueError(f"{name} is written in place: it must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor, "
+                         f"not {t.dtype}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return t
+
+
+F32, I32, BYTE = (torch.float32,), (torch.int32,), (torch.bool, torch.uint8, torch.int8)
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _cur_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device

@@ -280,7 +280,7 @@ extern "C" int64_t mnrf_train_workspace_floats(int64_t B) { return (int64_t)DY_F
 static int field_forward_train_impl(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                     const float* rays, const float* z_vals, int spr, const float* dir_emb,
                                     int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
-                                    float* is_mirror, float* normal, float* save_x, uint64_t* save_mask,
+                                    float* is_mirror, float* normal, void* save_x, uint64_t* save_mask,
                                     float* save_inv, float* save_invj, unsigned flags, const int32_t* n_live, void* stream) {
     if (n_live && !(flags & MNRF_TRAIN_PLANES))
         return mnrf_fail(MNRF_ERR_UNSUPPORTED, "mnrf_field_forward_train_n: a live row count needs MNRF_TRAIN_PLANES (the fp32-row layout depends on B)");
@@ -295,7 +295,7 @@ static int field_forward_train_impl(float* packed, int64_t B, const float* xyz, 
         return mnrf_fail(MNRF_ERR_ARG, "mnrf_field_forward_train: the four head outputs are required (the backward reads them)");
     FieldArgs A{packed, MNRF_GRAD_NORMAL, (long long)B, xyz, (long long)xyz_stride, rays, z_vals, spr, dir_emb,
                 (long long)dir_stride, sigma, rgb, pred_normal, is_mirror, normal, nullptr,
-                planes ? nullptr : save_x, (unsigned long long*)save_mask, save_inv, save_invj, planes ? (char*)save_x : nullptr};
+                planes ? nullptr : (float*)save_x, (unsigned long long*)save_mask, save_inv, save_invj, planes ? (char*)save_x : nullptr};
     A.n_live = n_live;
     // always a 128-sample tiling with the mask-producing (GRAD) body: the backward kernel shares its tile map.
     // MNRF_SPLIT_F16: the split-f16 tuning (same saved quantities, fp32 activations from its fp32 accumulators)
@@ -308,7 +308,7 @@ static int field_forward_train_impl(float* packed, int64_t B, const float* xyz, 
 extern "C" int mnrf_field_forward_train(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                         const float* rays, const float* z_vals, int spr, const float* dir_emb,
                                         int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
-                                        float* is_mirror, float* normal, float* save_x, uint64_t* save_mask,
+                                        float* is_mirror, float* normal, void* save_x, uint64_t* save_mask,
                                         float* save_inv, float* save_invj, unsigned flags, void* stream) {
     return field_forward_train_impl(packed, B, xyz, xyz_stride, rays, z_vals, spr, dir_emb, dir_stride, sigma, rgb, pred_normal, is_mirror,
                                     normal, save_x, save_mask, save_inv, save_invj, flags, nullptr, stream);
@@ -316,7 +316,7 @@ extern "C" int mnrf_field_forward_train(float* packed, int64_t B, const float* x
 extern "C" int mnrf_field_forward_train_n(float* packed, int64_t B, const float* xyz, int64_t xyz_stride,
                                           const float* rays, const float* z_vals, int spr, const float* dir_emb,
                                           int64_t dir_stride, float* sigma, float* rgb, float* pred_normal,
-                                          float* is_mirror, float* normal, float* save_x, uint64_t* save_mask,
+                                          float* is_mirror, float* normal, void* save_x, uint64_t* save_mask,
                                           float* save_inv, float* save_invj, unsigned flags, const int32_t* n_live, void* stream) {
     return field_forward_train_impl(packed, B, xyz, xyz_stride, rays, z_vals, spr, dir_emb, dir_stride, sigma, rgb, pred_normal, is_mirror,
                                     normal, save_x, save_mask, save_inv, save_invj, flags, n_live, stream);

@@ -135,7 +135,11 @@ class ObjectBounds:
     def cull(self, rays, xform):
         """mnrf_object_cull on one level's rays (N, 8) with the ray move `xform` (recursion.resolve_new_object) ->
         (object-frame rays of the kept rays (N, 8), their rows (N,) int32, count (1,) int32 on the device): rows from count on
-        are undefined."""
+        are undefined.  rays of another precision or layout are converted."""
+        return self._cull(_lib.f32_in(rays), xform)
+
+    def _cull(self, rays, xform):
+        """cull for the driver, whose rays are float32 rows already."""
         N = rays.shape[0]
         if self.bits is not None and self.bits.device != rays.device:
             raise ValueError(f"ObjectBounds: the bits live on {self.bits.device}, the rays on {rays.device} (use .to(device))")

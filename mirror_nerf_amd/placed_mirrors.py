@@ -197,7 +197,19 @@ def pack(mirrors):
 
 def place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool=None, flag=None, index=None):
     """mnrf_place_mirrors on one level's rays (N, 8) and maps, in place.  packed: pack(mirrors); mask_bool: (N,) torch.bool or
-    None; flag: device int32 of one element, OR-ed with "any merged ray", or None; index: (N,) int32 or None."""
+    None; flag: device int32 of one element, OR-ed with "any merged ray", or None; index: (N,) int32 or None.
+    rays of another precision or layout are converted; the maps, mask_bool, flag and index are written: float32 (mask_bool an
+    8-bit type, flag and index int32) and contiguous, or refused."""
+    for name, t in (("depth", depth), ("mask", mask), ("normal", normal), ("x_surface", x_surface)):
+        _lib.written(t, _lib.F32, name)
+    _lib.written(mask_bool, _lib.BYTE, "mask_bool")
+    _lib.written(flag, _lib.I32, "flag")
+    _lib.written(index, _lib.I32, "index")
+    _place_mirrors(_lib.f32_in(rays), packed, near, depth, mask, normal, x_surface, mask_bool, flag, index)
+
+
+def _place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool, flag, index):
+    """place_mirrors for the driver, whose tensors are float32 / int32 rows already."""
     p = _lib.ptr
     K, kinds, shapes, axes, positions, frames, normals, rects = packed
     _lib.check(_lib.lib().mnrf_place_mirrors(

@@ -124,7 +124,12 @@ def cull_objects(rays, placed):
     """mnrf_objects_cull on one level's rays (N, 8) for the resolved objects `placed` (PlacedObject.resolve) ->
     (out_rays (K, N, 8), index (K, N) int32, slot (K, N) int32, counts (K,) int32 on the device): per object what
     ObjectBounds.cull returns -- for an object without bounds every ray, in order -- and slot, the inverse of index (-1: the
-    ray is not in the object's list)."""
+    ray is not in the object's list).  rays of another precision or layout are converted."""
+    return _cull_objects(_lib.f32_in(rays), placed)
+
+
+def _cull_objects(rays, placed):
+    """cull_objects for the driver, whose rays are float32 rows already."""
     K, N, dev = len(placed), rays.shape[0], rays.device
     posed, poses, scales, trans = (ctypes.c_int * K)(), (ctypes.c_float * (12 * K))(), (ctypes.c_float * K)(), (ctypes.c_float * (3 * K))()
     unbounded, lo, hi, res = (ctypes.c_int * K)(), (ctypes.c_float * (3 * K))(), (ctypes.c_float * (3 * K))(), (ctypes.c_int * (3 * K))()
@@ -155,7 +160,18 @@ def cull_objects(rays, placed):
 
 def merge_objects(maps, placed, slot, counts, capacity, near, rgb, depth, mask, n_used):
     """mnrf_objects_merge: maps[k] = (rgb, depth, opacity) of object k rendered on its kept rows, or None (not rendered), into
-    the level's rgb, depth, mask (None: no mirror head) in place; n_used: (K,) int32 on the device or None."""
+    the level's rgb, depth, mask (None: no mirror head) in place; n_used: (K,) int32 on the device or None.
+    The objects' maps, slot and counts are converted where they are of another precision; rgb, depth, mask and n_used are
+    written: float32 (n_used int32) and contiguous, or refused."""
+    for name, t in (("rgb", rgb), ("depth", depth), ("mask", mask)):
+        _lib.written(t, _lib.F32, name)
+    _lib.written(n_used, _lib.I32, "n_used")
+    maps = [None if m is None else tuple(_lib.f32_in(t) for t in m) for m in maps]
+    _merge_objects(maps, placed, _lib.i32_in(slot), _lib.i32_in(counts), capacity, near, rgb, depth, mask, n_used)
+
+
+def _merge_objects(maps, placed, slot, counts, capacity, near, rgb, depth, mask, n_used):
+    """merge_objects for the driver, whose tensors are float32 / int32 rows already."""
     K, N = len(placed), rgb.shape[0]
     tables = [(ctypes.c_void_p * K)() for _ in range(3)]
     hold = []

@@ -292,7 +292,7 @@ def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index):
     """The K-mirror rule on one level's maps, in place (placed_mirrors.py, mnrf_place_mirrors): _place_mirror's edits of the
     result dict for the mirrors `packed` (placed_mirrors.pack); index: (N,) int32 that receives the mirror each ray took, or
     None."""
-    from .placed_mirrors import place_mirrors
+    from .placed_mirrors import _place_mirrors as place_mirrors
     N = rays_chunk.shape[0]
     for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
         if k in r and not r[k].is_contiguous():
@@ -333,7 +333,7 @@ def _merge_object(r, rays_chunk, xform, near, n_used, render, bounds=None):
         return
     p = _lib.ptr
     if bounds is not None:
-        obj_rays, index, count = bounds.cull(rays_chunk, xform)
+        obj_rays, index, count = bounds._cull(rays_chunk, xform)
         M = int(count.item())
         if M == 0:
             return
@@ -403,7 +403,7 @@ def _merge_objects(r, rays_chunk, placed, near, n_used, renderers):
     object, ONE device->host read brings the K counts, every object with a non-zero count is rendered on its kept rows
     (renderers[k]: rays -> dict; queued back to back, no read in between), ONE mnrf_objects_merge applies the chain.  placed:
     the resolved objects (PlacedObject.resolve); n_used: (K,) int32 on the device or None."""
-    from .placed_objects import cull_objects, merge_objects
+    from .placed_objects import _cull_objects as cull_objects, _merge_objects as merge_objects
     N = rays_chunk.shape[0]
     if N == 0:
         return
@@ -591,6 +591,8 @@ def render_rays_chunk_recursively(models, embeddings, hp, rays_chunk, mirror_mas
     the ground-truth mask is valid (train.py:153 `(mask >= 0).all()`) is the caller's statement extra_chunk["_gt_valid"]."""
     static = bool(extra_chunk.get("_static")) and not extra_chunk.get("is_eval", False) and torch.is_grad_enabled()
     n_live = extra_chunk.get("_n_live")
+    if recur_level == 0:
+        rays_chunk = _lib.f32_in(rays_chunk)              # (a direct caller's chunk; NeRFSystem hands on float32 rows)
     if static and recur_level == 0 and "_rng_share" not in extra_chunk and hp.trace_secondary_rays and not train_geometry_stage:
         # every level of a static step renders the same capacity of rays: the first one draws the random numbers of all of them
         # (two generator launches per step instead of two per level)
@@ -795,6 +797,7 @@ class NeRFSystem(nn.Module):
     def _forward_chunks(self, rays, extra):
         hp = self.hparams
         results = defaultdict(list)
+        rays = _lib.f32_in(rays)             # once per call: the reflect launches of the no-grad route read (N,8) float32 rows
         for i in range(0, rays.shape[0], hp.chunk):
             ex = {k: (v[i:i + hp.chunk] if isinstance(v, torch.Tensor) else v) for k, v in extra.items() if k != "_guard"}
             rc = rays[i:i + hp.chunk].contiguous()
@@ -930,6 +933,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     if isinstance(args, dict):
         args = SimpleNamespace(**args)
     _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
+    rays = _lib.f32_in(rays)             # once per call: every launch of every level reads the chunk as (N,8) float32 rows
     objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
     placed = kwargs.get("placed_objects")
     single = objects and placed is None                                    # the single-object keywords
@@ -948,6 +952,8 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                 raise ValueError(f"object_used holds {len(placed)} elements (one per placed object) or 1 (their total), not {obj_used.numel()}")
             used_k = torch.zeros(len(placed), dtype=torch.int32, device=rays.device)
     if obj_used is not None:
+        if obj_used.dtype != torch.int32:      # the merge kernels add into it: a tensor the call writes is never converted
+            raise ValueError(f"object_used must be an int32 tensor, not {obj_used.dtype}")
         obj_used.zero_()
     place = bool(getattr(args, "app_place_new_mirror", False))
     subst = bool(getattr(args, "app_reflection_substitution", False))

@@ -76,6 +76,7 @@ def sample_pdf(bins_z, weights, N_importance, det=False, u=None, n_live=None):
     (models/rendering.py:7-51 and 312-326 in one kernel)."""
     N, S = bins_z.shape
     dev = bins_z.device
+    bins_z, weights = _lib.f32_in(bins_z), _lib.f32_in(weights)
     if u is None:
         u = _linspace01(N_importance, dev) if det else torch.rand(N, N_importance, device=dev)
     u = u.float().contiguous()
