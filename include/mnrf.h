@@ -339,6 +339,32 @@ int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirrors, MNRF_HO
                        MNRF_HOST const float* normals, MNRF_HOST const float* rects, float near, float* depth, float* mask,
                        float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any, int32_t* index, void* stream);
 
+/* THE RULE with the mirror a ray has just left excluded: batched_inference(new_mirrors=, exclude_source_mirror=True).  Every ray
+ * of a level carries source (int32): the index in the list of the placed mirror the ray was reflected off at the level DIRECTLY
+ * above; -1 for a ray that left the scene's own mirror, for a ray that took no mirror and for a ray of the call itself.  THE
+ * RULE changes in one place,
+ *     hit_k = inside && s > 0 && !blocked && k != source,
+ * and in nothing else: the winner, the ties, the writes, the merged mask, the flag and index are as above.  A source outside
+ * 0 .. n_mirrors-1 excludes nothing; the device makes no range check.  Only the mirror left at the level directly above is
+ * excluded: a ray may return to it after another bounce.  Why: a ray reflected off a tilted frame mirror starts within an ulp
+ * of that mirror's plane, on either side; from behind it, the rule above finds the same mirror again at a distance of 1e-9 to
+ * 1e-7, nearer than everything else.
+ * source: n_rays int32 on the device, one dword read per ray; null = no ray has one, and the result is mnrf_place_mirrors' bit
+ * for bit.  Everything else as mnrf_place_mirrors.  One launch. */
+int mnrf_place_mirrors_from(const float* rays, int64_t n_rays, int n_mirrors, MNRF_HOST const int* kinds, MNRF_HOST const int* shapes,
+                            MNRF_HOST const int* axes, MNRF_HOST const float* positions, MNRF_HOST const float* frames,
+                            MNRF_HOST const float* normals, MNRF_HOST const float* rects, float near, const int32_t* source,
+                            float* depth, float* mask, float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any,
+                            int32_t* index, void* stream);
+
+/* The source row of the next level: out[j * m + p] = level_index[compaction_index[p]] for j < n_rep, p < m.  level_index: the index
+ * mnrf_place_mirrors(_from) wrote at this level, null = this level placed none: -1 everywhere; compaction_index (m) int32: the
+ * rays that are reflected, as mnrf_reflect_compact numbers them, null = p itself (level 0 reflects every ray); n_rep >= 1: the
+ * jitter blocks of a fan (mnrf_reflect_jitter_fan_rows), each a copy of the first.  Precondition: every compaction_index[p] is a
+ * row of level_index (it is a compaction of that level's rays).  out (n_rep * m) int32, distinct from the inputs.  m == 0
+ * returns 0 without a launch; a negative m, n_rep < 1 or a null out returns MNRF_ERR_ARG.  One launch. */
+int mnrf_mirror_sources(const int32_t* level_index, const int32_t* compaction_index, int64_t m, int n_rep, int32_t* out, void* stream);
+
 /* ---- Mirror roughness on partly mirrored chunks: batched_inference with app_control_mirror_roughness (eval.py:506-511,
  * 622-674).  csrc/mnrf_rough.hip.
  *

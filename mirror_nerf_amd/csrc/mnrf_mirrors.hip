@@ -10,9 +10,16 @@
 // per lane; the K intersections live in registers; depth, the 12-byte rows of normal and x_surface are written only where
 // a mirror is taken (neither is read), the two masks and the index for every ray.  About 45 B read and up to 41 B written
 // per ray: a memory-bound stream, 256 threads per workgroup as the other per-ray kernels.
+//
+// mnrf_place_mirrors_from is the same kernel body with one more input, `source` (one coalesced dword per lane): the placed mirror
+// the ray was reflected off at the level directly above, which cannot be hit (`k != source`, a compare against the uniform k: no
+// branch is added to the loop).  The body is a template on "a source row is given", so mnrf_place_mirrors' instantiation is the
+// code it was.  mnrf_mirror_sources builds that row for the next level: a gather of this level's index through the
+// compaction's index, repeated per jitter block -- one thread per written element, 4 B read through each index and 4 B written.
 // Compiled with -ffp-contract=off and IEEE division, as the rest of the library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/mnrf.h"
 #include "mnrf_error.h"
@@ -30,8 +37,10 @@ struct Mirror {
 struct MirrorsArgs {
     const float* rays; long long n; int K; int wide; Mirror m[MNRF_MIRRORS_MAX]; float near;
     float* depth; float* mask; float* normal; float* x_surface; uint8_t* mask_bool; int* any; int* index;
+    const int* source;                                 // FROM: the mirror ray i left at the level above, never hit; else not read
 };
 
+template <bool FROM>
 __global__ __launch_bounds__(256) void place_mirrors_kernel(MirrorsArgs A) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     bool merged = false;
@@ -48,6 +57,7 @@ __global__ __launch_bounds__(256) void place_mirrors_kernel(MirrorsArgs A) {
             d[0] = r[3]; d[1] = r[4]; d[2] = r[5];
         }
         const float depth0 = A.depth[i];               // the depth every mirror is tested against
+        const int src = FROM ? A.source[i] : -1;       // no range check: a value outside 0 .. K-1 equals no k
         int best = -1;
         float best_dist = 0.f, bx[3] = {0.f, 0.f, 0.f}, bn[3] = {0.f, 0.f, 0.f};
         for (int k = 0; k < A.K; ++k) {
@@ -58,7 +68,7 @@ __global__ __launch_bounds__(256) void place_mirrors_kernel(MirrorsArgs A) {
             const bool inside = M.shape == MNRF_MIRROR_ELLIPSE ? mnrf_mirror::in_ellipse(u, w, M.rect) : mnrf_mirror::in_rect(u, w, M.rect);
             const float dist = mnrf_mirror::distance(o, x);
             const float s = mnrf_mirror::side(o, d, x);
-            const bool hit = inside && s > 0.f && !mnrf_mirror::blocked(dist, depth0, A.near);
+            const bool hit = inside && s > 0.f && !mnrf_mirror::blocked(dist, depth0, A.near) && !(FROM && k == src);
             if (hit && (best < 0 || dist <= best_dist)) {      // the nearest hit; a tie goes to the later mirror; a NaN never replaces
                 best = k;
                 best_dist = dist;
@@ -83,25 +93,36 @@ __global__ __launch_bounds__(256) void place_mirrors_kernel(MirrorsArgs A) {
     if (A.any && __ballot(merged) != 0ull && (threadIdx.x & 63) == 0) atomicOr(A.any, 1);
 }
 
-}  // namespace
+__global__ __launch_bounds__(256) void mirror_sources_kernel(const int* __restrict__ level_index, const int* __restrict__ compaction_index,
+                                                            long long m, long long total, int* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // element j * m + p of out
+    if (t >= total) return;
+    const long long p = t % m;
+    out[t] = level_index ? level_index[compaction_index ? (long long)compaction_index[p] : p] : -1;
+}
 
-extern "C" int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirrors, const int* kinds, const int* shapes, const int* axes,
-                                  const float* positions, const float* frames, const float* normals, const float* rects, float near,
-                                  float* depth, float* mask, float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any,
-                                  int32_t* index, void* stream) {
-    if (n_rays < 0 || n_rays > 0x7fffffffLL) return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: bad size");
-    if (n_mirrors < 1 || n_mirrors > MNRF_MIRRORS_MAX) return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: n_mirrors must be in 1..8");
-    if (!kinds || !shapes || !axes || !positions || !frames || !normals || !rects)
-        return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: a per-mirror host array is null");
+int fail(const char* who, const char* what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return mnrf_fail(MNRF_ERR_ARG, msg);
+}
+
+// both entry points: `source` null launches the instantiation without it
+int place_mirrors(const char* who, const float* rays, int64_t n_rays, int n_mirrors, const int* kinds, const int* shapes, const int* axes,
+                  const float* positions, const float* frames, const float* normals, const float* rects, float near, const int32_t* source,
+                  float* depth, float* mask, float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any, int32_t* index,
+                  void* stream) {
+    if (n_rays < 0 || n_rays > 0x7fffffffLL) return fail(who, "bad size");
+    if (n_mirrors < 1 || n_mirrors > MNRF_MIRRORS_MAX) return fail(who, "n_mirrors must be in 1..8");
+    if (!kinds || !shapes || !axes || !positions || !frames || !normals || !rects) return fail(who, "a per-mirror host array is null");
     MirrorsArgs A{};
     for (int k = 0; k < n_mirrors; ++k) {
         Mirror& M = A.m[k];
-        if (kinds[k] != MNRF_MIRROR_AXIS && kinds[k] != MNRF_MIRROR_FRAME)
-            return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: kind must be MNRF_MIRROR_AXIS or MNRF_MIRROR_FRAME");
+        if (kinds[k] != MNRF_MIRROR_AXIS && kinds[k] != MNRF_MIRROR_FRAME) return fail(who, "kind must be MNRF_MIRROR_AXIS or MNRF_MIRROR_FRAME");
         if (shapes[k] != MNRF_MIRROR_RECT && shapes[k] != MNRF_MIRROR_ELLIPSE)
-            return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: shape must be MNRF_MIRROR_RECT or MNRF_MIRROR_ELLIPSE");
+            return fail(who, "shape must be MNRF_MIRROR_RECT or MNRF_MIRROR_ELLIPSE");
         if (kinds[k] == MNRF_MIRROR_AXIS && axes[k] != MNRF_PLANE_X && axes[k] != MNRF_PLANE_Y)
-            return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: axis must be MNRF_PLANE_X or MNRF_PLANE_Y");
+            return fail(who, "axis must be MNRF_PLANE_X or MNRF_PLANE_Y");
         M.kind = kinds[k];
         M.shape = shapes[k];
         M.axis = axes[k];
@@ -115,7 +136,7 @@ extern "C" int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirro
         for (int j = 0; j < 4; ++j) M.rect[j] = rects[4 * k + j];
     }
     if (n_rays == 0) return MNRF_OK;
-    if (!rays || !depth || !mask || !normal || !x_surface) return mnrf_fail(MNRF_ERR_ARG, "mnrf_place_mirrors: null pointer");
+    if (!rays || !depth || !mask || !normal || !x_surface) return fail(who, "null pointer");
     A.rays = rays;
     A.n = (long long)n_rays;
     A.K = n_mirrors;
@@ -128,6 +149,41 @@ extern "C" int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirro
     A.mask_bool = mask_bool;
     A.any = any;
     A.index = index;
-    hipLaunchKernelGGL(place_mirrors_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
-    return mnrf_check_launch("mnrf_place_mirrors");
+    A.source = source;
+    const dim3 grid((unsigned)((n_rays + 255) / 256));
+    if (source) hipLaunchKernelGGL(place_mirrors_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(place_mirrors_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    return mnrf_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int mnrf_place_mirrors(const float* rays, int64_t n_rays, int n_mirrors, const int* kinds, const int* shapes, const int* axes,
+                                  const float* positions, const float* frames, const float* normals, const float* rects, float near,
+                                  float* depth, float* mask, float* normal, float* x_surface, uint8_t* mask_bool, int32_t* any,
+                                  int32_t* index, void* stream) {
+    return place_mirrors("mnrf_place_mirrors", rays, n_rays, n_mirrors, kinds, shapes, axes, positions, frames, normals, rects, near, nullptr,
+                         depth, mask, normal, x_surface, mask_bool, any, index, stream);
+}
+
+extern "C" int mnrf_place_mirrors_from(const float* rays, int64_t n_rays, int n_mirrors, const int* kinds, const int* shapes, const int* axes,
+                                       const float* positions, const float* frames, const float* normals, const float* rects, float near,
+                                       const int32_t* source, float* depth, float* mask, float* normal, float* x_surface,
+                                       uint8_t* mask_bool, int32_t* any, int32_t* index, void* stream) {
+    return place_mirrors("mnrf_place_mirrors_from", rays, n_rays, n_mirrors, kinds, shapes, axes, positions, frames, normals, rects, near,
+                         source, depth, mask, normal, x_surface, mask_bool, any, index, stream);
+}
+
+extern "C" int mnrf_mirror_sources(const int32_t* level_index, const int32_t* compaction_index, int64_t m, int n_rep, int32_t* out,
+                                   void* stream) {
+    if (m < 0 || m > 0x7fffffffLL) return fail("mnrf_mirror_sources", "bad size");
+    if (n_rep < 1) return fail("mnrf_mirror_sources", "n_rep must be at least 1");
+    if (m == 0) return MNRF_OK;
+    if (!out) return fail("mnrf_mirror_sources", "null pointer");
+    const long long total = (long long)m * n_rep;
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail("mnrf_mirror_sources", "n_rep * m is too large for one launch");
+    hipLaunchKernelGGL(mirror_sources_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, level_index, compaction_index,
+                       (long long)m, total, out);
+    return mnrf_check_launch("mnrf_mirror_sources");
 }

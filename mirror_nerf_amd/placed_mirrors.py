@@ -22,10 +22,11 @@ list's values for mnrf_rough_rows; without rough_times a list that holds a frost
 import ctypes
 
 import numpy as np
+import torch
 
 from . import _lib
 
-__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors", "roughness_row"]
+__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors", "mirror_sources", "roughness_row"]
 
 MAX_MIRRORS = 8      # MNRF_MIRRORS_MAX
 SHAPES = ("rect", "ellipse")
@@ -195,25 +196,71 @@ def pack(mirrors):
     return K, kinds, shapes, axes, positions, frames, normals, rects
 
 
-def place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool=None, flag=None, index=None):
+def place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool=None, flag=None, index=None, source=None):
     """mnrf_place_mirrors on one level's rays (N, 8) and maps, in place.  packed: pack(mirrors); mask_bool: (N,) torch.bool or
     None; flag: device int32 of one element, OR-ed with "any merged ray", or None; index: (N,) int32 or None.
     rays of another precision or layout are converted; the maps, mask_bool, flag and index are written: float32 (mask_bool an
-    8-bit type, flag and index int32) and contiguous, or refused."""
+    8-bit type, flag and index int32) and contiguous, or refused.
+    source: (N,) integers, the placed mirror each ray left at the level above (-1: none), which the ray cannot hit
+    (mnrf_place_mirrors_from; converted to int32 like any input), or None: mnrf_place_mirrors itself."""
     for name, t in (("depth", depth), ("mask", mask), ("normal", normal), ("x_surface", x_surface)):
         _lib.written(t, _lib.F32, name)
     _lib.written(mask_bool, _lib.BYTE, "mask_bool")
     _lib.written(flag, _lib.I32, "flag")
     _lib.written(index, _lib.I32, "index")
-    _place_mirrors(_lib.f32_in(rays), packed, near, depth, mask, normal, x_surface, mask_bool, flag, index)
+    if source is not None and tuple(source.shape) != (rays.shape[0],):
+        raise ValueError(f"source holds one mirror index per ray, ({rays.shape[0]},), not {tuple(source.shape)}")
+    _place_mirrors(_lib.f32_in(rays), packed, near, depth, mask, normal, x_surface, mask_bool, flag, index, _lib.i32_in(source), source is not None)
 
 
-def _place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool, flag, index):
-    """place_mirrors for the driver, whose tensors are float32 / int32 rows already."""
+def _place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool, flag, index, source=None, exclude=False):
+    """place_mirrors for the driver, whose tensors are float32 / int32 rows already.  exclude: the launch is
+    mnrf_place_mirrors_from, with `source` ((N,) int32, or None where no ray of the level has one)."""
     p = _lib.ptr
     K, kinds, shapes, axes, positions, frames, normals, rects = packed
-    _lib.check(_lib.lib().mnrf_place_mirrors(
-        p(rays), rays.shape[0], K, kinds, shapes, axes, positions, frames, normals, rects, float(near), p(depth), p(mask), p(normal),
-        p(x_surface), ctypes.c_void_p(mask_bool.data_ptr()) if mask_bool is not None else None, p(flag), p(index), _lib.stream()),
-        "mnrf_place_mirrors")
+    head = (p(rays), rays.shape[0], K, kinds, shapes, axes, positions, frames, normals, rects, float(near))
+    tail = (p(depth), p(mask), p(normal), p(x_surface), ctypes.c_void_p(mask_bool.data_ptr()) if mask_bool is not None else None,
+            p(flag), p(index), _lib.stream())
+    if exclude:
+        _lib.check(_lib.lib().mnrf_place_mirrors_from(*head, p(source), *tail), "mnrf_place_mirrors_from")
+    else:
+        _lib.check(_lib.lib().mnrf_place_mirrors(*head, *tail), "mnrf_place_mirrors")
 
+
+def mirror_sources(level_index, compaction_index, m, n_rep=1, device=None):
+    """The `source` row of the next level (mnrf_mirror_sources): (n_rep * m,) int32 with row j * m + p =
+    level_index[compaction_index[p]].  level_index: the (N,) int32 index this level's mnrf_place_mirrors wrote, or None (-1
+    everywhere); compaction_index: (m,) int32 rows of it, or None (p itself); device: where the row is made when both are None."""
+    given = level_index if level_index is not None else compaction_index
+    out = torch.empty(n_rep * m, dtype=torch.int32, device=given.device if given is not None else device)
+    p = _lib.ptr
+    _lib.check(_lib.lib().mnrf_mirror_sources(p(level_index), p(compaction_index), m, n_rep, p(out), _lib.stream()), "mnrf_mirror_sources")
+    return out
+
+
+def refuse_source(kwargs):
+    """The refusals of exclude_source_mirror= and source_mirror= that need no look at the rays, each with its reason."""
+    on = kwargs.get("exclude_source_mirror", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"exclude_source_mirror is a bool, not {on!r}")
+    if on and kwargs.get("new_mirrors") is None:
+        raise ValueError("exclude_source_mirror=True keeps a ray from hitting the placed mirror it has just left: it needs new_mirrors=")
+    if kwargs.get("source_mirror") is not None and not on:
+        raise ValueError("source_mirror= is read by exclude_source_mirror=True alone (the placed mirror each ray of the call left)")
+
+
+def resolve_source(kwargs, rays):
+    """exclude_source_mirror=, source_mirror= -> (on, the (N,) int32 source of the call's own rays or None: all -1).  The tensor is an
+    input, but one that says what it is by its dtype: another dtype, shape or device is refused, another layout is converted."""
+    refuse_source(kwargs)
+    on, source = bool(kwargs.get("exclude_source_mirror", False)), kwargs.get("source_mirror")
+    if source is None:
+        return on, None
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.int32:
+        raise ValueError("source_mirror must be an int32 tensor (an index into new_mirrors= per ray, -1 for none), not "
+                         f"{getattr(source, 'dtype', type(source).__name__)}")
+    if tuple(source.shape) != (rays.shape[0],):
+        raise ValueError(f"source_mirror holds one index per ray of the call, ({rays.shape[0]},), not {tuple(source.shape)}")
+    if source.device != rays.device:
+        raise ValueError(f"source_mirror is on {source.device}, the rays are on {rays.device}")
+    return on, source.contiguous()

@@ -15,7 +15,8 @@ order-preserving compaction and blending are the HIP kernels mnrf_threshold_mask
 mnrf_reflect_compact and mnrf_blend_scatter; the applications add mnrf_place_mirror,
 mnrf_transform_rays, mnrf_object_rays and mnrf_object_merge (with object bounds: mnrf_object_cull and
 mnrf_object_merge_indexed; several objects, placed_objects=: mnrf_objects_cull and mnrf_objects_merge; several mirrors on any
-plane, new_mirrors=: mnrf_place_mirrors); roughness adds mnrf_reflect_jitter_fan and mnrf_jitter_mean (a roughness per
+plane, new_mirrors=: mnrf_place_mirrors; with exclude_source_mirror=: mnrf_place_mirrors_from and mnrf_mirror_sources);
+roughness adds mnrf_reflect_jitter_fan and mnrf_jitter_mean (a roughness per
 mirror, rough_times=: mnrf_rough_rows, mnrf_perturb_normals and mnrf_reflect_jitter_fan_rows beside them).  One 4-byte device->host
 read per level decides
 whether (and how many) reflected rays are traced -- the reference syncs at the same place
@@ -210,6 +211,9 @@ def _refuse_apps(args, models, kwargs):
     elif kwargs.get("scene_roughness") not in (None, 0, 0.0):
         raise ValueError(f"scene_roughness={kwargs['scene_roughness']!r} is read by the per-mirror roughness route alone: pass "
                          "rough_times=T (the number of jittered reflections beside the first)")
+    if kwargs.get("exclude_source_mirror", False) is not False or kwargs.get("source_mirror") is not None:
+        from .placed_mirrors import refuse_source     # allowed wherever new_mirrors= is; the tensor is looked at with the rays
+        refuse_source(kwargs)
     if multi:                                         # its own refusals; what it is allowed beside keeps its own, below
         from .placed_mirrors import refuse as refuse_mirrors
         refuse_mirrors(args, models, kwargs)
@@ -288,10 +292,11 @@ def _place_mirror(r, rays_chunk, sel, plane, near, flag):
     return mask
 
 
-def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index):
+def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index, source=None, exclude=False):
     """The K-mirror rule on one level's maps, in place (placed_mirrors.py, mnrf_place_mirrors): _place_mirror's edits of the
     result dict for the mirrors `packed` (placed_mirrors.pack); index: (N,) int32 that receives the mirror each ray took, or
-    None."""
+    None.  exclude: mnrf_place_mirrors_from with the level's `source` ((N,) int32: the placed mirror each ray left at the level
+    above, which it cannot hit; None: no ray has one)."""
     from .placed_mirrors import _place_mirrors as place_mirrors
     N = rays_chunk.shape[0]
     for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
@@ -300,7 +305,7 @@ def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index):
     mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
     mask, depth, normal = r[mkey], r[f"depth_{sel}"], _pick_normal(r, sel)
     merged = torch.empty(N, dtype=torch.bool, device=rays_chunk.device)
-    place_mirrors(rays_chunk, packed, near, depth, mask, normal, r[f"x_surface_{sel}"], merged, flag, index)
+    place_mirrors(rays_chunk, packed, near, depth, mask, normal, r[f"x_surface_{sel}"], merged, flag, index, source, exclude)
     r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
     if "depth_fine" in r:
         r["depth_fine"] = depth
@@ -911,6 +916,18 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     new_mirror=, the single-object keywords and roughness.  The result gains new_mirror_index: int32 per ray of the call's own
     rays, the mirror the ray took at level 0, -1 for none.
 
+    exclude_source_mirror=True (a bool; default False: nothing changes) with new_mirrors=: a ray never re-hits the placed mirror it
+    has just left (include/mnrf.h mnrf_place_mirrors_from).  A ray reflected off a tilted frame mirror starts within
+    an ulp of that mirror's plane, on either side; without the keyword THE RULE finds the same mirror again at a distance of 1e-9
+    to 1e-7 and reflects the ray a second time off it.  With it every ray of a level carries `source`, the index in the list of
+    the placed mirror it was reflected off at the level directly above (-1: the scene's own mirror, no mirror, a ray of the call),
+    and mirror `source` is no hit: every level that applies the list keeps its index, stage_b makes the next level's row from it
+    through the compaction (mnrf_mirror_sources: the plain reflection, the rough_times fan and its one-by-one form), and the
+    launch is mnrf_place_mirrors_from.  Only the mirror left directly above is excluded: a ray may return to it after another
+    bounce.  source_mirror= ((N,) int32 on the rays' device, default all -1; another dtype, shape or device is refused): the
+    `source` of the call's own rays, for a caller that traces level by level; sliced per chunk.  Allowed wherever new_mirrors=
+    is; under substitution nothing recurses, so it changes nothing there.  new_mirror_index stays level 0's.
+
     rough_times=T (an int >= 1; None, the default: off) with scene_roughness=S (float32, >= 0, finite; default 0) and the
     `roughness` of each PlacedMirror: a roughness PER MIRROR (include/mnrf.h "A roughness per mirror").  At a level
     that traces, the std of ray i is the roughness of the placed mirror it took at THAT level (mnrf_place_mirrors' index) or S
@@ -934,6 +951,10 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         args = SimpleNamespace(**args)
     _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
     rays = _lib.f32_in(rays)             # once per call: every launch of every level reads the chunk as (N,8) float32 rows
+    exclude, source_all = False, None                                      # exclude_source_mirror=, source_mirror=
+    if kwargs.get("exclude_source_mirror", False) or kwargs.get("source_mirror") is not None:
+        from .placed_mirrors import mirror_sources, resolve_source
+        exclude, source_all = resolve_source(kwargs, rays)
     objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
     placed = kwargs.get("placed_objects")
     single = objects and placed is None                                    # the single-object keywords
@@ -1005,7 +1026,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     # Level 0 runs in two stages so that chunk k+1's primary pass can be queued BEFORE the host waits for chunk k's
     # "any mirror pixel" flag (eval.py:303-312 branches on it): the GPU then never idles on that read.  Not used with the
     # roughness jitters, whose random draws would change order against the primary passes.
-    def stage_a(rays_chunk, level, host_flags=None, slot=0):
+    def stage_a(rays_chunk, level, host_flags=None, slot=0, source=None):
         # The last level of a recursion traces nothing: its caller (stage_b of the level above) reads rgb_* and depth_* of it
         # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
         # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
@@ -1060,11 +1081,12 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
         if place and not last:
             edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
         # (with a roughness per mirror every level that places mirrors keeps its index: the std of a ray follows the mirror it
-        # took at THAT level; only level 0's is returned)
-        if multi and (level == 0 or (rough_rows and not last)):      # the mirror each ray took; -1 where the list is not applied
+        # took at THAT level; only level 0's is returned.  exclude_source_mirror keeps it too: it is the next level's `source`)
+        if multi and (level == 0 or ((rough_rows or exclude) and not last)):      # the mirror each ray took; -1 where the list is not applied
             r["new_mirror_index"] = torch.full((rays_chunk.shape[0],), -1, dtype=torch.int32, device=rays_chunk.device)
         if multi and not last:
-            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index"))  # noqa: E731
+            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index"),  # noqa: E731
+                                               source, exclude)
         pending, any_mirror, counted = None, False, None
         if mask is not None:
             if host_flags is not None and not last and rays_chunk.shape[0]:
@@ -1104,8 +1126,12 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
 
     placed_renderers = [placed_renderer(o) for o in placed] if placed is not None else None
 
-    def recurse(rays_chunk, level):
-        return stage_b(stage_a(rays_chunk, level))
+    def recurse(rays_chunk, level, source=None):
+        return stage_b(stage_a(rays_chunk, level, source=source))
+
+    def sources(r, index, m, n_rep=1):
+        # the `source` of the rays reflected off this level (mnrf_mirror_sources): the mirror each took here, through the compaction
+        return mirror_sources(r.get("new_mirror_index"), index, m, n_rep, r[f"rgb_{sel}"].device) if exclude else None
 
     def stage_b(state):
         r, rays_chunk, level, mask, any_mirror, pending, counted = state
@@ -1147,7 +1173,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                                  only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
                                  current_epoch=fine_epoch + 1, _guard=False, _maps_only=True, _rgb_depth_only=True)
             else:
-                r2 = recurse(sec.contiguous(), level + 1)
+                r2 = recurse(sec.contiguous(), level + 1, sources(r, index, sec.shape[0]))
             if rough:                                                     # eval.py:622-674
                 # THE RULE of include/mnrf.h "Mirror roughness" (DESIGN 4.4b).  The reference adds the (M,3) colours of each
                 # jittered render, M = sum(mask), to the first secondary render, which at level 0 has N rows: that works only
@@ -1221,7 +1247,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
                         else:         # one by one: a jitter is mnrf_perturb_normals, then mnrf_reflect_compact on J's mask
                             s2 = _reflect(rays_chunk, r[f"x_surface_{sel}"], _perturb_normals(normal, draw(N, dev), std_rows),
                                           jitter_mask, True, want_dir=False)[0].contiguous()
-                        r3 = recurse(s2, level + 1)
+                        r3 = recurse(s2, level + 1, sources(r, jit_index, mj, n_g))      # (one by one: J's own compaction, n_g = 1)
                         g += n_g
                         for k in keys:
                             _jitter_mean(r2[k], r3[k], acc_index, mj, n_g, finish if g >= rough_times else None)
@@ -1249,15 +1275,16 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     pipelined = rays.is_cuda and not (rough or rough_rows) and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
     host_flags = torch.zeros(2, dtype=torch.int32).pin_memory() if pipelined else None
     host_counts = torch.zeros(2, dtype=torch.int64).pin_memory() if pipelined else None
-    ahead = stage_a(rays[:chunk].contiguous(), 0, host_flags, 0) if (pipelined and starts) else None
+    chunk_source = lambda i: source_all[i:i + chunk] if source_all is not None else None  # noqa: E731
+    ahead = stage_a(rays[:chunk].contiguous(), 0, host_flags, 0, chunk_source(0)) if (pipelined and starts) else None
     for n_c, i in enumerate(starts):
         if pipelined:
             state = ahead
-            ahead = stage_a(rays[starts[n_c + 1]:starts[n_c + 1] + chunk].contiguous(), 0, host_flags, (n_c + 1) % 2) \
-                if n_c + 1 < len(starts) else None
+            ahead = stage_a(rays[starts[n_c + 1]:starts[n_c + 1] + chunk].contiguous(), 0, host_flags, (n_c + 1) % 2,
+                            chunk_source(starts[n_c + 1])) if n_c + 1 < len(starts) else None
             out = stage_b(state)
         else:
-            out = recurse(rays[i:i + chunk].contiguous(), 0)
+            out = recurse(rays[i:i + chunk].contiguous(), 0, chunk_source(i))
         if stage_maps:
             done = torch.cuda.Event()
             done.record()

@@ -72,6 +72,17 @@ reads, and the estimate t(off) + T x |J| x c with c = t(off) / (rays the roughne
 with the mirror polished and no rough_times.  (c) the same with scene_roughness=0.01.  Nothing is asserted.
 
     python scripts/bench_apps.py --rough_mirrors [--reps 7] > profiles/rough_mirrors_bench.json
+
+--mirrors_facing runs the leg of exclude_source_mirror= INSTEAD, on the --mirrors leg's workload with near = 1e9: two parallel frame
+mirrors tilted by 0.3 rad about z, one unit in front of the camera (3 x 3, facing it) and one unit behind it (8 x 8, facing it),
+at max_recursive_level 1, 2 and 4, each with the keyword off and on.  One warm-up and one counting frame per route, then --reps
+rounds (default 7) alternating the six routes frame by frame; median and spread per route, the rays each level renders (level 0:
+the frame's; level L + 1: the rows the L-th reflection of a chunk hands on), and the smallest level-1 depth on the rows that
+took the first mirror -- the self-hits of the route without the keyword.  At level 1 the keyword changes no ray: `on_over_off`
+stands beside the two spreads.  At levels 2 and 4 the two routes trace different rays -- a self-hit row goes on bouncing off
+one mirror, an excluded one crosses to the other -- so their times are not compared: nothing is asserted, no speed-up is claimed.
+
+    python scripts/bench_apps.py --mirrors_facing [--reps 7] > profiles/mirrors_facing_bench.json
 """
 import argparse
 import json
@@ -400,6 +411,63 @@ def mirrors_leg(a, models, emb, rays, dev, base_args):
     return res
 
 
+def mirrors_facing_leg(a, models, emb, rays, dev, base_args):
+    """The --mirrors_facing leg (module docstring) -> the result dict."""
+    import math
+    import numpy as np
+    from mirror_nerf_amd import PlacedMirror
+    reps = a.reps
+    eye = np.array((0.0, -4.0, 1.5))                                        # synthetic.look_at_pose's defaults
+    view = -eye / np.linalg.norm(eye)
+    right = np.cross(view, (0.0, 0.0, 1.0))
+    right /= np.linalg.norm(right)
+    tilt = -math.cos(0.3) * view + math.sin(0.3) * right
+    pair = [PlacedMirror(eye + view, tilt, (0, 0, 1), (3, 3)), PlacedMirror(eye - view, -tilt, (0, 0, 1), (8, 8))]
+
+    def route(level, on):
+        args = dict(base_args, max_recursive_level=level, near=1e9)
+        kw = dict(exclude_source_mirror=True) if on else {}
+
+        def frame():
+            out = M.batched_inference(models, emb, rays, N_SAMPLES, N_IMPORTANCE, False, CHUNK, args=args, trace_secondary_rays=True,
+                                      to_cpu=False, maps_only=True, new_mirrors=pair, **kw)
+            torch.cuda.synchronize()
+            return out
+
+        frame()
+        # the reflections of a chunk run depth first: the one that does not compact is level 0's, each further one a level deeper
+        per_level, level_now, reflect = [int(rays.shape[0])] + [0] * level, [0], REC._reflect
+
+        def counting_reflect(rays_, x, n, mask, compact, *a_, **k):
+            got = reflect(rays_, x, n, mask, compact, *a_, **k)
+            level_now[0] = level_now[0] + 1 if compact else 0
+            per_level[level_now[0] + 1] += int(got[0].shape[0])
+            return got
+
+        REC._reflect = counting_reflect
+        try:
+            out = frame()
+        finally:
+            REC._reflect = reflect
+        first = out["new_mirror_index"] == 0
+        got = {"rays_per_level": per_level, "rays_that_took_each_mirror_level0": torch.bincount(out["new_mirror_index"].clamp(min=-1).long() + 1,
+                                                                                                minlength=3)[1:].tolist()}
+        if level >= 2 and bool(first.any()):
+            depth = out["depth_fine_reflect"][first]
+            got.update(min_level1_depth_on_first_mirror_rows=float(depth.min()), level1_depth_below_1e_6=int((depth < 1e-6).sum()))
+        return got, frame
+
+    routes = {f"l{level}_{'on' if on else 'off'}": route(level, on) for level in (1, 2, 4) for on in (False, True)}
+    res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, all-mirror "
+                       "random-init pair (bench.py config 2), near 1e9 (nothing hides a mirror), maps_only; two parallel frame mirrors tilted by "
+                       "0.3 rad about z, one unit in front of the camera (3 x 3) and one unit behind it (8 x 8), facing each other",
+           "protocol": f"one warm-up and one counting frame per route, then {reps} rounds alternating the six routes frame by frame; host clock "
+                       "around a frame that ends in a synchronise; median, spread = (max - min) / median of a route's frames"}
+    res.update(_alternate(routes, reps))
+    res["l1_on_over_off"] = round(res["l1_on"]["ms_per_frame"] / res["l1_off"]["ms_per_frame"], 4)
+    return res
+
+
 def _rough_frames(models, emb, rays, n_imp, chunk, args, reps, std):
     """One warm-up frame, one frame that counts the compacting _reflect calls (each reads its count on the host) and the rows
     of every render_rays call, then `reps` timed frames -> dict."""
@@ -609,8 +677,9 @@ def main():
     ap.add_argument("--rough_child", action="store_true", help="(--rough's child process) part (a) on the package of --package_root")
     ap.add_argument("--package_root", type=str, default=None, metavar="DIR", help="(--rough's child process) the tree whose package is imported")
     ap.add_argument("--rough_mirrors", action="store_true", help="run the leg of a roughness per mirror instead of the others")
+    ap.add_argument("--mirrors_facing", action="store_true", help="run the leg of exclude_source_mirror= (two facing mirrors) instead of the others")
     a = ap.parse_args()
-    a.reps = a.reps or (7 if (a.objects or a.mirrors or a.rough or a.rough_child or a.rough_mirrors) else 3)
+    a.reps = a.reps or (7 if (a.objects or a.mirrors or a.rough or a.rough_child or a.rough_mirrors or a.mirrors_facing) else 3)
     dev = "cuda:0"
     if a.rough_child:
         print(json.dumps(rough_all_mirror(dev, a.reps)))
@@ -677,6 +746,9 @@ def main():
         return
     if a.mirrors:
         print(json.dumps(mirrors_leg(a, models, emb, rays, dev, base_args)))
+        return
+    if a.mirrors_facing:
+        print(json.dumps(mirrors_facing_leg(a, models, emb, rays, dev, base_args)))
         return
     off, ms_off, t_off, traced_off = run(base_args)
     res = {"workload": f"batched_inference {W}x{H}, {N_SAMPLES} coarse + {N_SAMPLES + N_IMPORTANCE} fine samples/ray, chunk {CHUNK}, "

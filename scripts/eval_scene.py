@@ -57,6 +57,9 @@ follows --root_dir).  --mirrors_json FILE, a JSON list of up to 8 entries
 the scene does not hide wins.  It implies tracing, may be combined with --objects_json (a placed object is then seen in the
 placed mirrors) and is refused beside --app_place_new_mirror.  An entry of either kind may carry "roughness": s, the standard
 deviation of the normal jitter of the rays that take that mirror (read with --rough_times, below).
+--exclude_source_mirror, beside --mirrors_json and --max_recursive_level 2 or more: a reflected ray never re-hits the placed
+mirror it has just left (batched_inference(exclude_source_mirror=True)) -- what two mirrors that face each other need unless
+their normals are world axes.
 
 Mirror roughness (run.sh "control_mirror_roughness"): --app_control_mirror_roughness --trace_ray_times T --normal_noise_std S
 renders every mirror pixel as the mean of T + 1 reflections about jittered normals (batched_inference's roughness rule: a
@@ -141,6 +144,8 @@ def get_opts(argv=None):
     ap.add_argument("--plane_pos", type=str, default="plane_x", choices=("plane_x", "plane_y"))
     ap.add_argument("--mirrors_json", type=str, default=None,
                     help="several new mirrors: a JSON list of {center, normal, up, size, shape} or {axis, position, normal, rect, shape}")
+    ap.add_argument("--exclude_source_mirror", action="store_true",
+                    help="with --mirrors_json: a reflected ray never re-hits the placed mirror it has just left (facing mirrors, two bounces or more)")
     # mirror roughness, named as in the reference's eval.py:60-70
     ap.add_argument("--app_control_mirror_roughness", action="store_true",
                     help="render mirror pixels as the mean of trace_ray_times + 1 reflections about jittered normals")
@@ -179,6 +184,8 @@ def get_opts(argv=None):
         if args.mirrors_json is not None:
             ap.error("app_control_mirror_roughness cannot be combined with new_mirrors= (one application at a time, except "
                      "placed mirrors with placed objects or substitution)")
+    if args.exclude_source_mirror and args.mirrors_json is None:
+        ap.error("--exclude_source_mirror keeps a ray from hitting the placed mirror it has just left: it needs --mirrors_json")
     if args.mirrors_json is not None and args.app_place_new_mirror:
         ap.error("--mirrors_json carries every new mirror: it cannot be combined with --app_place_new_mirror (an entry "
                  "{axis, position, normal, rect} is that mirror)")
@@ -386,6 +393,8 @@ def render(system, rays, args, obj=None, frame_time=None, placed=None, mirrors=N
         extra = {"placed_objects": placed}
     if mirrors is not None:
         extra["new_mirrors"] = mirrors
+        if getattr(args, "exclude_source_mirror", False):
+            extra["exclude_source_mirror"] = True
     if getattr(args, "rough_times", None) is not None:
         extra.update(rough_times=args.rough_times, scene_roughness=args.scene_roughness)
     if "render_kwargs_test_d_nerf" in extra:
