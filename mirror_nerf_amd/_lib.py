@@ -186,6 +186,14 @@ if os.environ.get("MNRF_CHECK_ABI", "") == "1":
     _enter_checked()
 
 
+def preset(table, root_dir):
+    """The first entry of a preset table ((key, dict), ...) whose key is a substring of root_dir (None: the reference's `else`)."""
+    for key, value in table:
+        if key is None or key in (root_dir or ""):
+            return dict(value)
+    raise AssertionError("preset tables end with a default entry")
+
+
 # ---- the rule of the public entry points for a caller's tensor of another precision or layout: an input is converted, a tensor
 # the call writes into is refused (DESIGN "The Python-to-kernel boundary").  Applied where a tensor enters, never per launch.
 

@@ -477,7 +477,6 @@ def _arkit_meta(root_dir, split, img_wh, near, far, scale_factor, val_idx, train
     """Everything of read_arkit but the pixels: dict(frames: the split's frame entries (None for the path splits), poses_f64
     (F, 3, 4), poses float32, focal, near, far, pose_avg)."""
     from . import poses as P
-    from .recursion import _preset
     if split not in IMAGE_SPLITS + PATH_SPLITS:
         raise ValueError(f"read_arkit: split must be one of {IMAGE_SPLITS + PATH_SPLITS}, not {split!r}")
     with open(os.path.join(root_dir, "transforms.json"), "r") as f:
@@ -509,7 +508,7 @@ def _arkit_meta(root_dir, split, img_wh, near, far, scale_factor, val_idx, train
 
     frames = meta["frames"]
     if split == "test_rotate":                                       # real_arkit.py:153-169
-        preset = _preset(ROTATE_PRESETS, root_dir)
+        preset = _lib.preset(ROTATE_PRESETS, root_dir)
         idx = val_idx if preset["frame"] is None else preset["frame"]
         base = poses_all[idx].copy()
         base[2, 3] += preset["dz"]

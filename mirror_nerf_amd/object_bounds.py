@@ -43,6 +43,17 @@ def _res3(res):
     return tuple(int(r) for r in res)
 
 
+def _object_system(system_obj):
+    """(models, embeddings) of system_obj as the dicts render_rays takes: nerf_pl keeps lists, [coarse, fine] and [xyz, dir]
+    (models/nerf_pl/rendering_nerfpl.py:138-140, 197)."""
+    models, embeddings = system_obj.models, system_obj.embeddings
+    if not isinstance(models, dict):
+        models = dict(zip(("coarse", "fine"), models))
+    if not isinstance(embeddings, dict):
+        embeddings = dict(zip(("xyz", "dir"), embeddings))
+    return models, embeddings
+
+
 def words_per_row(rx):
     return (int(rx) + 31) // 32
 
@@ -133,7 +144,7 @@ class ObjectBounds:
 
     # ---- the device passes
     def cull(self, rays, xform):
-        """mnrf_object_cull on one level's rays (N, 8) with the ray move `xform` (recursion.resolve_new_object) ->
+        """mnrf_object_cull on one level's rays (N, 8) with the ray move `xform` (placed_objects.resolve_new_object) ->
         (object-frame rays of the kept rays (N, 8), their rows (N,) int32, count (1,) int32 on the device): rows from count on
         are undefined.  rays of another precision or layout are converted."""
         return self._cull(_lib.f32_in(rays), xform)
@@ -221,7 +232,6 @@ def estimate_object_bounds(obj, region_lo, region_hi, res=64, frame_time=None, s
                 volume[start:start + cnt] = dnerf_field(net, cnt, float(frame_time), xyz=xyz, sigma_only=True, want_dx=False)["sigma"]
         volume = volume.view(n, n, n)
     else:                                                                        # nerf_pl
-        from .recursion import _object_system
         models, embeddings = _object_system(obj)
         model = models["fine"] if "fine" in models else models["coarse"]
         volume = mesh.density_grid(model, embeddings["xyz"], *ranges, n)

@@ -25,11 +25,53 @@ import numpy as np
 import torch
 
 from . import _lib
+from .placed_objects import SINGLE_OBJECT_KEYWORDS
 
-__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors", "mirror_sources", "roughness_row"]
+__all__ = ["PlacedMirror", "MAX_MIRRORS", "pack", "place_mirrors", "mirror_sources", "roughness_row", "PLACE_MIRROR_PRESETS",
+           "resolve_new_mirror"]
 
 MAX_MIRRORS = 8      # MNRF_MIRRORS_MAX
 SHAPES = ("rect", "ellipse")
+
+# app_place_new_mirror presets (eval.py:369-433), restated as data: the first entry whose key is a substring of args.root_dir
+# wins (None: the reference's `else`).  position: the plane x = position (plane_x) or y = position (plane_y); rect: the
+# rectangle (u0, u1, w0, w1) on the plane's (y, z) resp. (x, z).  The livingroom plane_y preset assigns position and rectangle
+# twice (eval.py:421-425): the last assignment is the one the reference uses.
+PLACE_MIRROR_PRESETS = {
+    "plane_x": (
+        ("livingroom", dict(position=0.0, normal=(-1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),     # eval.py:370-374
+        ("washroom", dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),      # eval.py:375-378
+        ("office", dict(position=1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),         # eval.py:379-382
+        (None, dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:383-386
+    ),
+    "plane_y": (
+        ("washroom", dict(position=1.3, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -1.0, 1.0))),       # eval.py:416-419
+        ("livingroom", dict(position=1.65, normal=(0.0, -1.0, 0.0), rect=(-0.3, 1.5, -0.5, 1.0))),    # eval.py:420-425
+        ("office", dict(position=0.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),         # eval.py:426-429
+        (None, dict(position=1.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:430-433
+    ),
+}
+
+
+def resolve_new_mirror(args, new_mirror=None):
+    """The plane of app_place_new_mirror: dict(axis="x"|"y", position, normal (3,), rect (u0, u1, w0, w1)).  `new_mirror`
+    (same keys) overrides the preset that args.plane_pos / args.root_dir select (eval.py:369-433)."""
+    if new_mirror is not None:
+        nm = dict(new_mirror)
+        missing = {"axis", "position", "normal", "rect"} - set(nm)
+        if missing:
+            raise ValueError(f"new_mirror needs the keys axis, position, normal, rect (missing: {sorted(missing)})")
+        if nm["axis"] not in ("x", "y"):
+            raise ValueError(f"new_mirror axis must be 'x' or 'y', not {nm['axis']!r}")
+        if len(nm["normal"]) != 3 or len(nm["rect"]) != 4:
+            raise ValueError("new_mirror normal has 3 entries and rect 4 (u0, u1, w0, w1)")
+        return dict(axis=nm["axis"], position=float(nm["position"]), normal=tuple(float(v) for v in nm["normal"]),
+                    rect=tuple(float(v) for v in nm["rect"]))
+    plane_pos = getattr(args, "plane_pos", "plane_x")            # eval.py get_opt: default plane_x
+    if plane_pos not in PLACE_MIRROR_PRESETS:
+        raise ValueError(f"args.plane_pos must be 'plane_x' or 'plane_y', not {plane_pos!r}")
+    p = _lib.preset(PLACE_MIRROR_PRESETS[plane_pos], getattr(args, "root_dir", ""))
+    return dict(axis=plane_pos[-1], **p)
 
 
 def _f32(v):
@@ -150,7 +192,6 @@ def refuse(args, models, kwargs):
     if getattr(args, "app_place_new_mirror", False) or kwargs.get("new_mirror") is not None:
         raise ValueError("new_mirrors= carries every mirror of the call: it cannot be combined with app_place_new_mirror or new_mirror= "
                          "(the single mirror; PlacedMirror.axis_aligned takes its keys)")
-    from .placed_objects import SINGLE_OBJECT_KEYWORDS
     given = [k for k in SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
     if given or (getattr(args, "app_reflect_newly_placed_objects", False) and kwargs.get("placed_objects") is None):
         raise ValueError("new_mirrors= is combined with objects through placed_objects=[PlacedObject(...), ...], not with the "
@@ -225,6 +266,49 @@ def _place_mirrors(rays, packed, near, depth, mask, normal, x_surface, mask_bool
         _lib.check(_lib.lib().mnrf_place_mirrors_from(*head, p(source), *tail), "mnrf_place_mirrors_from")
     else:
         _lib.check(_lib.lib().mnrf_place_mirrors(*head, *tail), "mnrf_place_mirrors")
+
+
+def _edit_level(r, rays_chunk, sel, launch):
+    """What placing one mirror and placing a list share, on one level's maps in place: the maps the launch writes are made
+    contiguous, launch(depth, mask, normal, x_surface, merged) runs, the returned mirror mask becomes the merged bool tensor
+    (eval.py:492-496) and depth_fine the edited depth (eval.py:497-500).  The normal is the composited predicted one, else the
+    composited grad normal (eval.py:338-360); -> the level's float mask."""
+    for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
+        if k in r and not r[k].is_contiguous():
+            r[k] = r[k].contiguous()
+    mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
+    mask, depth = r[mkey], r[f"depth_{sel}"]
+    merged = torch.empty(rays_chunk.shape[0], dtype=torch.bool, device=rays_chunk.device)
+    normal = r[f"surface_normal_{sel}"] if f"surface_normal_{sel}" in r else r[f"surface_normal_grad_{sel}"]
+    launch(depth, mask, normal, r[f"x_surface_{sel}"], merged)
+    r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
+    if "depth_fine" in r:
+        r["depth_fine"] = depth
+    elif "depth_coarse" in r:
+        r["depth_coarse"] = depth
+    return mask
+
+
+def _place_mirror_level(r, rays_chunk, sel, plane, near, flag):
+    """eval.py:364-504 on one level's maps, in place (mnrf_place_mirror, _edit_level); `flag` (device int32) is OR-ed with "any
+    mirror after the merge"."""
+    def launch(depth, mask, nrm, x_surface, merged):
+        p = _lib.ptr
+        nx, ny, nz = plane["normal"]
+        u0, u1, w0, w1 = plane["rect"]
+        _lib.check(_lib.lib().mnrf_place_mirror(
+            p(rays_chunk), rays_chunk.shape[0], _lib.MNRF_PLANE_Y if plane["axis"] == "y" else _lib.MNRF_PLANE_X, plane["position"],
+            nx, ny, nz, u0, u1, w0, w1, float(near), p(depth), p(mask), p(nrm), p(x_surface), ctypes.c_void_p(merged.data_ptr()),
+            p(flag), _lib.stream()), "mnrf_place_mirror")
+    return _edit_level(r, rays_chunk, sel, launch)
+
+
+def _place_mirrors_level(r, rays_chunk, sel, packed, near, flag, index, source=None, exclude=False):
+    """The K-mirror rule on one level's maps, in place (mnrf_place_mirrors, _edit_level) for the mirrors `packed` (pack); index:
+    (N,) int32 that receives the mirror each ray took, or None.  exclude: mnrf_place_mirrors_from with the level's `source`
+    ((N,) int32: the placed mirror each ray left at the level above, which it cannot hit; None: no ray has one)."""
+    return _edit_level(r, rays_chunk, sel, lambda depth, mask, nrm, x_surface, merged: _place_mirrors(
+        rays_chunk, packed, near, depth, mask, nrm, x_surface, merged, flag, index, source, exclude))
 
 
 def mirror_sources(level_index, compaction_index, m, n_rep=1, device=None):

@@ -32,14 +32,18 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
-from .mirror_nerf import Embedding, MirrorNeRF
+from . import _lib, placed_mirrors, placed_objects
+from .mirror_nerf import Embedding, MirrorNeRF, check_guard, release_transient
 from .dnerf import render_rays_dnerf
 from .rendering import render_rays
+# (re-exported: callers reach the presets and resolvers of the applications through this module)
+from .object_bounds import _object_system
+from .placed_mirrors import PLACE_MIRROR_PRESETS, resolve_new_mirror  # noqa: F401
+from .placed_objects import OBJECT_PRESETS, load_object_system, resolve_new_object, resolve_object_bounds  # noqa: F401
 
 RAY_FORWARD_OFFSET = 0.1   # train.py:232, eval.py:529 (absolute near of a reflected ray)
 # Share of rays above the mirror threshold from which the blended-level launch is the faster route for a chunk of a level that
-# traces (batched_inference stage_a): measured, profiles/blended_level_ab.txt section 4 -- 13.60 ms without and 12.55 ms with
+# traces (_stage_a): measured, profiles/blended_level_ab.txt section 4 -- 13.60 ms without and 12.55 ms with
 # every ray a mirror, against 13.21 ms for the field launch and the compositing launch it replaces
 BLENDED_BREAK_EVEN = 0.37
 _MIRROR_FRACTION = weakref.WeakKeyDictionary()      # model of the selected pass -> {recursion level: share last counted}
@@ -49,24 +53,6 @@ _MIRROR_FRACTION = weakref.WeakKeyDictionary()      # model of the selected pass
 ROUGH_FINISH = _lib.MNRF_MEAN_MULTIPLY
 JITTER_RAYS = 262144      # rays per batched group of jittered reflections (roughness, eval.py:622-674)
 
-# app_place_new_mirror presets (eval.py:369-433), restated as data: the first entry whose key is a substring of args.root_dir
-# wins (None: the reference's `else`).  position: the plane x = position (plane_x) or y = position (plane_y); rect: the
-# rectangle (u0, u1, w0, w1) on the plane's (y, z) resp. (x, z).  The livingroom plane_y preset assigns position and rectangle
-# twice (eval.py:421-425): the last assignment is the one the reference uses.
-PLACE_MIRROR_PRESETS = {
-    "plane_x": (
-        ("livingroom", dict(position=0.0, normal=(-1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),     # eval.py:370-374
-        ("washroom", dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),      # eval.py:375-378
-        ("office", dict(position=1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -1.0, 0.75))),         # eval.py:379-382
-        (None, dict(position=-1.0, normal=(1.0, 0.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:383-386
-    ),
-    "plane_y": (
-        ("washroom", dict(position=1.3, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -1.0, 1.0))),       # eval.py:416-419
-        ("livingroom", dict(position=1.65, normal=(0.0, -1.0, 0.0), rect=(-0.3, 1.5, -0.5, 1.0))),    # eval.py:420-425
-        ("office", dict(position=0.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),         # eval.py:426-429
-        (None, dict(position=1.0, normal=(0.0, -1.0, 0.0), rect=(-1.0, 1.0, -0.5, 0.5))),             # eval.py:430-433
-    ),
-}
 # app_reflection_substitution presets (eval.py:551-591): how the reflected rays are moved into the substituted scene.
 # rotation: the 3x3 of the market `pose_align` (its translation column is zero), directions re-normalised after it.
 SUBSTITUTION_PRESETS = (
@@ -75,100 +61,11 @@ SUBSTITUTION_PRESETS = (
                     translation=(0.0, 0.0, 0.0))),                                                          # eval.py:555-583
     (None, dict(rotation=None, scale=1.0, translation=(0.0, 0.0, 0.0))),                                    # eval.py:584-586
 )
-# app_reflect_newly_placed_objects presets (eval.py:177-190): how a level's rays are moved into the object's frame.  pose_align
-# is None in every branch of the reference (eval.py:177); `new_object=` of batched_inference may give one.
-OBJECT_PRESETS = (
-    ("livingroom", dict(pose_align=None, scale=2.0, translation=(0.0, 0.0, 0.0))),                          # eval.py:180-184
-    ("washroom", dict(pose_align=None, scale=2.0, translation=(-0.5, -0.5, 0.0))),                          # eval.py:185-187
-    ("office", dict(pose_align=None, scale=2.0, translation=(0.0, 3.0, 0.5))),                              # eval.py:188-190
-    (None, dict(pose_align=None, scale=1.0, translation=(0.0, 0.0, 0.0))),                                  # eval.py:178-179
-)
-
-
-def _preset(table, root_dir):
-    for key, value in table:
-        if key is None or key in (root_dir or ""):
-            return dict(value)
-    raise AssertionError("preset tables end with a default entry")
-
-
-def resolve_new_mirror(args, new_mirror=None):
-    """The plane of app_place_new_mirror: dict(axis="x"|"y", position, normal (3,), rect (u0, u1, w0, w1)).  `new_mirror`
-    (same keys) overrides the preset that args.plane_pos / args.root_dir select (eval.py:369-433)."""
-    if new_mirror is not None:
-        nm = dict(new_mirror)
-        missing = {"axis", "position", "normal", "rect"} - set(nm)
-        if missing:
-            raise ValueError(f"new_mirror needs the keys axis, position, normal, rect (missing: {sorted(missing)})")
-        if nm["axis"] not in ("x", "y"):
-            raise ValueError(f"new_mirror axis must be 'x' or 'y', not {nm['axis']!r}")
-        if len(nm["normal"]) != 3 or len(nm["rect"]) != 4:
-            raise ValueError("new_mirror normal has 3 entries and rect 4 (u0, u1, w0, w1)")
-        return dict(axis=nm["axis"], position=float(nm["position"]), normal=tuple(float(v) for v in nm["normal"]),
-                    rect=tuple(float(v) for v in nm["rect"]))
-    plane_pos = getattr(args, "plane_pos", "plane_x")            # eval.py get_opt: default plane_x
-    if plane_pos not in PLACE_MIRROR_PRESETS:
-        raise ValueError(f"args.plane_pos must be 'plane_x' or 'plane_y', not {plane_pos!r}")
-    p = _preset(PLACE_MIRROR_PRESETS[plane_pos], getattr(args, "root_dir", ""))
-    return dict(axis=plane_pos[-1], **p)
 
 
 def resolve_substitution(args):
     """The ray transform of app_reflection_substitution chosen by args.root_dir (eval.py:551-591)."""
-    return _preset(SUBSTITUTION_PRESETS, getattr(args, "root_dir", ""))
-
-
-def resolve_new_object(args, new_object=None):
-    """The ray move of app_reflect_newly_placed_objects: dict(pose (12 floats, the row-major 3x4 [A | p], or None), scale,
-    translation (3,), pose_scale0).  `new_object=dict(pose_align=None | 3x4 | 4x4, scale=, translation=)` overrides the preset
-    that args.root_dir selects (eval.py:177-190).  pose_scale0 is the fp32 norm of the first column of A (eval.py:194-196) and
-    1 without a pose: the reference leaves `pose_scale` unbound there (eval.py:264), and no alignment is a scale of 1."""
-    if new_object is not None:
-        cfg = dict(new_object)
-        missing = {"pose_align", "scale", "translation"} - set(cfg)
-        if missing:
-            raise ValueError(f"new_object needs the keys pose_align, scale, translation (missing: {sorted(missing)})")
-    else:
-        cfg = _preset(OBJECT_PRESETS, getattr(args, "root_dir", ""))
-    if len(cfg["translation"]) != 3:
-        raise ValueError("new_object translation has 3 entries")
-    scale = float(cfg["scale"])
-    if not scale > 0.0:
-        raise ValueError(f"new_object scale must be positive, not {cfg['scale']!r}")
-    pose, pose_scale0 = None, 1.0
-    if cfg["pose_align"] is not None:
-        m = torch.as_tensor(cfg["pose_align"], dtype=torch.float32)            # eval.py:193 (FloatTensor)
-        if tuple(m.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"new_object pose_align must be None, 3x4 or 4x4, not {tuple(m.shape)}")
-        pose = tuple(float(v) for v in m[:3, :4].reshape(-1))
-        pose_scale0 = float(torch.norm(m[:3, 0]))                              # eval.py:194-196, the only entry that is read
-        if not pose_scale0 > 0.0:
-            raise ValueError("new_object pose_align: the first column of its 3x3 is zero")
-    return dict(pose=pose, scale=scale, translation=tuple(float(v) for v in cfg["translation"]), pose_scale0=pose_scale0)
-
-
-def _object_system(system_obj):
-    """(models, embeddings) of system_obj as the dicts render_rays takes: nerf_pl keeps lists, [coarse, fine] and [xyz, dir]
-    (models/nerf_pl/rendering_nerfpl.py:138-140, 197)."""
-    models, embeddings = system_obj.models, system_obj.embeddings
-    if not isinstance(models, dict):
-        models = dict(zip(("coarse", "fine"), models))
-    if not isinstance(embeddings, dict):
-        embeddings = dict(zip(("xyz", "dir"), embeddings))
-    return models, embeddings
-
-
-def load_object_system(ckpt_path, device, N_importance=64, trusted=False):
-    """The object of app_reflect_newly_placed_objects from a nerf_pl checkpoint (eval.py:1041-1061): the pair of plain NeRF
-    fields -- MirrorNeRF without the optional heads, whose parameter names are nerf_pl's (models/nerf_pl/nerf_nerfpl.py:42-109)
-    -- filled from `nerf_coarse.*` and, with N_importance > 0, `nerf_fine.*`; .models / .embeddings are dicts."""
-    from . import checkpoint
-    models = {}
-    for key in ("coarse", "fine") if N_importance > 0 else ("coarse",):
-        m = MirrorNeRF(in_channels_xyz=63, in_channels_dir=27, predict_normal=False, predict_mirror_mask=False)
-        checkpoint.load_ckpt(m, ckpt_path, model_name="nerf_" + key, trusted=trusted)
-        models[key] = m.to(device).eval()
-    return SimpleNamespace(models=models, embeddings={"xyz": Embedding(10), "dir": Embedding(4)})
+    return _lib.preset(SUBSTITUTION_PRESETS, getattr(args, "root_dir", ""))
 
 
 def resolve_rough_rows(kwargs):
@@ -178,8 +75,7 @@ def resolve_rough_rows(kwargs):
         return None, 0.0
     if isinstance(times, bool) or not isinstance(times, (int, np.integer)) or times < 1:
         raise ValueError(f"rough_times is an int of at least 1 (the jittered reflections beside the first; None: off), not {times!r}")
-    from .placed_mirrors import _roughness
-    return int(times), _roughness(kwargs.get("scene_roughness", 0.0), "scene_roughness")
+    return int(times), placed_mirrors._roughness(kwargs.get("scene_roughness", 0.0), "scene_roughness")
 
 
 def _refuse_rough_rows(args, kwargs):
@@ -191,8 +87,7 @@ def _refuse_rough_rows(args, kwargs):
     if getattr(args, "app_place_new_mirror", False) or kwargs.get("new_mirror") is not None:
         raise ValueError("rough_times= cannot be combined with app_place_new_mirror or new_mirror= (the single mirror carries no "
                          "roughness; PlacedMirror.axis_aligned(..., roughness=) in new_mirrors= takes its keys)")
-    from .placed_objects import SINGLE_OBJECT_KEYWORDS
-    given = [k for k in SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
+    given = [k for k in placed_objects.SINGLE_OBJECT_KEYWORDS if kwargs.get(k) is not None]
     if given or (getattr(args, "app_reflect_newly_placed_objects", False) and kwargs.get("placed_objects") is None):
         raise ValueError("rough_times= is combined with objects through placed_objects=[PlacedObject(...), ...], not with the "
                          f"single-object keywords ({', '.join(k + '=' for k in given) or 'app_reflect_newly_placed_objects without placed_objects='})")
@@ -212,14 +107,11 @@ def _refuse_apps(args, models, kwargs):
         raise ValueError(f"scene_roughness={kwargs['scene_roughness']!r} is read by the per-mirror roughness route alone: pass "
                          "rough_times=T (the number of jittered reflections beside the first)")
     if kwargs.get("exclude_source_mirror", False) is not False or kwargs.get("source_mirror") is not None:
-        from .placed_mirrors import refuse_source     # allowed wherever new_mirrors= is; the tensor is looked at with the rays
-        refuse_source(kwargs)
+        placed_mirrors.refuse_source(kwargs)          # allowed wherever new_mirrors= is; the tensor is looked at with the rays
     if multi:                                         # its own refusals; what it is allowed beside keeps its own, below
-        from .placed_mirrors import refuse as refuse_mirrors
-        refuse_mirrors(args, models, kwargs)
+        placed_mirrors.refuse(args, models, kwargs)
     if kwargs.get("placed_objects") is not None:      # the list carries the kinds: args.obj_model_type is not consulted
-        from .placed_objects import refuse
-        return refuse(args, models, kwargs)
+        return placed_objects.refuse(args, models, kwargs)
     if getattr(args, "app_reflect_newly_placed_objects", False):
         obj_type = getattr(args, "obj_model_type", "d_nerf")                   # eval.py:108: the reference's default
         if obj_type == "d_nerf":
@@ -266,54 +158,6 @@ def _refuse_apps(args, models, kwargs):
         raise ValueError("app_place_new_mirror needs args.near: the foreground test compares the depth with it (eval.py:169-171)")
 
 
-def _place_mirror(r, rays_chunk, sel, plane, near, flag):
-    """eval.py:364-504 on one level's maps, in place (mnrf_place_mirror); `flag` (device int32) is OR-ed with "any mirror
-    after the merge".  The returned mirror mask becomes the merged bool tensor (eval.py:492-496), and depth_fine the edited
-    depth (eval.py:497-500)."""
-    N = rays_chunk.shape[0]
-    for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
-        if k in r and not r[k].is_contiguous():
-            r[k] = r[k].contiguous()
-    mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
-    mask, depth, normal = r[mkey], r[f"depth_{sel}"], _pick_normal(r, sel)
-    merged = torch.empty(N, dtype=torch.bool, device=rays_chunk.device)
-    p = _lib.ptr
-    nx, ny, nz = plane["normal"]
-    u0, u1, w0, w1 = plane["rect"]
-    _lib.check(_lib.lib().mnrf_place_mirror(
-        p(rays_chunk), N, _lib.MNRF_PLANE_Y if plane["axis"] == "y" else _lib.MNRF_PLANE_X, plane["position"], nx, ny, nz, u0, u1, w0, w1, float(near),
-        p(depth), p(mask), p(normal), p(r[f"x_surface_{sel}"]), ctypes.c_void_p(merged.data_ptr()), p(flag), _lib.stream()),
-        "mnrf_place_mirror")
-    r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
-    if "depth_fine" in r:
-        r["depth_fine"] = depth
-    elif "depth_coarse" in r:
-        r["depth_coarse"] = depth
-    return mask
-
-
-def _place_mirrors(r, rays_chunk, sel, packed, near, flag, index, source=None, exclude=False):
-    """The K-mirror rule on one level's maps, in place (placed_mirrors.py, mnrf_place_mirrors): _place_mirror's edits of the
-    result dict for the mirrors `packed` (placed_mirrors.pack); index: (N,) int32 that receives the mirror each ray took, or
-    None.  exclude: mnrf_place_mirrors_from with the level's `source` ((N,) int32: the placed mirror each ray left at the level
-    above, which it cannot hit; None: no ray has one)."""
-    from .placed_mirrors import _place_mirrors as place_mirrors
-    N = rays_chunk.shape[0]
-    for k in (f"depth_{sel}", f"x_surface_{sel}", f"surface_normal_{sel}", f"surface_normal_grad_{sel}"):
-        if k in r and not r[k].is_contiguous():
-            r[k] = r[k].contiguous()
-    mkey = next(k for k in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if k in r)
-    mask, depth, normal = r[mkey], r[f"depth_{sel}"], _pick_normal(r, sel)
-    merged = torch.empty(N, dtype=torch.bool, device=rays_chunk.device)
-    place_mirrors(rays_chunk, packed, near, depth, mask, normal, r[f"x_surface_{sel}"], merged, flag, index, source, exclude)
-    r["mirror_mask_fine" if "mirror_mask_fine" in r else "mirror_mask_coarse"] = merged
-    if "depth_fine" in r:
-        r["depth_fine"] = depth
-    elif "depth_coarse" in r:
-        r["depth_coarse"] = depth
-    return mask
-
-
 def _transform_rays(sec, xform):
     """eval.py:551-594 in place on the (M,8) secondary rays (mnrf_transform_rays)."""
     rot = xform["rotation"]
@@ -321,110 +165,6 @@ def _transform_rays(sec, xform):
     tx, ty, tz = xform["translation"]
     _lib.check(_lib.lib().mnrf_transform_rays(_lib.ptr(sec), sec.shape[0], rot, float(xform["scale"]), tx, ty, tz, _lib.stream()),
                "mnrf_transform_rays")
-
-
-def _merge_object(r, rays_chunk, xform, near, n_used, render, bounds=None):
-    """eval.py:173-291 on one level's maps, in place: the level's rays moved into the object's frame (mnrf_object_rays), the
-    object field rendered for colour, depth and opacity (`render`: rays -> dict), and its maps merged where the object is
-    opaque and not hidden by the scene (mnrf_object_merge).  The mirror flag is cleared there BEFORE the caller's hard clip,
-    as in the reference; x_surface and the normals are not edited (the reference does not edit them either).
-
-    bounds (an ObjectBounds): only the rays whose object-frame segment can touch a set cell are rendered -- mnrf_object_cull
-    compacts them in order, ONE 4-byte device->host read says how many there are, `render` runs on those rows (not at all when
-    there are none) and mnrf_object_merge_indexed applies the same per-ray rule through their index.  The other rays stay as
-    the scene rendered them."""
-    N = rays_chunk.shape[0]
-    if N == 0:
-        return
-    p = _lib.ptr
-    if bounds is not None:
-        obj_rays, index, count = bounds._cull(rays_chunk, xform)
-        M = int(count.item())
-        if M == 0:
-            return
-        o = render(obj_rays[:M])
-        for k in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
-            if k in r and not r[k].is_contiguous():
-                r[k] = r[k].contiguous()
-        _lib.check(_lib.lib().mnrf_object_merge_indexed(
-            p(o["rgb_fine"].contiguous()), p(o["depth_fine"].contiguous()), p(o["opacity_fine"].contiguous()), p(index), p(count), M,
-            xform["scale"], xform["pose_scale0"], float(near), p(r["rgb_fine"]), p(r["depth_fine"]), p(r.get("mirror_mask_fine")),
-            p(n_used), _lib.stream()), "mnrf_object_merge_indexed")
-        return
-    obj_rays = torch.empty_like(rays_chunk)
-    pose = (ctypes.c_float * 12)(*xform["pose"]) if xform["pose"] is not None else None
-    tx, ty, tz = xform["translation"]
-    _lib.check(_lib.lib().mnrf_object_rays(p(rays_chunk), N, pose, xform["scale"], tx, ty, tz, p(obj_rays), _lib.stream()),
-               "mnrf_object_rays")
-    o = render(obj_rays)
-    for k in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
-        if k in r and not r[k].is_contiguous():
-            r[k] = r[k].contiguous()
-    _lib.check(_lib.lib().mnrf_object_merge(
-        p(o["rgb_fine"].contiguous()), p(o["depth_fine"].contiguous()), p(o["opacity_fine"].contiguous()), N, xform["scale"],
-        xform["pose_scale0"], float(near), p(r["rgb_fine"]), p(r["depth_fine"]), p(r.get("mirror_mask_fine")), p(n_used),
-        _lib.stream()), "mnrf_object_merge")
-
-
-def resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, device):
-    """The `object_bounds=` keyword of batched_inference -> an ObjectBounds on `device`, or None.  "auto" estimates them from
-    the object's own density inside object_region=(lo, hi) at object_bounds_res (default 64) cells per axis
-    (object_bounds.estimate_object_bounds): once for a nerf_pl object, kept on system_obj; per call, at frame_time, for a
-    D-NeRF object, which moves."""
-    from .object_bounds import ObjectBounds, estimate_object_bounds
-    bounds = kwargs.get("object_bounds")
-    if bounds is None:
-        if kwargs.get("object_region") is not None:
-            raise ValueError("object_region= is the region object_bounds='auto' looks for the object in: pass object_bounds='auto'")
-        return None
-    if not objects:
-        raise ValueError("object_bounds= bounds the object of app_reflect_newly_placed_objects: the application is not on")
-    if isinstance(bounds, ObjectBounds):
-        return bounds.to(device)
-    if not (isinstance(bounds, str) and bounds == "auto"):
-        raise ValueError(f"object_bounds must be None, an ObjectBounds or 'auto', not {bounds!r}")
-    region = kwargs.get("object_region")
-    if region is None or len(region) != 2:
-        raise ValueError("object_bounds='auto' needs object_region=(lo, hi): the box of the object's frame to look for it in")
-    res = kwargs.get("object_bounds_res", 64)
-    lo, hi = (tuple(float(v) for v in c) for c in region)
-    if obj_dnerf is not None:
-        return estimate_object_bounds(obj_dnerf, lo, hi, res=res, frame_time=frame_time).to(device)
-    system_obj = kwargs["system_obj"]
-    key = (lo, hi, res, str(device))
-    cached = getattr(system_obj, "_mnrf_object_bounds", None)
-    if cached is None or cached[0] != key:
-        cached = (key, estimate_object_bounds(system_obj, lo, hi, res=res).to(device))
-        try:
-            system_obj._mnrf_object_bounds = cached
-        except AttributeError:      # (an object without a __dict__: estimated per call)
-            pass
-    return cached[1]
-
-
-def _merge_objects(r, rays_chunk, placed, near, n_used, renderers):
-    """The K-object rule on one level's maps, in place (placed_objects.py): for k = 0 .. K-1 in list order, _merge_object's
-    per-ray rule of object k on the ray's current maps.  ONE mnrf_objects_cull moves and culls the level's rays for every
-    object, ONE device->host read brings the K counts, every object with a non-zero count is rendered on its kept rows
-    (renderers[k]: rays -> dict; queued back to back, no read in between), ONE mnrf_objects_merge applies the chain.  placed:
-    the resolved objects (PlacedObject.resolve); n_used: (K,) int32 on the device or None."""
-    from .placed_objects import _cull_objects as cull_objects, _merge_objects as merge_objects
-    N = rays_chunk.shape[0]
-    if N == 0:
-        return
-    obj_rays, _, slot, counts = cull_objects(rays_chunk, placed)
-    host = counts.tolist()                                    # the one read of this chunk and level
-    maps = [None] * len(placed)
-    for k, M in enumerate(host):
-        if M > 0:
-            o = renderers[k](obj_rays[k, :M])
-            maps[k] = (o["rgb_fine"], o["depth_fine"], o["opacity_fine"])
-    if not any(m is not None for m in maps):
-        return
-    for key in ("rgb_fine", "depth_fine", "mirror_mask_fine"):
-        if key in r and not r[key].is_contiguous():
-            r[key] = r[key].contiguous()
-    merge_objects(maps, placed, slot, counts, N, near, r["rgb_fine"], r["depth_fine"], r.get("mirror_mask_fine"), n_used)
 
 
 def _f(dev, *s):
@@ -785,7 +525,6 @@ class NeRFSystem(nn.Module):
 
     def forward(self, rays, extra=dict()):
         out = self._forward(rays, extra)
-        from .mirror_nerf import check_guard, release_transient
         # (training.train_step passes _guard=False: it reads the sticky flag once, after the backward, for both passes)
         if rays.shape[0] and extra.get("_guard", True) and check_guard(self):   # out of range: the models are on fp32 now
             try:
@@ -837,6 +576,381 @@ def _pinned(key, rows, tail, dtype):
     return buf
 
 
+def _resolve_call(models, rays, N_samples, N_importance, use_disp, chunk, kwargs):
+    """One call of batched_inference, refused or resolved: a plain namespace that the stages below read.  Written after it is
+    made: embeddings (batched_inference hands it on), noise_iter (_run_chunks starts it afresh per pass, _draw advances it) and
+    the entries of mirror_fraction (the per-model evidence of _MIRROR_FRACTION).  _refuse_apps runs first; then every keyword is
+    read once, here.  A single object (the single-object keywords) becomes a list of one record of the kind
+    PlacedObject.resolve returns, rendered through the single-object launches (object_chain)."""
+    args = kwargs.get("args")
+    if isinstance(args, dict):
+        args = SimpleNamespace(**args)
+    _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
+    rays = _lib.f32_in(rays)             # once per call: every launch of every level reads the chunk as (N,8) float32 rows
+    c = SimpleNamespace(models=models, rays=rays, N_samples=N_samples, N_importance=N_importance, use_disp=use_disp, chunk=chunk,
+                        args=args)
+    c.exclude, c.source_all = placed_mirrors.resolve_source(kwargs, rays)      # exclude_source_mirror=, source_mirror= (DESIGN 4.5c)
+    c.objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
+    listed, frame_time = kwargs.get("placed_objects"), kwargs.get("frame_time")
+    # used: what the merges add into, element k for object k -- object_used itself for a single object; a list counts in a tensor
+    # of its own, and used_out is then the caller's object_used, filled at the end of the call
+    object_used = kwargs.get("object_used") if c.objects else None
+    c.used, c.used_out = object_used, None
+    c.placed, c.object_chain = None, bool(kwargs.get("_object_chain", False))
+    if listed is None:                                                         # the single-object keywords, or no object at all
+        kind = None if not c.objects else "d_nerf" if getattr(args, "obj_model_type", "d_nerf") == "d_nerf" else "nerf_pl"
+        xform = resolve_new_object(args, kwargs.get("new_object")) if c.objects else None
+        field = kwargs.get("render_kwargs_test_d_nerf" if kind == "d_nerf" else "system_obj") if c.objects else None
+        time = float(frame_time) if kind == "d_nerf" else None
+        bounds = resolve_object_bounds(kwargs.get("object_bounds"), kwargs.get("object_region"), kwargs.get("object_bounds_res", 64),
+                                       kind, field, time, rays.device)
+        if c.objects:
+            c.placed, c.object_chain = [dict(kind=kind, field=field, xform=xform, bounds=bounds, time=time)], True
+    else:
+        c.placed = [o.resolve(args, None if frame_time is None else float(frame_time), rays.device) for o in listed]
+        if object_used is not None:
+            if object_used.numel() not in (1, len(c.placed)):
+                raise ValueError(f"object_used holds {len(c.placed)} elements (one per placed object) or 1 (their total), not {object_used.numel()}")
+            c.used, c.used_out = torch.empty(len(c.placed), dtype=torch.int32, device=rays.device), object_used
+    if object_used is not None and object_used.dtype != torch.int32:      # the merge kernels add into it: a tensor the call writes is never converted
+        raise ValueError(f"object_used must be an int32 tensor, not {object_used.dtype}")
+    c.place, c.subst = bool(getattr(args, "app_place_new_mirror", False)), bool(getattr(args, "app_reflection_substitution", False))
+    c.plane = resolve_new_mirror(args, kwargs.get("new_mirror")) if c.place else None
+    mirrors = kwargs.get("new_mirrors")                                    # several mirrors on any plane (placed_mirrors.py)
+    c.multi = mirrors is not None
+    c.mirrors_packed = placed_mirrors.pack(mirrors) if c.multi else None
+    c.xform = resolve_substitution(args) if c.subst else None
+    c.system_sub = kwargs.get("system_substitution") if c.subst else None
+    c.trace_flag = kwargs.get("trace_secondary_rays", False)
+    c.test_time = kwargs.get("test_time", True)
+    c.white_back = kwargs.get("white_back", False)
+    c.noise_std = kwargs.get("normal_noise_std", 0)
+    # injected draws are kept as a list so that a second pass after a range-guard trip replays the SAME draws
+    draws = kwargs.get("_normal_noise")
+    c.draws = None if draws is None else list(draws)
+    c.to_cpu = kwargs.get("to_cpu", True)
+    # per-ray maps only (the per-sample tensors are neither copied nor, in the final pass, produced at all: render_rays
+    # `_maps_only`): what to_cpu="maps" returns anyway; with to_cpu=False it is opt-in (maps_only=True), the full dict stays
+    # the default contract
+    c.maps_only = bool(kwargs.get("maps_only", c.to_cpu == "maps"))
+    c.rough = getattr(args, "app_control_mirror_roughness", False)
+    # a roughness per mirror (DESIGN 4.4c): its own keywords, its own branch of _stage_b; it takes every exclusion `rough` takes
+    c.rough_times, c.scene_roughness = resolve_rough_rows(kwargs)
+    c.rough_rows = c.rough_times is not None
+    c.rough_row = placed_mirrors.roughness_row(mirrors) if c.rough_rows else None
+    c.jitters_possible = c.rough_rows and (c.scene_roughness > 0 or any(v > 0 for v in c.rough_row[1][:c.rough_row[0]]))  # else J is empty, known here
+    c.batch_jitter = kwargs.get("batch_jitter", c.draws is None)   # see _add_jitters
+    c.one_field = getattr(args, "only_one_field", False)
+    c.fine_epoch = getattr(args, "only_one_field_fine_epoch", 2)
+    c.sel = "fine" if (N_importance > 0 and not c.one_field) else "coarse"
+    c.blend_mode = kwargs.get("blended_level", "auto")      # True / False / "auto": see _stage_a
+    if c.blend_mode not in (True, False, "auto"):
+        raise ValueError(f"blended_level must be True, False or 'auto', not {c.blend_mode!r}")
+    c.mirror_fraction = _MIRROR_FRACTION.setdefault(models.get(c.sel, models["coarse"]), {})      # level -> share of mirror rays in the chunk last counted
+    # what several conditions of the stages ask, formed once
+    c.jitters = bool(c.rough or c.rough_rows)                      # a roughness rule: further draws and renders per level
+    c.implies_trace = bool(c.trace_flag or c.place or c.multi)     # a placed mirror makes every level below the last trace
+    c.edits_level = bool(c.place or c.subst or c.objects or c.multi)      # an application reads or edits more of a level than the blend does
+    c.renderers = [_renderer(c, o) for o in c.placed] if c.placed is not None else None
+    # the models whose range guard the call reads (a D-NeRF object runs fp32 only: no guard)
+    c.guarded = list(models.values()) + (list(c.system_sub.models.values()) if c.system_sub is not None else [])
+    for o in c.placed or ():
+        if o["kind"] == "nerf_pl":
+            c.guarded += [m for m in _object_system(o["field"])[0].values() if not any(m is g for g in c.guarded)]
+    return c
+
+
+def _draw(c, n, dev):
+    if c.noise_iter is not None:
+        return next(c.noise_iter).to(dev).float().contiguous()
+    return torch.randn(n, 3, device=dev)
+
+
+def _render_field(c, obj_rays, dnerf, time, field_models, field_embeddings):
+    if dnerf is not None:
+        # eval.py:233-259: the time in column 8, the normalised directions behind it (a plain division); near and far are
+        # the rays' own columns 6 and 7; samples, background and models come from the OBJECT's configuration
+        d = obj_rays[:, 3:6]
+        batch = torch.cat([obj_rays, torch.full_like(obj_rays[:, :1], time), d / torch.norm(d, dim=-1, keepdim=True)], -1)
+        o = render_rays_dnerf(batch, **dict(dnerf, _frame_time=time))
+        return {"rgb_fine": o["rgb_map"], "depth_fine": o["depth_map"], "opacity_fine": o["acc_map"]}
+    # eval.py:221-232: only colour, depth and opacity of this render are read -- the maps-only path
+    return render_rays(field_models, field_embeddings, obj_rays, c.N_samples, c.use_disp, 0, 0, c.N_importance, c.chunk, c.white_back,
+                       test_time=True, compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
+
+
+def _renderer(c, o):
+    """rays -> the maps of the resolved object o (a record of c.placed) along them."""
+    if o["kind"] == "d_nerf":
+        return lambda obj_rays: _render_field(c, obj_rays, o["field"], o["time"], None, None)
+    field_models, field_embeddings = _object_system(o["field"])
+    return lambda obj_rays: _render_field(c, obj_rays, None, None, field_models, field_embeddings)
+
+
+def _stage_a(c, rays_chunk, level, host=None, slot=0, source=None):
+    """The primary pass of one chunk at one level, the objects and the placed mirrors merged into its maps, its mirror mask
+    thresholded.  host: the pinned (flags, counts) of a pipelined pass (_run_chunks) -- the flag is then not waited for here."""
+    args, sel = c.args, c.sel
+    # The last level of a recursion traces nothing: its caller (_stage_b of the level above) reads rgb_* and depth_* of it
+    # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
+    # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
+    rgb_depth = 1 <= level == args.max_recursive_level and not c.jitters
+    # A level that traces has its colour replaced by m * reflected + (1 - m) * colour in _stage_b, m = 1 wherever the
+    # composited mirror value is not below 0.5 (the threshold, then `!= 0`): the colour of such a ray reaches nothing --
+    # no other key of the result carries it -- so the final pass may leave it out and write 0 (render_rays
+    # `_blended_level`, mnrf_field_composite_fused MNRF_FUSED_BLENDED_LEVEL; 0 * colour and 0 * 0 are the same +0).  A chunk
+    # whose "any mirror" flag comes back false is returned unblended -- and then holds no ray above the threshold, so no
+    # row of it was left out.  Not with roughness jitters, a placed mirror, reflection substitution or placed objects:
+    # those read or edit more of the level than the blend does.  (render_rays falls back to the launches of before when
+    # the pass is not one the fused kernel covers: fp32 arithmetic, another sample count, density-gradient normals.)
+    # Both routes give the same result, so the choice is one of speed alone, and it is made PER CHUNK from evidence: a chunk
+    # with no ray above the threshold is about 3 % slower through the ray-fused form than through the two-kernel path, one
+    # with every ray above it 5 % faster, and the two meet at BLENDED_BREAK_EVEN.  The evidence is the share of rays above
+    # the threshold in the chunk of this level whose count was last known (neighbouring chunks of a frame, and the same
+    # chunks of the frame before, see much the same scene); it is kept per model across calls (_MIRROR_FRACTION).  Without
+    # evidence -- the first chunk ever rendered with a model -- the launches of before are used, so a scene with few mirror
+    # pixels never takes the slower route for more than the chunks it takes to notice a change.
+    # `blended_level=True` / `False` forces the choice (tests, measurements).
+    can_blend = bool(level < args.max_recursive_level and c.trace_flag and c.test_time and c.blend_mode is not False
+                     and not (c.jitters or c.edits_level))
+    evidence = c.mirror_fraction.get(level)
+    blended = can_blend and (c.blend_mode is True or (evidence is not None and evidence >= BLENDED_BREAK_EVEN))
+    count_it = can_blend and c.blend_mode is not True
+    r = render_rays(c.models, c.embeddings, rays_chunk, c.N_samples, c.use_disp, 0, 0, c.N_importance, c.chunk,
+                    c.white_back, test_time=c.test_time,
+                    compute_normal=c.trace_flag and (not args.predict_normal),
+                    only_one_field=c.one_field, only_one_field_fine_epoch=c.fine_epoch,
+                    current_epoch=c.fine_epoch + 1, _guard=False, _maps_only=c.maps_only or rgb_depth,
+                    _rgb_depth_only=rgb_depth, _blended_level=blended)
+    r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
+    r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
+    if c.placed is not None and not c.object_chain:                   # the K-object rule, ahead of the hard clip
+        placed_objects._merge_placed(r, rays_chunk, c.placed, args.near, c.used, c.renderers)
+    elif c.placed is not None:              # eval.py:173-291, ahead of the hard clip: the single-object launches, object after object
+        for k, o in enumerate(c.placed):
+            placed_objects._merge_object(r, rays_chunk, o["xform"], args.near, None if c.used is None else c.used.view(-1)[k:k + 1],
+                                         c.renderers[k], o["bounds"])
+    mask = next((r[key] for key in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse") if key in r), None)
+    # in place (eval.py:303-307); at the last level nothing branches on "any mirror pixel": no host read, so the next
+    # chunk's launches queue behind this pass without a stream sync.  A new mirror (eval.py:311-320) makes every level
+    # below the last one trace; it is merged into the mask right behind the threshold, and its flag is the one read.
+    last = level >= args.max_recursive_level or not c.implies_trace
+    edit = None
+    if c.place and not last:
+        edit = lambda flag: placed_mirrors._place_mirror_level(r, rays_chunk, sel, c.plane, args.near, flag)  # noqa: E731
+    # (with a roughness per mirror every level that places mirrors keeps its index: the std of a ray follows the mirror it
+    # took at THAT level; only level 0's is returned.  exclude_source_mirror keeps it too: it is the next level's `source`)
+    if c.multi and (level == 0 or ((c.rough_rows or c.exclude) and not last)):      # the mirror each ray took; -1 where the list is not applied
+        r["new_mirror_index"] = torch.full((rays_chunk.shape[0],), -1, dtype=torch.int32, device=rays_chunk.device)
+    if c.multi and not last:
+        edit = lambda flag: placed_mirrors._place_mirrors_level(r, rays_chunk, sel, c.mirrors_packed, args.near, flag,  # noqa: E731
+                                                                r.get("new_mirror_index"), source, c.exclude)
+    pending, any_mirror, counted = None, False, None
+    if mask is not None:
+        if host is not None and not last and rays_chunk.shape[0]:
+            pending = _threshold_async(mask, host[0], slot, edit)
+            if count_it:      # the count follows the flag to pinned memory; _stage_b reads it behind its own event
+                host_count = host[1][slot:slot + 1]
+                host_count.copy_(torch.count_nonzero(mask).view(1), non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                counted = (host_count, ev)
+        else:
+            any_mirror = _threshold_(mask, want_any=not last, edit=edit)
+            if count_it and rays_chunk.shape[0]:
+                c.mirror_fraction[level] = (int(torch.count_nonzero(mask).item()) if any_mirror else 0) / rays_chunk.shape[0]
+    return r, rays_chunk, level, mask, any_mirror, pending, counted
+
+
+def _recurse(c, rays_chunk, level, source=None):
+    return _stage_b(c, _stage_a(c, rays_chunk, level, source=source))
+
+
+def _sources(c, r, index, m, n_rep=1):
+    # the `source` of the rays reflected off this level (mnrf_mirror_sources): the mirror each took here, through the compaction
+    return placed_mirrors.mirror_sources(r.get("new_mirror_index"), index, m, n_rep, r[f"rgb_{c.sel}"].device) if c.exclude else None
+
+
+def _add_jitters(c, r, r2, rays_chunk, level, jit_index, row_map, fan, one, times):
+    """`times` further samples added to rows of R = r2's colours, and the finish: both roughness rules end a level with it.
+    jit_index: (mj,) int32, the compaction of the jitter set among the level's rays; row_map: the row of R that jittered ray p
+    adds into (None: p itself); fan(noise (n, N, 3)) -> the (n * mj, 8) secondary rays of a group of n draws; one(draw (N, 3))
+    -> the (mj, 8) rays of one draw (batch_jitter=False); `source` rows are handed on wherever the call keeps them (_sources).
+
+    The reference renders the jittered reflections one after the other (run.sh:187: 64 of them, each a full secondary render).
+    Rays are independent, so groups of them go through ONE recursion call and the colours are added in the reference's order.
+    Groups are sized to JITTER_RAYS rays (~2.5 GB of per-sample tensors at 64+128 samples); a group is one buffer of draws (one
+    (N,3) draw per jitter, in the reference's order), one fan launch, one recursion call and one mnrf_jitter_mean per colour
+    key.  Not the default when a test injects the draws: their order interleaves with the nested levels' draws."""
+    N, dev, mj = rays_chunk.shape[0], rays_chunk.device, jit_index.shape[0]
+    keys = [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]
+    for k in keys:
+        r2[k] = r2[k].contiguous()
+    finish = float(np.float32(1) / np.float32(times + 1))   # torch's `/ (times + 1)` on the device: see ROUGH_FINISH
+    g = 0
+    while g < times:
+        if c.batch_jitter:
+            n_g = max(1, min(times - g, JITTER_RAYS // max(1, mj)))
+            noise = torch.stack([_draw(c, N, dev) for _ in range(n_g)]) if c.noise_iter is not None \
+                else torch.randn(n_g, N, 3, device=dev)
+            s2 = fan(noise)
+        else:
+            n_g, s2 = 1, one(_draw(c, N, dev)).contiguous()
+        r3 = _recurse(c, s2, level + 1, _sources(c, r, jit_index, mj, n_g))
+        g += n_g
+        for k in keys:
+            _jitter_mean(r2[k], r3[k], row_map, mj, n_g, finish if g >= times else None)
+
+
+def _stage_b(c, state):
+    """The reflected pass of one chunk at one level: what _stage_a left is traced, where it holds a mirror ray, and blended."""
+    r, rays_chunk, level, mask, any_mirror, pending, counted = state
+    args, sel = c.args, c.sel
+    if pending is not None:
+        any_mirror = _flag_ready(pending)
+    if counted is not None:
+        counted[1].synchronize()
+        c.mirror_fraction[level] = int(counted[0].item()) / rays_chunk.shape[0]
+    N, dev = rays_chunk.shape[0], rays_chunk.device
+    only_in = not (level < 1)                                         # eval.py:159
+    trace = bool(mask is not None and any_mirror and c.implies_trace and level < args.max_recursive_level)     # eval.py:311-320, 503-504
+    if not trace or N == 0:
+        return r
+    # `mirror_mask = mirror_mask.bool()` then `.float()` (eval.py:307, 689): an exact 0.5 blends as 1
+    mask = (mask != 0).float()
+    normal, x_surface = _pick_normal(r, sel), r[f"x_surface_{sel}"]
+    nn0 = _draw(c, N, dev) if c.jitters else None                     # eval.py:506-511
+    first_normal, first_std = normal, c.noise_std
+    if c.rough_rows:
+        # THE RULE of include/mnrf.h "A roughness per mirror" (DESIGN 4.4c): the std of a ray follows the mirror it took at
+        # this level.  The first reflection is the existing launch on normals that carry draw_0 * std already (no addition
+        # where the std is 0: the bits of the frame without roughness); with every std 0 there is nothing to add at all.
+        if c.jitters_possible:
+            std_rows, jitter_mask = _rough_rows(r.get("new_mirror_index"), mask, c.rough_row, c.scene_roughness)
+            first_normal = _perturb_normals(normal, nn0, std_rows)
+        nn0, first_std = None, 0.0                                    # (the draw is made either way: the order of draws)
+    sec, index, rdir = _reflect(rays_chunk, x_surface, first_normal, mask, only_in, nn0, first_std)
+    r["reflect_direction"] = rdir
+    if sec.shape[0] == 0:
+        return r
+    if c.subst:                                                       # eval.py:550-613: no recursion below
+        _transform_rays(sec, c.xform)
+        # only rgb / depth of this render are read (eval.py:676-697): the maps-only path, without the density-gradient
+        # normals the reference also computes for it
+        r2 = render_rays(c.system_sub.models, c.system_sub.embeddings, sec.contiguous(), c.N_samples, c.use_disp, 0, 0,
+                         c.N_importance, c.chunk, c.white_back, test_time=c.test_time, compute_normal=False,
+                         only_one_field=c.one_field, only_one_field_fine_epoch=c.fine_epoch,
+                         current_epoch=c.fine_epoch + 1, _guard=False, _maps_only=True, _rgb_depth_only=True)
+    else:
+        r2 = _recurse(c, sec.contiguous(), level + 1, _sources(c, r, index, sec.shape[0]))
+    if c.rough and args.trace_ray_times > 0:                          # eval.py:622-674
+        # THE RULE of include/mnrf.h "Mirror roughness" (DESIGN 4.4b).  The reference adds the (M,3) colours of each
+        # jittered render, M = sum(mask), to the first secondary render, which at level 0 has N rows: that works only
+        # where every ray of the chunk is a mirror ray (SURVEY a14).  Here the sums go through the compaction's index,
+        # so a mirror ray gets the mean of its times + 1 samples and a ray of level 0 that is no mirror ray keeps the
+        # one sample it has; where M == N it is the reference's arithmetic.
+        # The ONE compaction of the level's mask, and the one host read of its count: every jitter compacts through
+        # the same mask.  At levels >= 1 the first _reflect above made both; at level 0, which reflects every
+        # ray, mnrf_reflect_compact runs once more with compact = 1 for its index alone
+        jit_index = index if only_in else _reflect(rays_chunk, x_surface, normal, mask, True, want_dir=False)[1]
+        _add_jitters(c, r, r2, rays_chunk, level, jit_index, None if only_in else jit_index,      # row of R: p at levels >= 1, index[p] at level 0
+                     lambda noise: _reflect_fan(rays_chunk, x_surface, normal, noise, c.noise_std, jit_index),
+                     lambda draw: _reflect(rays_chunk, x_surface, normal, mask, True, draw, c.noise_std, want_dir=False)[0],
+                     args.trace_ray_times)
+    elif c.rough:
+        for k in [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]:
+            r2[k] = r2[k] / (args.trace_ray_times + 1)
+    elif c.rough_rows and c.jitters_possible:
+        # The branch above with J = {mask != 0 and std > 0} in the mask's place: ONE compaction of J and the read of its
+        # count (the second and last of the level), the fan with the std per ray, the same groups, sums and finish.  A
+        # mirror ray outside J keeps its one sample; an empty J takes no further draw.  One by one a jitter is
+        # mnrf_perturb_normals, then mnrf_reflect_compact on J's mask.
+        jit_index = _reflect(rays_chunk, x_surface, normal, jitter_mask, True, want_dir=False)[1]
+        if jit_index.shape[0] > 0:
+            row_map = jit_index
+            if only_in:       # row of R: the ray's rank in the mask's compaction, from the two indices, on the device
+                rank = torch.empty(N, dtype=torch.int32, device=dev)
+                rank[index.long()] = torch.arange(index.shape[0], dtype=torch.int32, device=dev)
+                row_map = rank[jit_index.long()]
+            _add_jitters(c, r, r2, rays_chunk, level, jit_index, row_map,
+                         lambda noise: _reflect_fan_rows(rays_chunk, x_surface, normal, noise, std_rows, jit_index),
+                         lambda draw: _reflect(rays_chunk, x_surface, _perturb_normals(normal, draw, std_rows), jitter_mask, True,
+                                               want_dir=False)[0],
+                         c.rough_times)
+    r[f"rgb_{sel}"], refl = _blend(r[f"rgb_{sel}"], r2[f"rgb_{sel}"], index, mask, True)
+    r[f"rgb_{sel}_reflect"] = refl
+    if only_in:
+        d = torch.zeros_like(r[f"depth_{sel}"])
+        d[index.long()] = r2[f"depth_{sel}"]
+        r[f"depth_{sel}_reflect"] = d
+    else:
+        r[f"depth_{sel}_reflect"] = r2[f"depth_{sel}"]
+    return r
+
+
+def _collect(c, out, results, staging):
+    """One chunk's result into `results` (key -> list of pieces).  staging (to_cpu="maps" on the GPU, else None): the per-ray
+    maps of the chunk travel to PINNED staging buffers on a side stream while the next chunk renders (pageable destinations
+    made every copy synchronous: 33 ms per 51 MB frame)."""
+    if staging is not None:
+        done = torch.cuda.Event()
+        done.record()
+        staging.stream.wait_event(done)
+    maps = c.to_cpu == "maps" or c.maps_only                           # per-ray maps only
+    for k, v in out.items():
+        if maps and not (v.dim() <= 2 and (v.dim() == 1 or v.shape[1] <= 3)):
+            continue
+        if staging is None:
+            results[k] += [v.to("cpu", non_blocking=True) if c.to_cpu == "maps" else (v.cpu() if c.to_cpu else v)]
+            continue
+        buf = staging.buffers.get(k)
+        if buf is None:
+            buf = staging.buffers[k] = _pinned(k, c.rays.shape[0], tuple(v.shape[1:]), v.dtype)
+        r0 = staging.rows[k]
+        with torch.cuda.stream(staging.stream):
+            buf[r0:r0 + v.shape[0]].copy_(v, non_blocking=True)
+        staging.rows[k] = r0 + v.shape[0]
+        staging.hold.append(v)      # (alive until the copies have run)
+
+
+def _run_chunks(c):
+    """One pass over the chunks of the call -> key -> list of pieces.  A pass starts its own counts of object_used, its own
+    iterator over injected draws and its own staging state, so a second pass after a range-guard trip repeats the first.
+    Level 0 runs in two stages so that chunk k+1's primary pass can be queued BEFORE the host waits for chunk k's "any mirror
+    pixel" flag (eval.py:303-312 branches on it): the GPU then never idles on that read.  Not used with the roughness jitters,
+    whose random draws would change order against the primary passes.  MNRF_EVAL_PIPELINE (default on): the per-sample tensors
+    of TWO chunks are then alive at once (~2 x 3 KB/ray x chunk: 200 MB at chunk 32768) -- set it to 0 on a memory-tight
+    device.  With random roughness draws (no injection) a second pass draws afresh, as any re-render would."""
+    rays, chunk = c.rays, c.chunk
+    for counts in (c.used, c.used_out):
+        if counts is not None:
+            counts.zero_()
+    c.noise_iter = iter(c.draws) if c.draws is not None else None
+    results = defaultdict(list)
+    staging = SimpleNamespace(stream=_copy_stream(rays.device), buffers={}, rows=defaultdict(int), hold=[]) \
+        if c.to_cpu == "maps" and rays.is_cuda else None
+    starts = list(range(0, rays.shape[0], chunk))
+    pipelined = rays.is_cuda and not c.jitters and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
+    host = (torch.zeros(2, dtype=torch.int32).pin_memory(), torch.zeros(2, dtype=torch.int64).pin_memory()) if pipelined else None
+    source = lambda i: c.source_all[i:i + chunk] if c.source_all is not None else None  # noqa: E731
+    primary = lambda n_c: _stage_a(c, rays[starts[n_c]:starts[n_c] + chunk].contiguous(), 0, host, n_c % 2, source(starts[n_c]))  # noqa: E731
+    ahead = primary(0) if (pipelined and starts) else None
+    for n_c, i in enumerate(starts):
+        if pipelined:
+            state = ahead
+            ahead = primary(n_c + 1) if n_c + 1 < len(starts) else None
+            out = _stage_b(c, state)
+        else:
+            out = _recurse(c, rays[i:i + chunk].contiguous(), 0, source(i))
+        _collect(c, out, results, staging)
+    if staging is not None:       # one host-side copy out of the (re-used) staging buffers hands back tensors the caller owns
+        staging.stream.synchronize()
+        staging.hold.clear()
+        for k, buf in staging.buffers.items():
+            results[k] = [buf[:staging.rows[k]].clone()]
+    return results
+
+
 @torch.no_grad()
 def batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk, **kwargs):
     """eval.batched_inference.  kwargs: args (namespace/dict with predict_normal, only_one_field,
@@ -849,7 +963,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     recursion call each instead of one by one; default on unless draws are injected), blended_level (default "auto": a chunk
     of a level that traces renders its fine pass with the blended-level launch, which leaves out the colour of mirror rays,
     when the chunk last counted at that level held enough of them for it to pay -- same result either way; True / False force
-    the choice, see stage_a),
+    the choice, see _stage_a),
     _normal_noise (iterator of pre-drawn (n,3) standard-normal tensors, for tests).
 
     args.app_control_mirror_roughness with args.trace_ray_times and normal_noise_std= (eval.py:506-511, 622-674), on chunks with
@@ -899,7 +1013,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     of K single-object applications.  The merge writes depth = d, so the nearest opaque object wins; an exact tie in depth
     goes to the LATER object of the list; a current depth <= near hides nothing, as in the reference's own rule
     (eval.py:275-281).  x_surface and the normals are not edited.  One mnrf_objects_cull, one read of the K counts, the
-    renders of the objects with kept rays and one mnrf_objects_merge per chunk and level (_merge_objects).  object_used= is
+    renders of the objects with kept rays and one mnrf_objects_merge per chunk and level (_merge_placed).  object_used= is
     then a device int32 tensor of K elements -- element k: the number of rays, over all levels, that took object k when its
     turn came; a ray that a later, nearer object then takes counts for BOTH -- or of 1 element, which receives their sum.
     _object_chain=True (tests, measurements): the same list through K successive single-object passes (_merge_object), the
@@ -921,7 +1035,7 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     an ulp of that mirror's plane, on either side; without the keyword THE RULE finds the same mirror again at a distance of 1e-9
     to 1e-7 and reflects the ray a second time off it.  With it every ray of a level carries `source`, the index in the list of
     the placed mirror it was reflected off at the level directly above (-1: the scene's own mirror, no mirror, a ray of the call),
-    and mirror `source` is no hit: every level that applies the list keeps its index, stage_b makes the next level's row from it
+    and mirror `source` is no hit: every level that applies the list keeps its index, _stage_b makes the next level's row from it
     through the compaction (mnrf_mirror_sources: the plain reflection, the rough_times fan and its one-by-one form), and the
     launch is mnrf_place_mirrors_from.  Only the mirror left directly above is excluded: a ray may return to it after another
     bounce.  source_mirror= ((N,) int32 on the rays' device, default all -1; another dtype, shape or device is refused): the
@@ -946,385 +1060,16 @@ def batched_inference(models, embeddings, rays, N_samples, N_importance, use_dis
     args.trace_ray_times are not read; _normal_noise= and batch_jitter= work as with the flag.  Without rough_times a mirror
     with roughness > 0, or a scene_roughness > 0, is refused.  The route takes the exclusions of the flag: no pipelined
     stage, no blended level, no colour/depth-only last level."""
-    args = kwargs.get("args")
-    if isinstance(args, dict):
-        args = SimpleNamespace(**args)
-    _refuse_apps(args, models, dict(kwargs, _N_importance=N_importance))
-    rays = _lib.f32_in(rays)             # once per call: every launch of every level reads the chunk as (N,8) float32 rows
-    exclude, source_all = False, None                                      # exclude_source_mirror=, source_mirror= (DESIGN 4.5c)
-    if kwargs.get("exclude_source_mirror", False) or kwargs.get("source_mirror") is not None:
-        from .placed_mirrors import mirror_sources, resolve_source
-        exclude, source_all = resolve_source(kwargs, rays)
-    objects = bool(getattr(args, "app_reflect_newly_placed_objects", False))
-    placed = kwargs.get("placed_objects")
-    single = objects and placed is None                                    # the single-object keywords
-    obj_xform = resolve_new_object(args, kwargs.get("new_object")) if single else None
-    obj_dnerf = kwargs.get("render_kwargs_test_d_nerf") if single and getattr(args, "obj_model_type", "d_nerf") == "d_nerf" else None
-    obj_models, obj_embeddings = _object_system(kwargs["system_obj"]) if single and obj_dnerf is None else (None, None)
-    frame_time = float(kwargs["frame_time"]) if obj_dnerf is not None else None
-    obj_used = kwargs.get("object_used") if objects else None
-    obj_bounds = resolve_object_bounds(kwargs, objects, obj_dnerf, frame_time, rays.device) if placed is None else None
-    used_k, object_chain = None, bool(kwargs.get("_object_chain", False))
-    if placed is not None:
-        call_time = kwargs.get("frame_time")
-        placed = [o.resolve(args, None if call_time is None else float(call_time), rays.device) for o in placed]
-        if obj_used is not None:
-            if obj_used.numel() not in (1, len(placed)):
-                raise ValueError(f"object_used holds {len(placed)} elements (one per placed object) or 1 (their total), not {obj_used.numel()}")
-            used_k = torch.zeros(len(placed), dtype=torch.int32, device=rays.device)
-    if obj_used is not None:
-        if obj_used.dtype != torch.int32:      # the merge kernels add into it: a tensor the call writes is never converted
-            raise ValueError(f"object_used must be an int32 tensor, not {obj_used.dtype}")
-        obj_used.zero_()
-    place = bool(getattr(args, "app_place_new_mirror", False))
-    subst = bool(getattr(args, "app_reflection_substitution", False))
-    plane = resolve_new_mirror(args, kwargs.get("new_mirror")) if place else None
-    multi = kwargs.get("new_mirrors") is not None                          # several mirrors on any plane (placed_mirrors.py)
-    if multi:
-        from .placed_mirrors import pack
-        mirrors_packed = pack(kwargs["new_mirrors"])
-    xform = resolve_substitution(args) if subst else None
-    system_sub = kwargs.get("system_substitution") if subst else None
-    trace_flag = kwargs.get("trace_secondary_rays", False)
-    test_time = kwargs.get("test_time", True)
-    white_back = kwargs.get("white_back", False)
-    noise_std = kwargs.get("normal_noise_std", 0)
-    noise_iter = kwargs.get("_normal_noise")
-    if noise_iter is not None and not isinstance(noise_iter, (list, tuple)):
-        # injected draws are kept as a list in kwargs so that a range-guard retry (below) replays the SAME draws
-        kwargs = dict(kwargs, _normal_noise=list(noise_iter))
-        noise_iter = kwargs["_normal_noise"]
-    if noise_iter is not None:
-        noise_iter = iter(noise_iter)
-    to_cpu = kwargs.get("to_cpu", True)
-    # per-ray maps only (the per-sample tensors are neither copied nor, in the final pass, produced at all: render_rays
-    # `_maps_only`): what to_cpu="maps" returns anyway; with to_cpu=False it is opt-in (maps_only=True), the full dict stays
-    # the default contract
-    maps_only = bool(kwargs.get("maps_only", to_cpu == "maps"))
-    rough = getattr(args, "app_control_mirror_roughness", False)
-    # a roughness per mirror (DESIGN 4.4c): its own keywords, its own branch of stage_b; it takes every exclusion `rough` takes
-    rough_times, scene_roughness = resolve_rough_rows(kwargs)
-    rough_rows = rough_times is not None
-    if rough_rows:
-        from .placed_mirrors import roughness_row
-        rough_row = roughness_row(kwargs.get("new_mirrors"))
-        jitters_possible = scene_roughness > 0 or any(v > 0 for v in rough_row[1][:rough_row[0]])   # else J is empty, known here
-    batch_jitter = kwargs.get("batch_jitter", noise_iter is None)   # see the roughness branch of recurse()
-    one_field = getattr(args, "only_one_field", False)
-    fine_epoch = getattr(args, "only_one_field_fine_epoch", 2)
-    sel = "fine" if (N_importance > 0 and not one_field) else "coarse"
-    blend_mode = kwargs.get("blended_level", "auto")      # True / False / "auto": see stage_a
-    if blend_mode not in (True, False, "auto"):
-        raise ValueError(f"blended_level must be True, False or 'auto', not {blend_mode!r}")
-    mirror_fraction = _MIRROR_FRACTION.setdefault(models.get(sel, models["coarse"]), {})      # level -> share of mirror rays in the chunk last counted
-
-    def draw(n, dev):
-        if noise_iter is not None:
-            return next(noise_iter).to(dev).float().contiguous()
-        return torch.randn(n, 3, device=dev)
-
-    # Level 0 runs in two stages so that chunk k+1's primary pass can be queued BEFORE the host waits for chunk k's
-    # "any mirror pixel" flag (eval.py:303-312 branches on it): the GPU then never idles on that read.  Not used with the
-    # roughness jitters, whose random draws would change order against the primary passes.
-    def stage_a(rays_chunk, level, host_flags=None, slot=0, source=None):
-        # The last level of a recursion traces nothing: its caller (stage_b of the level above) reads rgb_* and depth_* of it
-        # and nothing else (eval.py:676-697), so its final pass runs ray-fused without the mirror head (render_rays
-        # `_rgb_depth_only`).  Not with the roughness jitters, whose groups add further keys of the render.
-        rgb_depth = 1 <= level == args.max_recursive_level and not (rough or rough_rows)
-        # A level that traces has its colour replaced by m * reflected + (1 - m) * colour in stage_b, m = 1 wherever the
-        # composited mirror value is not below 0.5 (the threshold, then `!= 0`): the colour of such a ray reaches nothing --
-        # no other key of the result carries it -- so the final pass may leave it out and write 0 (render_rays
-        # `_blended_level`, mnrf_field_composite_fused MNRF_FUSED_BLENDED_LEVEL; 0 * colour and 0 * 0 are the same +0).  A chunk
-        # whose "any mirror" flag comes back false is returned unblended -- and then holds no ray above the threshold, so no
-        # row of it was left out.  Not with roughness jitters, a placed mirror, reflection substitution or placed objects:
-        # those read or edit more of the level than the blend does.  (render_rays falls back to the launches of before when
-        # the pass is not one the fused kernel covers: fp32 arithmetic, another sample count, density-gradient normals.)
-        # Both routes give the same result, so the choice is one of speed alone, and it is made PER CHUNK from evidence: a chunk
-        # with no ray above the threshold is about 3 % slower through the ray-fused form than through the two-kernel path, one
-        # with every ray above it 5 % faster, and the two meet at BLENDED_BREAK_EVEN.  The evidence is the share of rays above
-        # the threshold in the chunk of this level whose count was last known (neighbouring chunks of a frame, and the same
-        # chunks of the frame before, see much the same scene); it is kept per model across calls (_MIRROR_FRACTION).  Without
-        # evidence -- the first chunk ever rendered with a model -- the launches of before are used, so a scene with few mirror
-        # pixels never takes the slower route for more than the chunks it takes to notice a change.
-        # `blended_level=True` / `False` forces the choice (tests, measurements).
-        can_blend = bool(level < args.max_recursive_level and trace_flag and test_time and blend_mode is not False
-                         and not (rough or rough_rows or place or subst or objects or multi))
-        evidence = mirror_fraction.get(level)
-        blended = can_blend and (blend_mode is True or (evidence is not None and evidence >= BLENDED_BREAK_EVEN))
-        count_it = can_blend and blend_mode is not True
-        r = render_rays(models, embeddings, rays_chunk, N_samples, use_disp, 0, 0, N_importance, chunk,
-                        white_back, test_time=test_time,
-                        compute_normal=trace_flag and (not args.predict_normal),
-                        only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
-                        current_epoch=fine_epoch + 1, _guard=False, _maps_only=maps_only or rgb_depth,
-                        _rgb_depth_only=rgb_depth, _blended_level=blended)
-        r[f"rgb_{sel}_reflect"] = torch.zeros_like(r[f"rgb_{sel}"])
-        r[f"depth_{sel}_reflect"] = torch.zeros_like(r[f"depth_{sel}"])
-        if placed is not None and not object_chain:                       # the K-object rule, ahead of the hard clip
-            _merge_objects(r, rays_chunk, placed, args.near, used_k, placed_renderers)
-        elif placed is not None:                                          # the same list through the single-object launches
-            for k, o in enumerate(placed):
-                _merge_object(r, rays_chunk, o["xform"], args.near, None if used_k is None else used_k[k:k + 1],
-                              placed_renderers[k], o["bounds"])
-        elif objects:                                                     # eval.py:173-291, ahead of the hard clip
-            _merge_object(r, rays_chunk, obj_xform, args.near, obj_used, render_object, obj_bounds)
-        mask = None
-        for key in (f"mirror_mask_{sel}", "mirror_mask_fine", "mirror_mask_coarse"):
-            if key in r:
-                mask = r[key]
-                break
-        # in place (eval.py:303-307); at the last level nothing branches on "any mirror pixel": no host read, so the next
-        # chunk's launches queue behind this pass without a stream sync.  A new mirror (eval.py:311-320) makes every level
-        # below the last one trace; it is merged into the mask right behind the threshold, and its flag is the one read.
-        last = level >= args.max_recursive_level or not (trace_flag or place or multi)
-        edit = None
-        if place and not last:
-            edit = lambda flag: _place_mirror(r, rays_chunk, sel, plane, args.near, flag)  # noqa: E731
-        # (with a roughness per mirror every level that places mirrors keeps its index: the std of a ray follows the mirror it
-        # took at THAT level; only level 0's is returned.  exclude_source_mirror keeps it too: it is the next level's `source`)
-        if multi and (level == 0 or ((rough_rows or exclude) and not last)):      # the mirror each ray took; -1 where the list is not applied
-            r["new_mirror_index"] = torch.full((rays_chunk.shape[0],), -1, dtype=torch.int32, device=rays_chunk.device)
-        if multi and not last:
-            edit = lambda flag: _place_mirrors(r, rays_chunk, sel, mirrors_packed, args.near, flag, r.get("new_mirror_index"),  # noqa: E731
-                                               source, exclude)
-        pending, any_mirror, counted = None, False, None
-        if mask is not None:
-            if host_flags is not None and not last and rays_chunk.shape[0]:
-                pending = _threshold_async(mask, host_flags, slot, edit)
-                if count_it:      # the count follows the flag to pinned memory; stage_b reads it behind its own event
-                    host = host_counts[slot:slot + 1]
-                    host.copy_(torch.count_nonzero(mask).view(1), non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    counted = (host, ev)
-            else:
-                any_mirror = _threshold_(mask, want_any=not last, edit=edit)
-                if count_it and rays_chunk.shape[0]:
-                    mirror_fraction[level] = (int(torch.count_nonzero(mask).item()) if any_mirror else 0) / rays_chunk.shape[0]
-        return r, rays_chunk, level, mask, any_mirror, pending, counted
-
-    def render_field(obj_rays, dnerf, time, field_models, field_embeddings):
-        if dnerf is not None:
-            # eval.py:233-259: the time in column 8, the normalised directions behind it (a plain division); near and far are
-            # the rays' own columns 6 and 7; samples, background and models come from the OBJECT's configuration
-            d = obj_rays[:, 3:6]
-            batch = torch.cat([obj_rays, torch.full_like(obj_rays[:, :1], time), d / torch.norm(d, dim=-1, keepdim=True)], -1)
-            o = render_rays_dnerf(batch, **dict(dnerf, _frame_time=time))
-            return {"rgb_fine": o["rgb_map"], "depth_fine": o["depth_map"], "opacity_fine": o["acc_map"]}
-        # eval.py:221-232: only colour, depth and opacity of this render are read -- the maps-only path
-        return render_rays(field_models, field_embeddings, obj_rays, N_samples, use_disp, 0, 0, N_importance, chunk, white_back,
-                           test_time=True, compute_normal=False, _guard=False, _maps_only=True, _rgb_depth_only=True)
-
-    def render_object(obj_rays):
-        return render_field(obj_rays, obj_dnerf, frame_time, obj_models, obj_embeddings)
-
-    def placed_renderer(o):
-        if o["kind"] == "d_nerf":
-            return lambda obj_rays: render_field(obj_rays, o["field"], o["time"], None, None)
-        field_models, field_embeddings = _object_system(o["field"])
-        return lambda obj_rays: render_field(obj_rays, None, None, field_models, field_embeddings)
-
-    placed_renderers = [placed_renderer(o) for o in placed] if placed is not None else None
-
-    def recurse(rays_chunk, level, source=None):
-        return stage_b(stage_a(rays_chunk, level, source=source))
-
-    def sources(r, index, m, n_rep=1):
-        # the `source` of the rays reflected off this level (mnrf_mirror_sources): the mirror each took here, through the compaction
-        return mirror_sources(r.get("new_mirror_index"), index, m, n_rep, r[f"rgb_{sel}"].device) if exclude else None
-
-    def stage_b(state):
-        r, rays_chunk, level, mask, any_mirror, pending, counted = state
-        if pending is not None:
-            any_mirror = _flag_ready(pending)
-        if counted is not None:
-            counted[1].synchronize()
-            mirror_fraction[level] = int(counted[0].item()) / rays_chunk.shape[0]
-        N = rays_chunk.shape[0]
-        dev = rays_chunk.device
-        only_in = not (level < 1)                                         # eval.py:159
-        trace = bool(mask is not None and any_mirror and (trace_flag or place or multi))     # eval.py:311-320, 503-504
-        if level >= args.max_recursive_level:
-            trace = False
-        if not trace or N == 0:
-            return r
-        # `mirror_mask = mirror_mask.bool()` then `.float()` (eval.py:307, 689): an exact 0.5 blends as 1
-        mask = (mask != 0).float()
-        normal = _pick_normal(r, sel)
-        nn0 = draw(N, dev) if (rough or rough_rows) else None             # eval.py:506-511
-        first_normal, first_std = normal, noise_std
-        if rough_rows:
-            # THE RULE of include/mnrf.h "A roughness per mirror" (DESIGN 4.4c): the std of a ray follows the mirror it took at
-            # this level.  The first reflection is the existing launch on normals that carry draw_0 * std already (no addition
-            # where the std is 0: the bits of the frame without roughness); with every std 0 there is nothing to add at all.
-            if jitters_possible:
-                std_rows, jitter_mask = _rough_rows(r.get("new_mirror_index"), mask, rough_row, scene_roughness)
-                first_normal = _perturb_normals(normal, nn0, std_rows)
-            nn0, first_std = None, 0.0                                    # (the draw is made either way: the order of draws)
-        sec, index, rdir = _reflect(rays_chunk, r[f"x_surface_{sel}"], first_normal, mask, only_in, nn0, first_std)
-        r["reflect_direction"] = rdir
-        if sec.shape[0] > 0:
-            if subst:                                                     # eval.py:550-613: no recursion below
-                _transform_rays(sec, xform)
-                # only rgb / depth of this render are read (eval.py:676-697): the maps-only path, without the density-gradient
-                # normals the reference also computes for it
-                r2 = render_rays(system_sub.models, system_sub.embeddings, sec.contiguous(), N_samples, use_disp, 0, 0,
-                                 N_importance, chunk, white_back, test_time=test_time, compute_normal=False,
-                                 only_one_field=one_field, only_one_field_fine_epoch=fine_epoch,
-                                 current_epoch=fine_epoch + 1, _guard=False, _maps_only=True, _rgb_depth_only=True)
-            else:
-                r2 = recurse(sec.contiguous(), level + 1, sources(r, index, sec.shape[0]))
-            if rough:                                                     # eval.py:622-674
-                # THE RULE of include/mnrf.h "Mirror roughness" (DESIGN 4.4b).  The reference adds the (M,3) colours of each
-                # jittered render, M = sum(mask), to the first secondary render, which at level 0 has N rows: that works only
-                # where every ray of the chunk is a mirror ray (SURVEY a14).  Here the sums go through the compaction's index,
-                # so a mirror ray gets the mean of its times + 1 samples and a ray of level 0 that is no mirror ray keeps the
-                # one sample it has; where M == N it is the reference's arithmetic.
-                times = args.trace_ray_times
-                keys = [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]
-                if times > 0:
-                    # the ONE compaction of the level's mask, and the one host read of its count: every jitter compacts through
-                    # the same mask.  At levels >= 1 the first _reflect above made both; at level 0, which reflects every
-                    # ray, mnrf_reflect_compact runs once more with compact = 1 for its index alone
-                    jit_index = index if only_in else _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, True,
-                                                               want_dir=False)[1]
-                    mj = jit_index.shape[0]
-                    acc_index = None if only_in else jit_index        # row of R: p at levels >= 1, index[p] at level 0
-                    for k in keys:
-                        r2[k] = r2[k].contiguous()
-                    finish = float(np.float32(1) / np.float32(times + 1))   # torch's `/ (times + 1)` on the device: see ROUGH_FINISH
-                if batch_jitter and times > 0:
-                    # The reference renders the `times` jittered reflections one after the other (run.sh:187: 64 of them,
-                    # each a full secondary render).  Rays are independent, so groups of them go through ONE recursion
-                    # call (one field launch per pass for the whole group) and the colours are added in the reference's
-                    # order.  Groups are sized to JITTER_RAYS rays (~2.5 GB of per-sample tensors at 64+128 samples).  A group
-                    # is one buffer of draws (one (N,3) draw per jitter, in the reference's order), one mnrf_reflect_jitter_fan,
-                    # one recursion call and one mnrf_jitter_mean per colour key.
-                    # Not used when a test injects the draws: their order interleaves with the nested levels' draws.
-                    g = 0
-                    while g < times:
-                        n_g = max(1, min(times - g, JITTER_RAYS // max(1, mj)))
-                        noise = torch.stack([draw(N, dev) for _ in range(n_g)]) if noise_iter is not None \
-                            else torch.randn(n_g, N, 3, device=dev)
-                        r3 = recurse(_reflect_fan(rays_chunk, r[f"x_surface_{sel}"], normal, noise, noise_std, jit_index), level + 1)
-                        g += n_g
-                        for k in keys:
-                            _jitter_mean(r2[k], r3[k], acc_index, mj, n_g, finish if g >= times else None)
-                elif times > 0:
-                    for j in range(times):
-                        s2, _, _ = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, mask, True, draw(N, dev),
-                                            noise_std, want_dir=False)
-                        r3 = recurse(s2.contiguous(), level + 1)
-                        for k in keys:
-                            _jitter_mean(r2[k], r3[k], acc_index, mj, 1, finish if j == times - 1 else None)
-                else:
-                    for k in keys:
-                        r2[k] = r2[k] / (times + 1)
-            elif rough_rows and jitters_possible:
-                # The branch above with J = {mask != 0 and std > 0} in the mask's place: ONE compaction of J and the read of its
-                # count (the second and last of the level), the fan with the std per ray, the same groups, sums and finish.  A
-                # mirror ray outside J keeps its one sample; an empty J takes no further draw.
-                keys = [f"rgb_{typ}" for typ in ("coarse", "fine") if f"rgb_{typ}" in r2]
-                jit_index = _reflect(rays_chunk, r[f"x_surface_{sel}"], normal, jitter_mask, True, want_dir=False)[1]
-                mj = jit_index.shape[0]
-                if mj > 0:
-                    if only_in:       # row of R: the ray's rank in the mask's compaction, from the two indices, on the device
-                        rank = torch.empty(N, dtype=torch.int32, device=dev)
-                        rank[index.long()] = torch.arange(index.shape[0], dtype=torch.int32, device=dev)
-                        acc_index = rank[jit_index.long()]
-                    else:
-                        acc_index = jit_index
-                    for k in keys:
-                        r2[k] = r2[k].contiguous()
-                    finish = float(np.float32(1) / np.float32(rough_times + 1))
-                    g = 0
-                    while g < rough_times:
-                        n_g = max(1, min(rough_times - g, JITTER_RAYS // mj)) if batch_jitter else 1
-                        if batch_jitter:
-                            noise = torch.stack([draw(N, dev) for _ in range(n_g)]) if noise_iter is not None \
-                                else torch.randn(n_g, N, 3, device=dev)
-                            s2 = _reflect_fan_rows(rays_chunk, r[f"x_surface_{sel}"], normal, noise, std_rows, jit_index)
-                        else:         # one by one: a jitter is mnrf_perturb_normals, then mnrf_reflect_compact on J's mask
-                            s2 = _reflect(rays_chunk, r[f"x_surface_{sel}"], _perturb_normals(normal, draw(N, dev), std_rows),
-                                          jitter_mask, True, want_dir=False)[0].contiguous()
-                        r3 = recurse(s2, level + 1, sources(r, jit_index, mj, n_g))      # (one by one: J's own compaction, n_g = 1)
-                        g += n_g
-                        for k in keys:
-                            _jitter_mean(r2[k], r3[k], acc_index, mj, n_g, finish if g >= rough_times else None)
-            r[f"rgb_{sel}"], refl = _blend(r[f"rgb_{sel}"], r2[f"rgb_{sel}"], index, mask, True)
-            r[f"rgb_{sel}_reflect"] = refl
-            if only_in:
-                d = torch.zeros_like(r[f"depth_{sel}"])
-                d[index.long()] = r2[f"depth_{sel}"]
-                r[f"depth_{sel}_reflect"] = d
-            else:
-                r[f"depth_{sel}_reflect"] = r2[f"depth_{sel}"]
-        return r
-
-    # MNRF_EVAL_PIPELINE (default on): chunk k+1's primary pass is queued before chunk k's reflected pass, so the
-    # per-sample tensors of TWO chunks are alive at once (~2 x 3 KB/ray x chunk: 200 MB at chunk 32768) -- set it to 0 on a
-    # memory-tight device.  With random roughness draws (no injection) a guard retry draws afresh, as any re-render would.
-    results = defaultdict(list)
-    # to_cpu="maps" on the GPU: the per-ray maps of a chunk travel to PINNED staging buffers on a side stream while the next
-    # chunk renders (pageable destinations made every copy synchronous: 33 ms per 51 MB frame); one host-side copy out of
-    # the staging buffers at the end hands back ordinary tensors the caller owns
-    stage_maps = to_cpu == "maps" and rays.is_cuda
-    staged, staged_rows, hold = {}, defaultdict(int), []
-    copy_stream = _copy_stream(rays.device) if stage_maps else None
-    starts = list(range(0, rays.shape[0], chunk))
-    pipelined = rays.is_cuda and not (rough or rough_rows) and len(starts) > 1 and os.environ.get("MNRF_EVAL_PIPELINE", "1") != "0"
-    host_flags = torch.zeros(2, dtype=torch.int32).pin_memory() if pipelined else None
-    host_counts = torch.zeros(2, dtype=torch.int64).pin_memory() if pipelined else None
-    chunk_source = lambda i: source_all[i:i + chunk] if source_all is not None else None  # noqa: E731
-    ahead = stage_a(rays[:chunk].contiguous(), 0, host_flags, 0, chunk_source(0)) if (pipelined and starts) else None
-    for n_c, i in enumerate(starts):
-        if pipelined:
-            state = ahead
-            ahead = stage_a(rays[starts[n_c + 1]:starts[n_c + 1] + chunk].contiguous(), 0, host_flags, (n_c + 1) % 2,
-                            chunk_source(starts[n_c + 1])) if n_c + 1 < len(starts) else None
-            out = stage_b(state)
-        else:
-            out = recurse(rays[i:i + chunk].contiguous(), 0, chunk_source(i))
-        if stage_maps:
-            done = torch.cuda.Event()
-            done.record()
-            copy_stream.wait_event(done)
-        for k, v in out.items():
-            if to_cpu == "maps" or maps_only:
-                if v.dim() <= 2 and (v.dim() == 1 or v.shape[1] <= 3):     # per-ray maps only
-                    if stage_maps:
-                        buf = staged.get(k)
-                        if buf is None:
-                            buf = staged[k] = _pinned(k, rays.shape[0], tuple(v.shape[1:]), v.dtype)
-                        r0 = staged_rows[k]
-                        with torch.cuda.stream(copy_stream):
-                            buf[r0:r0 + v.shape[0]].copy_(v, non_blocking=True)
-                        staged_rows[k] = r0 + v.shape[0]
-                        hold.append(v)      # (alive until the copies have run)
-                    else:
-                        results[k] += [v.to("cpu", non_blocking=True) if to_cpu == "maps" else (v.cpu() if to_cpu else v)]
-            else:
-                results[k] += [v.cpu() if to_cpu else v]
-    if stage_maps:
-        copy_stream.synchronize()
-        hold.clear()
-        for k, buf in staged.items():
-            results[k] = [buf[:staged_rows[k]].clone()]      # out of the (re-used) staging buffer into a tensor of the caller's
-    elif to_cpu == "maps" and rays.is_cuda:
-        torch.cuda.current_stream().synchronize()
-    # range guard of the split arithmetic, once per call (= per frame): a tripped model is on the fp32 kernels now
-    from .mirror_nerf import check_guard, release_transient
-    guarded = list(models.values()) + (list(system_sub.models.values()) if system_sub is not None else []) + \
-        (list(obj_models.values()) if obj_models is not None else [])      # (a D-NeRF object runs fp32 only: no guard)
-    for o in placed or ():
-        if o["kind"] == "nerf_pl":
-            guarded += [m for m in _object_system(o["field"])[0].values() if not any(m is g for g in guarded)]
-    if rays.shape[0] and not kwargs.get("_guard_retry") and check_guard(guarded):
+    c = _resolve_call(models, rays, N_samples, N_importance, use_disp, chunk, kwargs)
+    c.embeddings = embeddings
+    results = _run_chunks(c)
+    # range guard of the split arithmetic, once per call (= per frame): a tripped model is on the fp32 kernels now, and the
+    # chunks are rendered once more, from the same resolved call
+    if c.rays.shape[0] and check_guard(c.guarded):
         try:
-            return batched_inference(models, embeddings, rays, N_samples, N_importance, use_disp, chunk,
-                                     **dict(kwargs, _guard_retry=True))
+            results = _run_chunks(c)
         finally:
-            release_transient(guarded)      # (a range-only trip: this frame on fp32, the next one on split again)
-    if used_k is not None:
-        obj_used.copy_(used_k if obj_used.numel() == used_k.numel() else used_k.sum(dtype=torch.int32).view(1))
+            release_transient(c.guarded)      # (a range-only trip: this frame on fp32, the next one on split again)
+    if c.used_out is not None:
+        c.used_out.copy_(c.used if c.used_out.numel() == c.used.numel() else c.used.sum(dtype=torch.int32).view(1))
     return {k: torch.cat(v, 0) for k, v in results.items()}

@@ -275,6 +275,43 @@ def test_frame_driver_and_training_step_fall_back():
     assert torch.equal(r3["rgb_fine"], r2["rgb_fine"])
 
 
+def test_object_used_counts_one_pass_after_a_guard_trip():
+    """A frame whose scene models trip the guard is rendered twice; object_used counts the second pass alone.  The 16 x 16 frame
+    of tests/test_hip_mirrors.py in three chunks of 96, the nerf_pl object of fixture G26 through the single-object keywords
+    (near = 1e9: the scene hides nothing, so rays do take the object): object_used and every map are those of the same call on
+    scene models pinned to fp32 beforehand, which trips nothing."""
+    import mirror_nerf_amd as M
+    from mirror_nerf_amd import mirror_nerf as MN
+    from mirror_nerf_amd import synthetic as SY
+    from tests import test_hip_mirrors as TM
+    from tests import test_hip_objects as TO
+    from tests.golden import fixtures as FX
+    meta = FX.Fixture("g26_object_office_l2").meta
+    tweaks = SY.ALL_MIRROR + [["xyz_encoding_6.0.weight", "mul", 1e8]]
+    rays = torch.from_numpy(TM.camera_rays(TM.EYE, TM.TARGET)).to(DEV)
+    args = dict(ARGS, app_reflect_newly_placed_objects=True, obj_model_type="nerf_pl", near=1e9)
+
+    def frame(models):
+        used = torch.full((1,), 5, dtype=torch.int32, device=DEV)
+        out = M.batched_inference(models, _emb(), rays, 64, 64, False, 96, args=args, trace_secondary_rays=True, to_cpu=False,
+                                  maps_only=True, system_obj=TO._object_system(meta), new_object=meta["new_object"], object_used=used)
+        return out, int(used.item())
+    models = _models(tweaks)
+    with pytest.warns(RuntimeWarning):
+        got, used = frame(models)
+    assert all(MN.precision_of(m) == "fp32" for m in models.values())
+    pinned = _models(tweaks)
+    for m in pinned.values():
+        m.__dict__["_mnrf_precision"] = "fp32"
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        want, want_used = frame(pinned)
+    assert used == want_used and 0 < used <= 2 * rays.shape[0]          # (two levels render the object)
+    assert set(got) == set(want) and {"rgb_fine", "depth_fine", "mirror_mask_fine", "rgb_fine_reflect"} <= set(got)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k].cpu().numpy(), want[k].cpu().numpy(), equal_nan=True), k
+
+
 def test_guard_costs_no_accuracy_on_clean_models():
     """verify_split (both arithmetics on the model's own samples) still reports fp32-noise-class differences."""
     from mirror_nerf_amd import mirror_nerf as MN
