@@ -677,7 +677,12 @@ int mnrf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
  * indexing: one stream sync in the middle of every step).  Every `_n` entry point below is its namesake with ONE more argument
  * in front of `stream`: `n_live`, a DEVICE int32 holding the number of rows (rays; samples / spr for the field entry points)
  * that exist.  The row-count argument becomes the CAPACITY the buffers are sized for: the launch is sized for it, workgroups
- * past the live rows leave at once, rows past them are neither read nor written.  n_live == null: exactly the namesake.  With
+ * past the live rows leave at once, rows past them are neither read nor written.  n_live == null: exactly the namesake.  The
+ * field entry points at the end of this section (mnrf_field_forward_train_n, mnrf_field_backward_planes_n,
+ * mnrf_field_backward2_planes_n, mnrf_dw_planes2_n) clamp a count outside [0, capacity]: below zero nothing exists, above the
+ * capacity every row does.  They work in whole 128-sample tiles: the mask words and operand planes of the first
+ * ceil(*n_live * spr / 128) tiles are written (what the namesake writes for that many samples), nothing past them; with nothing
+ * live no output is written, an overwriting mnrf_dw_planes2_n leaves zeros and an accumulating one changes nothing.  With
  * them the forward, backward and optimizer launches of a whole step are a fixed sequence -- capturable as ONE hipGraph
  * (mirror_nerf_amd.training.GraphedTrainStep).  Field entry points: MNRF_SPLIT_F16 | MNRF_TRAIN_PLANES route only. */
 int mnrf_embed_n(const float* x, int64_t n, int c, int n_freqs, float* out, const int32_t* n_live, void* stream);

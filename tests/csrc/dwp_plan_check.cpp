@@ -1,8 +1,10 @@
 // Host-side check of the work plan of the weight-gradient GEMM (mirror_nerf_amd/csrc/mnrf_dwp.h), compiled with g++ by
 // tests/test_dwp_plan_cpu.py: the same inline functions the kernel and its launcher use.
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <set>
+#include <string>
 #include <vector>
 
 #include "mnrf_dwp.h"
@@ -55,7 +57,52 @@ static int check(const DwpPlan& p) {
     return 0;
 }
 
-int main() {
+// `dwp_plan_check plans <cus> <n_eval> <n_sb> <kind> ... [<cus> <n_eval> ...]`: what the header gives for plans stated on the command
+// line -- the layout of DwpDevPlan, the job weights, dwp_sample_blocks at some sample counts, then per plan T, G and the owners
+// [g_lo, g_hi] of every virtual job as the launcher and dwp_plan_kernel form them (1 0 where it has no stages).
+// tests/test_dwp_plan_ref_cpu.py holds tests/dwp_plan_ref.py to this output.
+static int print_plans(int argc, char** argv) {
+    std::printf("layout sizeof %zu n_eval %zu n_sb %zu kind %zu G %zu T %zu g_lo %zu g_hi %zu floats %d jobs %d max_eval %d\n",
+                sizeof(DwpDevPlan), offsetof(DwpDevPlan, plan.n_eval), offsetof(DwpDevPlan, plan.n_sb), offsetof(DwpDevPlan, plan.kind),
+                offsetof(DwpDevPlan, plan.G), offsetof(DwpDevPlan, plan.T), offsetof(DwpDevPlan, g_lo), offsetof(DwpDevPlan, g_hi),
+                DWP_DEVPLAN_FLOATS, DWP_JOBS, DWP_MAX_EVAL);
+    std::printf("weights");
+    for (int j = 0; j < DWP_JOBS; ++j) std::printf(" %d", dwp_weight(j));
+    std::printf("\n");
+    std::printf("sample_blocks");      // dwp_sample_blocks around the tile edges: pairs of sample count and blocks
+    for (long long B : {0LL, 1LL, 31LL, 32LL, 33LL, 127LL, 128LL, 129LL, 192LL, 255LL, 256LL, 257LL, 384LL, 512LL, 513LL, 576LL, 960LL, 4173LL, 32769LL})
+        std::printf(" %lld %lld", B, dwp_sample_blocks(B));
+    std::printf("\n");
+    int a = 2;
+    while (a < argc) {
+        if (a + 2 > argc) { std::printf("bad arguments\n"); return 2; }
+        const int cus = std::atoi(argv[a]);
+        DwpPlan p;
+        p.n_eval = std::atoi(argv[a + 1]);
+        a += 2;
+        if (p.n_eval < 1 || p.n_eval > DWP_MAX_EVAL || a + 2 * p.n_eval > argc) { std::printf("bad arguments\n"); return 2; }
+        for (int e = 0; e < DWP_MAX_EVAL; ++e) { p.n_sb[e] = 0; p.kind[e] = 0; }
+        for (int e = 0; e < p.n_eval; ++e, a += 2) { p.n_sb[e] = std::atoi(argv[a]); p.kind[e] = std::atoi(argv[a + 1]) ? 1 : 0; }
+        p.T = dwp_total(p);
+        p.G = dwp_pick_G(p.T, cus);
+        std::printf("plan T %lld G %d owners", p.T, p.G);
+        long long P = 0;
+        for (int j = 0; j < DWP_JOBS; ++j) {
+            const int w = dwp_weight(j);
+            for (int e = 0; e < p.n_eval; ++e) {
+                const int n = dwp_stages(p, j, e);
+                if (n > 0) std::printf(" %d %d", dwp_owner(p, P), dwp_owner(p, P + (long long)(n - 1) * w));
+                else std::printf(" 1 0");
+                P += (long long)n * w;
+            }
+        }
+        std::printf("\n");
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "plans") return print_plans(argc, argv);
     // job table sanity: sections inside the plane layouts, weights as documented
     int wsum = 0;
     for (int j = 0; j < DWP_JOBS; ++j) {
